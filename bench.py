@@ -235,6 +235,24 @@ def emit_report(full, secondaries=None):
     emit(line)
 
 
+DUMP_LIMIT = 64 << 20
+
+
+def dump_outputs(out_dir, arrays):
+    """--dump-outputs: the arrays a caller of the timed path received from its last step, one DIR/<name>.npy each (float32 / float64 only),
+    so that two builds can be compared output for output on the same seeded inputs."""
+    arrays = {k: np.ascontiguousarray(v) for k, v in arrays.items()}
+    for k, v in arrays.items():
+        if v.dtype not in (np.float32, np.float64):
+            raise TypeError(f"--dump-outputs: {k} is {v.dtype}, not float32 / float64")
+    total = sum(v.nbytes for v in arrays.values())
+    if total > DUMP_LIMIT:
+        raise ValueError(f"--dump-outputs: {total} bytes > {DUMP_LIMIT}")
+    os.makedirs(out_dir, exist_ok=True)
+    for k, v in arrays.items():
+        np.save(os.path.join(out_dir, k + ".npy"), v)
+
+
 def spawn_ranks(n):
     """`python bench.py --gpus N` without a launcher: start N fresh copies of this script, one rank per GPU (RANK / LOCAL_RANK /
     WORLD_SIZE / MASTER_* in their environment, exactly what torch.distributed.run would set), BEFORE anything here has
@@ -1049,7 +1067,12 @@ def main():
     ap.add_argument("--timed-only", action="store_true", help="label path: only the warm-up, the timed steps and the per-launch profiled repeat of the "
                     "same steps -- no seam calls, no isolated single-stream pass, no bf16 parity handle -- so that a rocprofv3 --stats run of this "
                     "command averages exactly the launches `roofline.avg_launch_ms` averages (scripts/prof_label.sh)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="label path: after the timed steps, write the rewards of the last timed step (float32, one per frame) to DIR/rewards.npy "
+                         "(rank r > 0: DIR/rewards_rank<r>.npy); the inputs are seeded, so two builds can be compared output for output")
     a = ap.parse_args()
+    if a.dump_outputs and a.path != "label":
+        ap.error("--dump-outputs is implemented for the label path (the headline workload) only")
     if a.mode is None:
         a.mode = "f16"  # IEEE-half MFMA operands on every path: the 16-bit mode that meets the parity bars (bf16 stays selectable)
     if a.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -1144,6 +1167,8 @@ def main():
         elapsed = float(t.item())
     rewards = d_rewards.download(np.float32, a.batch)
     assert np.isfinite(rewards).all(), "non-finite rewards"
+    if a.dump_outputs:  # d_rewards still holds the last timed step's rewards (nothing has been enqueued since)
+        dump_outputs(a.dump_outputs, {"rewards" if rank == 0 else f"rewards_rank{rank}": rewards})
 
     # ---- the S2 seam as the reference calls it (label_reward.py:132-146: host frames in, host rewards out), OUTSIDE the timed
     # region: arp_clip_label incl. the H2D upload over PCIe and the D2H of the rewards.  Never `value`.

@@ -125,3 +125,23 @@ def test_multi_gpu_lines_certify_their_rank_count_on_gloo():
                                               "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f16", "data": "synthetic",
                                               "config": {"workload": "w"}, "roofline": {}, "cpu_baseline": None, "rccl": res[0][1], "ranks_seen": res[0][2]}))
     assert '"rccl_nranks": [2]' in line and len(line) < 4096
+
+
+def test_dump_outputs_writes_float_arrays_and_refuses_the_rest(tmp_path):
+    """--dump-outputs: one DIR/<name>.npy per array, float32 / float64 only, at most 64 MB in all"""
+    import numpy as np
+    r = np.linspace(-1, 1, 1024, dtype=np.float32)
+    bench.dump_outputs(str(tmp_path / "d"), {"rewards": r})
+    got = np.load(tmp_path / "d" / "rewards.npy")
+    assert got.dtype == np.float32 and np.array_equal(got, r)
+    with pytest.raises(TypeError):
+        bench.dump_outputs(str(tmp_path / "e"), {"x": np.zeros(4, np.float16)})
+    with pytest.raises(ValueError):
+        bench.dump_outputs(str(tmp_path / "f"), {"x": np.zeros((bench.DUMP_LIMIT >> 3) + 1, np.float64)})
+    assert not (tmp_path / "e").exists() and not (tmp_path / "f").exists()
+
+
+def test_dump_outputs_is_refused_off_the_label_path():
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--path", "policy", "--dump-outputs", "x"], cwd=ROOT,
+                       capture_output=True, text=True, timeout=120)
+    assert r.returncode == 2 and "--dump-outputs" in r.stderr
