@@ -45,6 +45,14 @@ class FtCfg(C.Structure):
         (n, C.c_float) for n in ("gamma", "logit_scale", "weight_decay", "b1", "b2", "eps")] + [("goal_conditioned", C.c_int32)]
 
 
+class GemmSite(C.Structure):
+    """arp_gemm_site (include/arp_hip.h): one product GEMM instance on device buffers, for arp_op_gemm_site"""
+    _fields_ = [("name", C.c_char_p)] + [(n, C.c_int32) for n in ("mode", "force", "M", "N", "K", "lda", "ldr", "ldo")] + [
+        (n, C.c_void_p) for n in ("A", "W", "bias", "resid", "out", "ln_stats", "ln_c")] + [("ln_parts", C.c_int32), ("ln_eps", C.c_float)] + [
+        ("xb_out", C.c_void_p), ("ldxb", C.c_int32), ("split3", C.c_int32), ("stats_out", C.c_void_p)] + [
+        (n, C.c_int32) for n in ("plan", "sd", "sw")] + [("x4_out", C.c_void_p), ("dx4_out", C.c_void_p), ("ld4", C.c_int32)]
+
+
 class EncCfg(C.Structure):
     _fields_ = [(n, C.c_int32) for n in ("patch", "width", "layers", "heads", "mlp_ratio", "img_res", "mode", "device", "max_frames",
                                           "attn_impl")]
@@ -190,6 +198,7 @@ SIGNATURES = {
     "arp_op_gemm_nt": (_i, [_i, _i, _fp, _fp, _fp, _fp, _fp, _i, _i, _i]),
     "arp_op_skinny_gemm": (_i, [_i, _i, _fp, _fp, _fp, _fp, _fp, _i, _i, _i, _i, _fp, _fp, _f, _fp]),
     "arp_op_gemm_f16c": (_i, [_i, _fp, _fp, _fp, _fp, _i, _i, _i, _i32p]),
+    "arp_op_gemm_site": (_i, [C.POINTER(GemmSite)]),
     "arp_op_gemm_fp8": (_i, [_i, _fp, _fp, _fp, _fp, _fp, _i, _i, _i, _f, _i, _f]),
     "arp_op_gemm_bench": (_i, [_i, _i, _i, _i, _i, _i, _i, _i, _i, _fp]),
     "arp_op_gemm_tn": (_i, [_i, _i, _i, _fp, _fp, _fp, _i, _i, _i, _f]),

@@ -11,6 +11,7 @@
 
 #include "../../include/arp_hip.h"
 #include "attention.h"
+#include "enc_internal.h"
 #include "common.h"
 #include "gemm.h"
 #include "gemm256.h"
@@ -1445,6 +1446,32 @@ int arp_op_gemm_nt(int mode, int act, const float* A, const float* W, const floa
     if (!A || !W || !out || M <= 0 || N <= 0 || K <= 0) return fail("bad argument");
     if (mode == ARP_MODE_F16) return op_gemm<f16_t>(act, A, W, bias, resid, out, M, N, K);
     return mode == ARP_MODE_BF16 ? op_gemm<bf16_t>(act, A, W, bias, resid, out, M, N, K) : op_gemm<float>(act, A, W, bias, resid, out, M, N, K);
+}
+
+}  // extern "C"
+
+// the CLIP towers' four GEMM instances (run_blocks<T, ACT_QGELU, 0> above), by name
+template <typename T> static int op_gemm_site_vit(const arp_gemm_site& d, const std::string& s) {
+    if (s == "vit.qkv") return tower_gemm_site<T, T, ACT_NONE, false, SITE_QKV>(d);
+    if (s == "vit.c_fc") return tower_gemm_site<T, T, ACT_QGELU, false, SITE_FC1>(d);
+    if (s == "vit.out_proj") return tower_gemm_site<T, float, ACT_NONE, true, SITE_OUT>(d);
+    if (s == "vit.c_proj") return tower_gemm_site<T, float, ACT_NONE, true, SITE_FC2>(d);
+    return fail("gemm_site: unknown instance " + s);
+}
+
+extern "C" {
+
+int arp_op_gemm_site(const arp_gemm_site* d) {
+    if (!d || !d->name || !d->A || !d->W || d->M <= 0 || d->N <= 0 || d->K <= 0) return fail("bad argument");
+    const std::string s(d->name);
+    int rc;
+    if (s.rfind("m3ae.", 0) == 0) rc = enc_op_gemm_site(*d);
+    else if (d->mode == ARP_MODE_F16) rc = op_gemm_site_vit<f16_t>(*d, s);
+    else if (d->mode == ARP_MODE_BF16) rc = op_gemm_site_vit<bf16_t>(*d, s);
+    else return fail("gemm_site: 16-bit modes only");
+    ARP_TRY(rc);
+    ARP_HIP_OK(hipDeviceSynchronize());
+    return 0;
 }
 
 }  // extern "C"

@@ -452,6 +452,35 @@ static int forward_part(arp_enc* c, arp_enc::Ws& w, hipStream_t stream, const fl
     return forward_chunk<float>(c, w, stream, img, nb, out);
 }
 
+// the encoder's GEMM instances (forward_chunk / forward_chunk_x3 / forward_chunk_c above), by name
+template <typename T> static int enc_gemm_site_t(const arp_gemm_site& d, const std::string& s) {
+    if (s == "m3ae.qkv") return tower_gemm_site<T, T, ACT_NONE, false, 8 + SITE_QKV>(d);
+    if (s == "m3ae.c_fc") return tower_gemm_site<T, T, ACT_GELU_TANH, false, 8 + SITE_FC1>(d);
+    if (s == "m3ae.out_proj") return tower_gemm_site<T, float, ACT_NONE, true, 8 + SITE_OUT>(d);
+    if (s == "m3ae.c_proj") return tower_gemm_site<T, float, ACT_NONE, true, 8 + SITE_FC2>(d);
+    return fail("gemm_site: unknown instance " + s);
+}
+int enc_op_gemm_site(const arp_gemm_site& d) {
+    const std::string s(d.name);
+    if (s == "m3ae.x3.c_fc") return tower_gemm_site<f16_t, float, ACT_GELU_TANH, false, 8 + SITE_FC1>(d);
+    if (s == "m3ae.f16c.c_fc" || s == "m3ae.f16c.c_proj") {
+        // K is Kc, the binary16 width of a row; A / W are operand rows as the encoder lays them out (gemm_c); the plain instance (plan 0) has no fp4 side output
+        if (d.plan < 1 || d.plan > 2) return fail("gemm_site: f16c plans 1 and 2 only");
+        Profiler prof;
+        TowerCtx t;
+        t.prof = &prof;
+        if (s == "m3ae.f16c.c_fc")
+            return gemm_c<ACT_GELU_TANH, false, f16_t, 8 + SITE_FC1>(nullptr, t, "op.gemm_site", d.A, d.W, d.plan, d.sd, d.sw, d.bias, nullptr, d.out, d.M, d.N,
+                                                                      d.K, d.ldo ? d.ldo : d.N, d.x4_out, d.ld4, d.dx4_out);
+        if (d.x4_out || d.dx4_out) return fail("gemm_site: m3ae.f16c.c_proj has no fp4 side output");
+        return gemm_c<ACT_NONE, true, float, 8 + SITE_FC2>(nullptr, t, "op.gemm_site", d.A, d.W, d.plan, d.sd, d.sw, d.bias, d.resid, d.out, d.M, d.N, d.K,
+                                                          d.ldo ? d.ldo : d.N);
+    }
+    if (d.mode == ARP_MODE_F16) return enc_gemm_site_t<f16_t>(d, s);
+    if (d.mode == ARP_MODE_BF16) return enc_gemm_site_t<bf16_t>(d, s);
+    return fail("gemm_site: 16-bit modes only");
+}
+
 // Enqueues the encoder of `n` device-resident frames behind everything already on `stream`; `stream` continues behind the last part.  Safe under a
 // stream capture of `stream` (the part streams join the capture through the fork event and leave it through the join events), but every buffer must
 // exist beforehand: the first call of a geometry allocates and must run eagerly (arp_dt.hip runs two eager steps before it captures).

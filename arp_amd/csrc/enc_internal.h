@@ -3,8 +3,11 @@
 #include <hip/hip_runtime.h>
 
 struct arp_enc;
+struct arp_gemm_site;
 namespace arp {
 // images_dev: f32 NHWC [n, res, res, 3] in HBM; out_dev: f32 [n * tokens, width].  Enqueued on `stream`.
 int enc_forward_on(arp_enc* e, hipStream_t stream, const float* images_dev, int n, float* out_dev);
 int enc_geometry(arp_enc* e, int* tokens, int* width, int* img_res, int* device);
+// arp_op_gemm_site's "m3ae.*" instances (the encoder's own, in this unit)
+int enc_op_gemm_site(const arp_gemm_site& d);
 }  // namespace arp

@@ -85,6 +85,26 @@ struct GemmArgs {
 };
 constexpr int GEMM_SITE_ADAMW = 26;
 
+// Host-side refusal shared by the launchers (here and gemm256.h).  The folded-LayerNorm consumer and every side output -- xb_out / split3 / stats_out of the
+// f32 epilogue, the fp4 x4 / dx4 segments of gemm256's MIXC binary16 epilogue -- exist in the STAGED epilogues only (N and ldo multiples of 8, N, ldo and ldr
+// multiples of 4): a shape off that path would skip them silently and leave the next GEMM stale operand rows.  stats_out holds N / 128 segments per row, so a
+// ragged last segment would land in the next row's.  (tests/test_gemm_epilogues_gpu.py::test_launchers_refuse_what_the_epilogue_would_skip)
+template <typename OutT>
+inline int gemm_epilogue_refusal(const GemmArgs& g, bool fp4_side, const char* who) {
+    const bool staged = ((g.N | g.ldo | g.ldr) & 3) == 0 && ((g.N | g.ldo) & (sizeof(OutT) == 1 ? 15 : 7)) == 0 && !(g.flags & 2);
+    const bool fp4 = g.x8_shift >= 0 || g.dx4_out;
+    const std::string w(who);
+    if ((g.ln_stats || g.xb_out || g.stats_out || fp4) && !staged)
+        return fail(w + ": the folded LayerNorm and the side outputs need the staged epilogue (N, ldo % 8 == 0; ldr % 4 == 0)");
+    if (g.ln_stats && sizeof(OutT) != 2) return fail(w + ": the folded-LayerNorm consumer has a 16-bit output");
+    if ((g.stats_out || g.split3) && sizeof(OutT) != 4) return fail(w + ": stats_out / split3 belong to the f32 epilogue");
+    if (g.stats_out && g.N % 128) return fail(w + ": stats_out needs N % 128 == 0 (one (sum, sum of squares) pair per 128 columns)");
+    if (fp4 && !fp4_side) return fail(w + ": the fp4 side outputs exist on the MIXC binary16-output instances only");
+    if ((g.x8_shift >= 0 && !g.xb_out) || (g.split3 && !g.xb_out)) return fail(w + ": x8_shift / split3 without xb_out");
+    if (g.xb_out && sizeof(OutT) != 4 && g.x8_shift < 0) return fail(w + ": xb_out of a 16-bit output is the x4 segment (x8_shift >= 0)");
+    return 0;
+}
+
 constexpr int GEMM_BM = 128, GEMM_BN = 128, GEMM_THREADS = 256;
 constexpr int GEMM_ROW_BYTES = 128;                                   // one LDS row = one K-tile of one row
 constexpr int GEMM_STAGE_BYTES = (GEMM_BM + GEMM_BN) * GEMM_ROW_BYTES;  // 32 KiB
@@ -490,6 +510,7 @@ inline int launch_gemm_nt(const GemmArgs& g, hipStream_t stream) {
     if (g.N <= 0 || g.K % EPB != 0 || g.K <= 0 || g.lda % (16 / (int)sizeof(T)) != 0 || g.ldw % (16 / (int)sizeof(T)) != 0)
         return fail("gemm_nt: unsupported shape M=" + std::to_string(g.M) + " N=" + std::to_string(g.N) +
                     " K=" + std::to_string(g.K));
+    if (int rc = gemm_epilogue_refusal<OutT>(g, false, "gemm_nt")) return rc;
     // The staged epilogues (N, ldo multiples of 8) load their bias / folded-LayerNorm / residual fragments UNCONDITIONALLY from clamped addresses, and with no
     // bias or fold a dummy 16 bytes from A: that needs N >= 8 (implied), a 16-byte-aligned A and one whole readable row of it
     if (((g.N | g.ldo) & 7) == 0 && !(g.flags & 2) && ((reinterpret_cast<uintptr_t>(g.A) & 15) != 0 || (size_t)g.K * sizeof(T) < 16))

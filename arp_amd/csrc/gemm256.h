@@ -1136,6 +1136,7 @@ inline int launch_gemm256_nt(const GemmArgs& g, hipStream_t stream) {
     if (g.N <= 0 || g.K % EPB != 0 || g.K <= 0 || g.lda % (16 / (int)sizeof(T)) != 0 || g.ldw % (16 / (int)sizeof(T)) != 0)
         return fail("gemm256_nt: unsupported shape M=" + std::to_string(g.M) + " N=" + std::to_string(g.N) +
                     " K=" + std::to_string(g.K));
+    if (int rc = gemm_epilogue_refusal<OutT>(g, MIXC && __is_same(OutT, f16_t), "gemm256_nt")) return rc;
     if (g.ln_stats && G2_MASK_SITE(SITE)) return fail("gemm256_nt: no folded-LayerNorm epilogue in the masked-epilogue instances");
     if (g.ln_stats && (g.ln_parts < 1 || g.ln_parts > 8)) return fail("gemm256_nt: the folded-LayerNorm epilogue holds at most 8 partial sums per row (width <= 1024)");
     if (g.mask && (!G2_MASK_SITE(SITE) || sizeof(OutT) != 2 || ((g.N | g.ldo | g.ldm | g.ldr) & 7) || (g.flags & 3)))

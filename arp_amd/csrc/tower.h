@@ -218,6 +218,21 @@ static int tower_gemm(TowerCtx& c, const char* site, const void* A, const void* 
     //  slower, 5.3 vs 4.5 ms per step: the narrower wave tile's K loop loses more over 48 K-tiles than the rounding wins; removed)
     return launch_gemm_auto<T, OutT, ACT, RESID, SITE>(g, c.stream, force);
 }
+// arp_op_gemm_site (include/arp_hip.h): one tower GEMM as the tower launches it -- same instance, same routing (gemm_force, out_proj's kernel choice),
+// the fold / producer plumbing only when the descriptor carries it -- on the default stream, with no profiler and no latency path
+template <typename T, typename OutT, int ACT, bool RESID, int SITE, typename Site>
+static int tower_gemm_site(const Site& d) {
+    Profiler prof;
+    TowerCtx c;
+    c.prof = &prof;
+    c.gemm_force = d.force;
+    GemmFold f;
+    f.stats = d.ln_stats; f.c = d.ln_c; f.parts = d.ln_parts; f.inv_d = 1.0f / (float)d.K; f.eps = d.ln_eps;
+    f.xb_out = d.xb_out; f.ldxb = d.ldxb; f.stats_out = d.stats_out; f.split3 = d.split3;
+    const bool fold = d.ln_stats || d.xb_out || d.stats_out;
+    return tower_gemm<T, OutT, ACT, RESID, SITE>(c, "op.gemm_site", d.A, d.W, d.bias, RESID ? d.resid : nullptr, d.out, d.M, d.N, d.K, fold ? &f : nullptr,
+                                                 d.lda, d.ldr, d.ldo);
+}
 
 template <typename OutT>
 static int tower_layernorm(TowerCtx& c, const char* site, const float* in, size_t in_stride, OutT* out, int out_stride,

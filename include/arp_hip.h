@@ -430,6 +430,35 @@ int arp_op_adapter_dy(int mode, const float* dz, const float* Wi, const float* A
    kernels build them, out = A.W^T + bias (f32) with the weight rounding (plan 1) or both operand roundings (plan 2) corrected on the scaled fp4 MFMA;
    plan 0 = the plain binary16 product.  sd_sw[2] (optional): the power-of-two exponents of the e2m1 weight segments.  K % 256, N % 8. */
 int arp_op_gemm_f16c(int plan, const float* A, const float* W, const float* bias, float* out, int M, int N, int K, int* sd_sw);
+/* One launch of a GEMM instance the product itself launches, selected by name, on DEVICE buffers (arp_dev_malloc), through the tower's own routing
+ * (tower.h::tower_gemm, or arp_enc.hip::gemm_c for the f16c names).  Synchronises before it returns.  Names and instances (T = the mode's 16-bit type):
+ *   "vit.qkv" <T,T,none>  "vit.c_fc" <T,T,QuickGELU>  "vit.out_proj" / "vit.c_proj" <T,f32,none,+resid>            (the CLIP towers)
+ *   "m3ae.qkv" <T,T,none>  "m3ae.c_fc" <T,T,tanh-GELU>  "m3ae.out_proj" / "m3ae.c_proj" <T,f32,none,+resid>        (the M3AE encoder)
+ *   "m3ae.x3.c_fc" <f16,f32,tanh-GELU> (split3 producer of ARP_MODE_F16X3)
+ *   "m3ae.f16c.c_fc" <f16,f16,tanh-GELU,MIXC>  "m3ae.f16c.c_proj" <f16,f32,none,+resid,MIXC>                       (ARP_MODE_F16C; A / W are operand rows)
+ * Strides are in elements of the buffer's own type (0 = dense); ldxb as GemmArgs::ldxb.  force = TowerCtx::gemm_force (0 auto, 1 / 2 / 3). */
+typedef struct arp_gemm_site {
+    const char* name;
+    int mode, force;
+    int M, N, K, lda, ldr, ldo;
+    const void* A;
+    const void* W;
+    const float* bias;
+    const float* resid;
+    void* out;
+    const float* ln_stats; /* folded LayerNorm, consumer: [M][ln_parts][2] partial (sum, sum of squares), c[N], eps (1 / K is the width) */
+    const float* ln_c;
+    int ln_parts;
+    float ln_eps;
+    void* xb_out;          /* producer: operand-type copy ([hi | lo | hi] with split3) and per-128-column stats of the f32 output */
+    int ldxb, split3;
+    float* stats_out;
+    int plan, sd, sw;      /* f16c: correction plan of the weight rows and their e2m1 scales (2^sd, 2^sw) */
+    void* x4_out;          /* f16c c_fc: the e2m1 segments of the next product's operand rows (ld4 bytes per row) */
+    void* dx4_out;
+    int ld4;
+} arp_gemm_site;
+int arp_op_gemm_site(const arp_gemm_site* d);
 int arp_op_gemm_bench(int mode, int kernel, int act, int resid, int out_f32, int M, int N, int K, int iters, float* avg_ms);
 int arp_op_layernorm(const float* x, const float* w, const float* b, float* out, int rows, int D, float eps);
 /* qkv [B*N, 3*D] -> out [B*N, D]; impl 0 = MFMA (bf16 mode, head_dim 64 only), 1 = VALU. */
