@@ -40,21 +40,6 @@ struct HostTensor {
 
 using namespace arp;
 
-// Experiment (round 4, OFF by default): the part streams of a batch on DISJOINT halves of the chip (hipExtStreamCreateWithCUMask) instead of sharing all
-// 256 CUs -- ARP_CLIP_CUMASK=xcd: stream parity p gets the CUs whose index mod 8 is in [4 p, 4 p + 4) (whole XCDs, if the mask's bit order is the
-// round-robin over XCDs it is documented to be); =half: the low / high 128 mask bits.  Measured in profiles/r4_cumask.txt.
-static hipError_t create_part_stream(hipStream_t* st, int index) {
-    static const char* mode = getenv("ARP_CLIP_CUMASK");
-    if (!mode || !*mode || !strcmp(mode, "0")) return hipStreamCreateWithFlags(st, hipStreamNonBlocking);
-    uint32_t mask[8];
-    const int p = index & 1;
-    for (int w = 0; w < 8; ++w) {
-        if (!strcmp(mode, "xcd")) mask[w] = p ? 0xF0F0F0F0u : 0x0F0F0F0Fu;
-        else mask[w] = ((w < 4) == (p == 0)) ? 0xFFFFFFFFu : 0u;
-    }
-    return hipExtStreamCreateWithCUMask(st, 8, mask);
-}
-
 struct arp_clip {
     arp_clip_cfg cfg;
     hipStream_t stream = nullptr;
@@ -423,7 +408,7 @@ static int get_plan(arp_clip* c, int H, int W, int use_crop, ResizePlan** out, b
         return 0;
     }
     ResizePlan* p = new ResizePlan();
-    const int r = build_plan(H, W, use_crop, c->cfg.img_res, *p, small ? (getenv("ARP_PRE_TR_SMALL") ? atoi(getenv("ARP_PRE_TR_SMALL")) : 8) : 32);
+    const int r = build_plan(H, W, use_crop, c->cfg.img_res, *p, small ? 8 : 32);
     if (r != 0) {
         delete p;
         return r;
@@ -655,7 +640,7 @@ static int make_sibling(arp_clip* c) {
     s->copy_stream = nullptr;
     s->ev_copy.clear();
     for (auto& ls : s->lslot) ls = arp_clip::LabelSlot();
-    if (create_part_stream(&s->stream, (int)c->siblings.size() + 1) != hipSuccess) {
+    if (hipStreamCreateWithFlags(&s->stream, hipStreamNonBlocking) != hipSuccess) {
         delete s;
         return fail("hipStreamCreate failed");
     }
@@ -822,7 +807,7 @@ int arp_clip_create(const arp_clip_cfg* cfg, arp_clip** out) {
     if (const char* e = getenv("ARP_CLIP_GRAPH")) c->lat_graph = atoi(e) != 0;
     if (const char* e = getenv("ARP_SKINNY_ROWS")) c->lat_rows = std::min(std::max(atoi(e), 1), SKINNY_MAX_M);
     if (const char* e = getenv("ARP_CLIP_PINNED")) c->lat_pinned = atoi(e) != 0;
-    if (create_part_stream(&c->stream, 0) != hipSuccess) {
+    if (hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking) != hipSuccess) {
         delete c;
         return fail("hipStreamCreate failed");
     }
@@ -943,15 +928,9 @@ int arp_clip_set_text(arp_clip* c, const int32_t* tokens, int n_prompts) {
         ARP_HIP_OK(hipStreamSynchronize(c->stream));
         drop_lat_graphs(c);
     }
-    // 16-bit handles: the cached prompt features come from the f32 copy of the text tower (arp_clip::txt32); ARP_TEXT_F32=0 keeps
-    // the handle's own operand type (A/B measurements)
-    static const bool text32 = [] { const char* e = getenv("ARP_TEXT_F32"); return !e || atoi(e) != 0; }();
-    int rc;
-    if (c->cfg.mode != ARP_MODE_F32 && text32) rc = run_text<float>(c, tokens, n_prompts, nullptr, true, nullptr, false, true);
-    else if (c->cfg.mode == ARP_MODE_BF16) rc = run_text<bf16_t>(c, tokens, n_prompts);
-    else if (c->cfg.mode == ARP_MODE_F16) rc = run_text<f16_t>(c, tokens, n_prompts);
-    else rc = run_text<float>(c, tokens, n_prompts);
-    ARP_TRY(rc);
+    // 16-bit handles: the cached prompt features come from the f32 copy of the text tower (arp_clip::txt32)
+    if (c->cfg.mode != ARP_MODE_F32) ARP_TRY(run_text<float>(c, tokens, n_prompts, nullptr, true, nullptr, false, true));
+    else ARP_TRY(run_text<float>(c, tokens, n_prompts));
     ARP_TRY(c->txt_mean.ensure((size_t)c->cfg.embed * 4));
     hipLaunchKernelGGL(prompt_mean_kernel, dim3((c->cfg.embed + 255) / 256), dim3(256), 0, c->stream, c->txt_feat.as<float>(), c->txt_mean.as<float>(),
                        n_prompts, c->cfg.embed);
@@ -1553,8 +1532,6 @@ template <typename T> static int op_gemm_bench(int kernel, int act, int resid, i
         GemmArgs g;
         g.A = dA.p; g.W = dW.p; g.bias = dB.as<float>(); g.resid = resid ? dR.as<float>() : nullptr; g.out = resid ? dR.p : dO.p;
         g.M = M; g.N = N; g.K = K; g.lda = K; g.ldw = K; g.ldr = N; g.ldo = N;
-        if (const char* fe = getenv("ARP_GEMM_FLAGS")) g.flags = atoi(fe);
-        if (const char* fe = getenv("ARP_GEMM_STAGGER")) sscanf(fe, "%d,%d", &g.stagger_groups, &g.stagger_cycles);
         if (const char* fe = getenv("ARP_GEMM_GROUP_M")) g.group_m = atoi(fe);
         auto run = [&]() -> int {
             if (resid) return launch_gemm_auto<T, float, ACT_NONE, true, SITE_OP>(g, nullptr, kernel);

@@ -142,7 +142,6 @@ struct arp_dt {
     bool ac_a_dx = true;
     DevBuf Adx;            // d: [Mx, D / 2] bytes
     bool ac_a_exact = false;
-    bool ac_h1_inplace = true;  // the backward reads H1 out of the [hi | x4 | dx4] rows fc1 wrote (row stride 3 D / 2 halves) instead of a copy made by extract_hi_kernel
     const void* h1_ptr = nullptr;  // what the backward reads as H1 this step, and its row stride
     int h1_ld = 0;
     DevBuf Xc, H1c, A32, W1c, W2c, wc_scal;  // operand rows [hi | x4 | dx4]; packed weights [W_hi | dW4 | W4]; wc_scal: 16 ints (sd, sw of W1 / W2 at 4, 5 / 12, 13) + 2 x 32 per-block (max |dw|, max |w|) pairs
@@ -152,24 +151,13 @@ struct arp_dt {
     // the bytes, + everything the transformer produced) launched while the adapter's backward GEMMs still run (step_impl)
     hipStream_t comm_stream = nullptr;
     hipEvent_t ev_b1 = nullptr, ev_b2 = nullptr, ev_comm = nullptr;
-    // Experiment (round 4, OFF; ARP_DT_SIDE=1 switches it on): in the single-rank backward of the adapter (16-bit TN path) the weight-gradient GEMMs that
-    // nothing downstream waits for run on a SIDE stream beside the kernels that carry the dependent chain -- dWi beside the fused dY kernel (two streaming
-    // kernels at 3.4 - 3.9 TB/s each), dW2 (216 long workgroups) beside dApre . W2 (387 tiles = one and a half rounds of the chip); forked and joined by
-    // events, inside the captured graph as well.  MEASURED SLOWER (profiles/r4_side.txt, interleaved): step 0.862 -> 0.907 ms -- side by side dW2 takes
-    // 158 us instead of 56 (its K-slices-per-XCD walk wants the chip), dApre . W2 99 instead of 62, the fused dY kernel 94 instead of 72: these kernels
-    // are each sized for 256 CUs and lose more to each other than their tails were worth.
-    hipStream_t side_stream = nullptr;
-    hipEvent_t ev_fork = nullptr, ev_dapre = nullptr, ev_side = nullptr;
-    bool side_gemms = false;
     bool mix_x16 = true;      // iti_x3_kernel's mix reads the encodings' operand-type copy, not the f32 encodings (ARP_DT_MIX_X16=0; dtops.h: 16-seed logits 8.73e-4 -> 8.74e-4)
     bool dy_x16 = true;       // adapter_dy_kernel reads the encodings' operand-type copy for d loss / d res (ARP_DT_DY_X16=0: the f32 encodings, rounds 2-5)
     bool merge_small = true;  // the step's small dependent launches merged (ARP_DT_MERGE=0: one launch each, rounds 2-5)
     bool dzb_from_pf = false;
-    bool pack_early = false;
-    bool defer_w2t = false, w2t_pending = false, packed_in_prologue = false;  // forward<T>'s merged prologue launch (dt_prologue_kernel)
+    bool defer_w2t = false, w2t_pending = false;  // forward<T>'s merged prologue launch (dt_prologue_kernel)
     bool dwi_last = true;   // backward_adapter_tn: image_text_input's weight gradient last (Infinity Cache residency for the norm pass)
     bool adam_rev = true;   // apply_update: the update walks the flat state from its end (what the norm pass touched last)
-    DevBuf part_side;
     bool overlap_comm = true;   // ARP_DT_OVERLAP=0: the serial form (one all-reduce after the whole backward), for A/B and the bit-identity test
     bool force_comm = false;    // ARP_DT_FORCE_COMM=1: run the all-reduce path at world = 1 too (what a 1-GPU box can test)
     bool grads_summed = false;  // the gradient buffer holds the SUM over ranks (set by a data-parallel step)
@@ -190,13 +178,11 @@ struct arp_dt {
     // 16-bit modes with 128-aligned widths: weight gradients on the TN kernel (gemm_tn.h) straight from the row-major operands --
     // no transposed, K-padded copies.  Other geometries (and the f32 parity mode) keep the transposed-copy path.
     bool use_tn() const {
-        static const bool off = getenv("ARP_DT_TN") && atoi(getenv("ARP_DT_TN")) == 0;
-        return !off && cfg.mode != ARP_MODE_F32 && cfg.enc_dim % 128 == 0 && cfg.emb % 128 == 0;
+        return cfg.mode != ARP_MODE_F32 && cfg.enc_dim % 128 == 0 && cfg.emb % 128 == 0;
     }
     // ... and, with the adapter on, the gradient through image_text_input fused with the adapter's first mask (adapter_bwd.h)
     bool use_fused_dy() const {
-        static const bool off = getenv("ARP_DT_FUSED_DY") && atoi(getenv("ARP_DT_FUSED_DY")) == 0;
-        return !off && use_tn() && cfg.use_adapter && adapter_dy_supported(cfg.emb, cfg.enc_dim, (long long)cfg.enc_tokens * cfg.enc_dim);
+        return use_tn() && cfg.use_adapter && adapter_dy_supported(cfg.emb, cfg.enc_dim, (long long)cfg.enc_tokens * cfg.enc_dim);
     }
     // ARP_DT_FUSE_RELU_BWD: 0 = never, 1 (default) = where gemm256 is the kernel that would run anyway (>= 192 tiles), 2 = whenever
     // the shape allows (the parity tests' way to reach the masked epilogue at B = 2); read when the handle is created
@@ -365,7 +351,7 @@ int splitk_gemm(arp_dt* c, const char* site, const void* A, int lda, const void*
     constexpr int EPB = 128 / (int)sizeof(T);
     const int nk = K / EPB;
     const int tiles = cdiv(M, 128) * cdiv(N, 128);
-    static const int wg_target = getenv("ARP_SPLITK_WGS") ? atoi(getenv("ARP_SPLITK_WGS")) : 512;  // one resident round (2 WG/CU x 256 CUs); measured best of 256..2048
+    constexpr int wg_target = 512;  // one resident round (2 WG/CU x 256 CUs); measured best of 256..2048
     int S = std::max(1, std::min(nk, wg_target / std::max(tiles, 1)));
     const int per = (nk + S - 1) / S;
     S = (nk + per - 1) / per;  // every slice non-empty
@@ -392,19 +378,15 @@ int transpose_mask(arp_dt* c, const TI* in, int ldi, const TM* mask, const float
     return 0;
 }
 
-// The step's three independent preparations in one launch (16-bit modes, fused transformer): the encodings' f32 -> operand-type conversion (a 151 MB stream),
-// the fused kernel's fragment-major weight copies (pf_pack_kernel's jobs) and the transposed shadow of the adapter's second kernel.  They were three
-// dependent launches; none reads another's output, and the two small ones disappear under the stream.
+// The step's two independent preparations in one launch (16-bit modes, fused transformer): the encodings' f32 -> operand-type conversion (a 151 MB stream)
+// and the transposed shadow of the adapter's second kernel.  Neither reads the other's output, and the small one disappears under the stream.  (The fused
+// kernel's weight packing stays in pf_pack_kernel, right in front of it: DESIGN.md section 6a.)
 struct DtPrologueArgs {
     const float* enc; void* xb; size_t n8; int conv_blocks;
-    const PfPackJob* jobs; int pack_blocks, njobs;
     const void* W2; void* W2t; int D;  // W2t == nullptr: no transpose in this launch
 };
 template <typename T> static __global__ __launch_bounds__(256) void dt_prologue_kernel(DtPrologueArgs a) {
-    int b = (int)blockIdx.x;
-    const int npack = a.pack_blocks * a.njobs;
-    if (b < npack) { pf_pack_block(a.jobs, b % a.pack_blocks, a.pack_blocks, b / a.pack_blocks); return; }
-    b -= npack;
+    const int b = (int)blockIdx.x;
     const int tb = (a.D + 63) / 64, ntr = a.W2t ? tb * tb : 0;
     if (b < ntr) {
         transpose_mask_tile<T, T, T>(static_cast<const T*>(a.W2), a.D, nullptr, nullptr, 1.f, nullptr, 0, static_cast<T*>(a.W2t), a.D, a.D, a.D, b % tb, b / tb);
@@ -658,9 +640,7 @@ int policy_fused(arp_dt* c, bool do_bwd) {
     c->pf.dzb_f16 = k.mode == ARP_MODE_F16 ? 1 : 0;
     c->dzb_from_pf = dzb_here;
     const size_t lds = pf_lds_bytes(k.emb, k.mlp_ratio * k.emb, k.heads, k.depth);
-    if (!c->packed_in_prologue)  // (forward<T>'s merged prologue launch packed them already)
-        hipLaunchKernelGGL(pf_pack_kernel, dim3(c->pf_pack_blocks, c->pf_njobs), dim3(256), 0, c->stream, static_cast<const PfPackJob*>(c->pf_jobs.p));
-    c->packed_in_prologue = false;
+    hipLaunchKernelGGL(pf_pack_kernel, dim3(c->pf_pack_blocks, c->pf_njobs), dim3(256), 0, c->stream, static_cast<const PfPackJob*>(c->pf_jobs.p));
     if (k.emb == 128 && c->pf_x3) hipLaunchKernelGGL((policy_fused_kernel<128, 512, true>), dim3(c->B), dim3(PF_THREADS), lds, c->stream, c->pf);
     else if (k.emb == 128) hipLaunchKernelGGL((policy_fused_kernel<128, 512>), dim3(c->B), dim3(PF_THREADS), lds, c->stream, c->pf);
     else if (c->pf_x3) hipLaunchKernelGGL((policy_fused_kernel<64, 256, true>), dim3(c->B), dim3(PF_THREADS), lds, c->stream, c->pf);
@@ -716,7 +696,7 @@ template <typename T> int forward(arp_dt* c, bool with_bwd = false) {
     const int Kin = k.enc_tokens * D;
     const int Mxp = (int)((Mx + 63) / 64 * 64);
     const bool adapter_cpath = __is_same(T, f16_t) && k.use_adapter && c->adapter_c && D % 256 == 0 && D >= 512;
-    // 16-bit modes with the fused transformer: conversion + weight packing + W2's transposed shadow in ONE launch (dt_prologue_kernel)
+    // 16-bit modes with the fused transformer: conversion + W2's transposed shadow in ONE launch (dt_prologue_kernel)
     const bool prologue = sizeof(T) == 2 && c->merge_small && c->fused && !(adapter_cpath && c->use_tn()) && !(k.use_adapter && !c->use_tn()) && (Mx * D) % 8 == 0;
     c->defer_w2t = prologue;
     ARP_TRY(refresh_shadows<T>(c));
@@ -735,14 +715,10 @@ template <typename T> int forward(arp_dt* c, bool with_bwd = false) {
             if (prologue) {
                 DtPrologueArgs a;
                 a.enc = c->bt[c->cur].enc32.as<float>(); a.xb = c->Xb.p; a.n8 = n / 8; a.conv_blocks = (int)std::min<size_t>(cdiv(n / 8, 256), 4096);
-                // (the weight packing rides along only on request, ARP_DT_PACK_EARLY=1: packed 200 us ahead of the fused kernel the copies have left L2 by the time
-                //  it streams them -- policy_fused_kernel 113 -> 122 us, more than the launch saved; profiles/r5_policy_ab.txt run 13)
-                a.jobs = static_cast<const PfPackJob*>(c->pf_jobs.p); a.pack_blocks = c->pf_pack_blocks; a.njobs = c->pack_early ? c->pf_njobs : 0;
                 a.W2 = c->fwd_w("AdapterMLP_0/Dense_1/kernel"); a.W2t = c->w2t_pending ? c->W2t.p : nullptr; a.D = D;
                 const int tb = cdiv(D, 64);
-                hipLaunchKernelGGL((dt_prologue_kernel<T>), dim3(a.pack_blocks * a.njobs + (a.W2t ? tb * tb : 0) + a.conv_blocks), dim3(256), 0, c->stream, a);
+                hipLaunchKernelGGL((dt_prologue_kernel<T>), dim3((a.W2t ? tb * tb : 0) + a.conv_blocks), dim3(256), 0, c->stream, a);
                 c->w2t_pending = false;
-                c->packed_in_prologue = c->pack_early;
             } else if (n % 8 == 0) hipLaunchKernelGGL((convert8_kernel<T>), dim3((unsigned)std::min<size_t>(cdiv(n / 8, 256), 4096)), dim3(256), 0, c->stream, c->bt[c->cur].enc32.as<float>(), c->Xb.as<T>(), n / 8);
             else hipLaunchKernelGGL((convert_kernel<T>), dim3(cdiv(n, 1024)), dim3(256), 0, c->stream, c->bt[c->cur].enc32.as<float>(), c->Xb.as<T>(), n);
             ARP_HIP_OK(hipGetLastError());
@@ -799,9 +775,9 @@ template <typename T> int forward(arp_dt* c, bool with_bwd = false) {
                 ProfScope ps(c->prof, c->stream, "dt.adapter_fc1");
                 ARP_TRY((launch_gemm256_nt<f16_t, f16_t, ACT_RELU, false, SITE_DT, false, 1, true>(g, c->stream)));
             }
-            // (in place only where the backward's ReLU mask rides in dApre . W2's epilogue -- a row stride there -- and not in mask_copy_colsum_kernel, which walks a
-            //  contiguous H1: small geometries, ARP_DT_FUSE_RELU_BWD=0)
-            if (c->ac_h1_inplace && c->use_tn() && D % 8 == 0 && c->fuse_relu_bwd((long)cdiv((int)Mx, 256) * cdiv(D, 256))) {
+            // the backward reads H1 out of the [hi | x4 | dx4] rows fc1 wrote (row stride 3 D / 2 halves) where its ReLU mask rides in dApre . W2's epilogue;
+            // mask_copy_colsum_kernel walks a contiguous H1, so small geometries and ARP_DT_FUSE_RELU_BWD=0 get a copy (extract_hi_kernel)
+            if (c->use_tn() && D % 8 == 0 && c->fuse_relu_bwd((long)cdiv((int)Mx, 256) * cdiv(D, 256))) {
                 c->h1_ptr = c->H1c.p; c->h1_ld = D + D / 2;
             } else {
                 ProfScope ps(c->prof, c->stream, "dt.adapter_fc1");
@@ -866,16 +842,12 @@ template <typename T> int forward(arp_dt* c, bool with_bwd = false) {
         const float* Y32 = k.use_adapter ? c->Y32.as<float>() : c->bt[c->cur].enc32.as<float>();
         const int tiles = cdiv(R, 128) * cdiv(E, 128);
         const int nk = (int)(Kin / 64);
-        static const int iti_wgs = getenv("ARP_DT_ITI_WGS") ? atoi(getenv("ARP_DT_ITI_WGS")) : 256;
-        int S = std::max(1, std::min(nk, iti_wgs / std::max(tiles, 1)));  // workgroups on the chip (74 KB of LDS and 174 registers each: two fit a CU)
+        int S = std::max(1, std::min(nk, 256 / std::max(tiles, 1)));  // workgroups on the chip (74 KB of LDS and 174 registers each: two fit a CU)
         const int per = (nk + S - 1) / S;
         S = (nk + per - 1) / per;
         ARP_TRY(c->part.ensure((size_t)S * R * E * 4));
         ProfScope ps(c->prof, c->stream, "dt.image_text_input");
-        static const int ahead = [] { const char* e = getenv("ARP_DT_ITI_AHEAD"); return e && atoi(e) == 2 ? 2 : 1; }();
-        // (ARP_DT_ITI_CYCLIC=1: K-tiles dealt round-robin instead of one K range per workgroup -- measured 2 us slower, profiles/r5_policy_ab.txt: the stream is not short of DRAM locality)
-        static const bool cyclic = [] { const char* e = getenv("ARP_DT_ITI_CYCLIC"); return e && atoi(e) != 0; }();
-        const int kslice = cyclic ? 0 : per * 64;
+        const int kslice = per * 64;  // one K range per workgroup
         const float* Wi = c->p("image_text_input/kernel");
         if constexpr (sizeof(T) == 2) {
             if (mix_a32) {
@@ -893,8 +865,6 @@ template <typename T> int forward(arp_dt* c, bool with_bwd = false) {
             } else if (mix_a) {
                 hipLaunchKernelGGL((iti_x3_kernel<1, T, T>), dim3(S, tiles), dim3(256), 0, c->stream, c->bt[c->cur].enc32.as<float>(), Kin, Wi, Kin, c->part.as<float>(), R, E, (int)Kin,
                                    kslice, mix_a, c->p("residual_weight"), c->Y.as<T>(), (const T*)nullptr);
-            } else if (ahead == 2) {
-                hipLaunchKernelGGL(iti_x3_kernel<2>, dim3(S, tiles), dim3(256), 0, c->stream, Y32, Kin, Wi, Kin, c->part.as<float>(), R, E, (int)Kin, kslice, (const iti_nomix_t*)nullptr, (const float*)nullptr, (f16_t*)nullptr, (const f16_t*)nullptr);
             } else {
                 hipLaunchKernelGGL(iti_x3_kernel<1>, dim3(S, tiles), dim3(256), 0, c->stream, Y32, Kin, Wi, Kin, c->part.as<float>(), R, E, (int)Kin, kslice, (const iti_nomix_t*)nullptr, (const float*)nullptr, (f16_t*)nullptr, (const f16_t*)nullptr);
             }
@@ -953,17 +923,14 @@ template <typename T> int forward(arp_dt* c, bool with_bwd = false) {
 // Same math as the tail of backward<T>() below; the operands of the three weight-gradient contractions stay row-major
 // (no transposed K-padded copies): dWi = dz^T Y, dW2 = dApre^T H1, dW1 = dH1^T X.
 template <typename T>
-int tn_gemm(arp_dt* c, const char* site, const T* A, int lda, const T* B, int ldb, float* out, int M, int N, int K, float alpha, bool side = false) {
-    hipStream_t st = side ? c->side_stream : c->stream;
-    DevBuf& part = side ? c->part_side : c->part;  // (a side-stream GEMM keeps its split-K slabs to itself)
+int tn_gemm(arp_dt* c, const char* site, const T* A, int lda, const T* B, int ldb, float* out, int M, int N, int K, float alpha) {
     const int tcode = __is_same(T, bf16_t) ? 1 : 2;
     GemmTnArgs g;
     int S;
     // a long contraction into a few 256 x 256 tiles (the adapter's 768 x 768 x 32 896): the 256-tile kernel, whole K-slices per XCD
     const int t256 = (M % 256 == 0 && N % 256 == 0) ? (M / 256) * (N / 256) : 0;
     const int spx = t256 > 0 && t256 <= 32 ? 32 / t256 : 0;
-    static const bool allow256 = [] { const char* e = getenv("ARP_DT_TN256"); return !e || atoi(e) != 0; }();
-    if (allow256 && spx > 0 && K / 32 >= 8 * spx * 8) {
+    if (spx > 0 && K / 32 >= 8 * spx * 8) {
         S = 8 * spx;
         g.tile256 = 1;
         g.xcd_slices = 1;
@@ -974,16 +941,16 @@ int tn_gemm(arp_dt* c, const char* site, const T* A, int lda, const T* B, int ld
         S = (nk + per - 1) / per;
     }
     g.A = A; g.B = B; g.M = M; g.N = N; g.K = K; g.lda = lda; g.ldb = ldb; g.ksplit = S;
-    ProfScope ps(c->prof, st, site);
+    ProfScope ps(c->prof, c->stream, site);
     if (S == 1) {
         g.out = out; g.ldo = N; g.slice_stride = 0; g.alpha = alpha;
-        return launch_gemm_tn(tcode, g, st);
+        return launch_gemm_tn(tcode, g, c->stream);
     }
-    ARP_TRY(part.ensure((size_t)S * M * N * 4));
-    g.out = part.as<float>(); g.ldo = N; g.slice_stride = (size_t)M * N; g.alpha = 1.f;
-    ARP_TRY(launch_gemm_tn(tcode, g, st));
+    ARP_TRY(c->part.ensure((size_t)S * M * N * 4));
+    g.out = c->part.as<float>(); g.ldo = N; g.slice_stride = (size_t)M * N; g.alpha = 1.f;
+    ARP_TRY(launch_gemm_tn(tcode, g, c->stream));
     const size_t MN = (size_t)M * N;
-    launch_splitk_reduce<float>(st, part.as<float>(), S, MN, N, nullptr, ACT_NONE, out, nullptr, 0, alpha);
+    launch_splitk_reduce<float>(c->stream, c->part.as<float>(), S, MN, N, nullptr, ACT_NONE, out, nullptr, 0, alpha);
     ARP_HIP_OK(hipGetLastError());
     return 0;
 }
@@ -999,26 +966,20 @@ template <typename T> int backward_adapter_tn(arp_dt* c, int stage) {
     const int Mxp = (int)((Mx + 63) / 64 * 64), Rp64 = (R + 63) / 64 * 64;
     const float S = c->act_scale(), invS = 1.0f / S;
     const T* Yp = k.use_adapter ? c->Y.as<T>() : c->Xb.as<T>();
-    // the whole backward in one call on one rank, with the adapter and the fused dY kernel: the two weight-gradient GEMMs nothing waits for go to the side stream
-    const bool side = c->side_gemms && stage == 0 && k.use_adapter && c->use_fused_dy() && c->side_stream;
     // The whole backward in one call: dWi (101 MB of f32 gradient at the real geometry, 95 % of the flat gradient) is produced LAST, so that
     // the norm pass right behind it finds those bytes in the 256 MiB Infinity Cache instead of HBM (same launches, same arithmetic; a staged
     // backward needs dWi first for its all-reduce bucket).  ARP_DT_DWI_LAST=0 restores the old order.
-    const bool dwi_last = c->dwi_last && stage == 0 && k.use_adapter && !side;
-    // the three small reductions of this backward in one launch behind its last GEMM (both of its fused forms on, nothing on the side stream)
+    const bool dwi_last = c->dwi_last && stage == 0 && k.use_adapter;
+    // the three small reductions of this backward in one launch behind its last GEMM (both of its fused forms on)
     const long tiles256_dx = (long)cdiv((int)Mx, 256) * cdiv(D, 256);
-    const bool defer_small = c->merge_small && k.use_adapter && stage != 1 && !side && c->use_fused_dy() && D % 8 == 0 && c->fuse_relu_bwd(tiles256_dx);
+    const bool defer_small = c->merge_small && k.use_adapter && stage != 1 && c->use_fused_dy() && D % 8 == 0 && c->fuse_relu_bwd(tiles256_dx);
     int fin_rows1 = 0, fin_rows0 = 0, fin_ndres = 0;
     if (stage != 2) {
         // dz (f32) -> operand type, scaled (rows R..Rp64 of dzb stay zero); the fused kernel may have written it already (policy_fused)
         if (!(c->fused && c->dzb_from_pf)) ARP_TRY((transpose_mask<float, float, T>(c, c->dz.as<float>(), E, nullptr, nullptr, S, c->dzb.as<T>(), E, nullptr, 0, R, E)));
         // dWi[E, Kin] = dz^T Y: contraction over the R rows, written straight into the gradient buffer
-        if (side) {
-            ARP_HIP_OK(hipEventRecord(c->ev_fork, c->stream));
-            ARP_HIP_OK(hipStreamWaitEvent(c->side_stream, c->ev_fork, 0));
-        }
         if (!dwi_last)
-            ARP_TRY((tn_gemm<T>(c, "dt.image_text_input_dW", c->dzb.as<T>(), E, Yp, Kin, c->g("image_text_input/kernel"), E, Kin, Rp64, invS, side)));
+            ARP_TRY((tn_gemm<T>(c, "dt.image_text_input_dW", c->dzb.as<T>(), E, Yp, Kin, c->g("image_text_input/kernel"), E, Kin, Rp64, invS)));
     }
     if (!k.use_adapter || stage == 1) return 0;
     const int prow = Mxp / 64, ncb = cdiv(D, 256);
@@ -1058,12 +1019,8 @@ template <typename T> int backward_adapter_tn(arp_dt* c, int stage) {
         hipLaunchKernelGGL(dres_to_drw_kernel, dim3(1), dim3(1), 0, c->stream, c->scal.as<float>() + 8, c->p("residual_weight"), c->g("residual_weight"));
         ARP_HIP_OK(hipGetLastError());
     }
-    if (side) {  // dApre is complete on the main stream from here
-        ARP_HIP_OK(hipEventRecord(c->ev_dapre, c->stream));
-        ARP_HIP_OK(hipStreamWaitEvent(c->side_stream, c->ev_dapre, 0));
-    }
     // (H1 = the hidden rows' binary16 segment: c->H1 itself, or the head of fc1's [hi | x4 | dx4] rows with the adapter corrections on)
-    ARP_TRY((tn_gemm<T>(c, "dt.adapter_fc2_dW", c->dApre.as<T>(), D, static_cast<const T*>(c->h1_ptr), c->h1_ld, c->g("AdapterMLP_0/Dense_1/kernel"), D, D, Mxp, invS, side)));
+    ARP_TRY((tn_gemm<T>(c, "dt.adapter_fc2_dW", c->dApre.as<T>(), D, static_cast<const T*>(c->h1_ptr), c->h1_ld, c->g("AdapterMLP_0/Dense_1/kernel"), D, D, Mxp, invS)));
     const long tiles256 = (long)cdiv((int)Mx, 256) * cdiv(D, 256);
     if (D % 8 == 0 && c->fuse_relu_bwd(tiles256)) {
         // dH1 = (dApre W2) * (H1 > 0) and its column sums (the Dense_0 bias gradient) in the GEMM's own epilogue (gemm256.h)
@@ -1085,7 +1042,7 @@ template <typename T> int backward_adapter_tn(arp_dt* c, int stage) {
         ARP_TRY((big_gemm<T, T, ACT_NONE>(c, "dt.adapter_fc2_dX", c->dApre.p, D, c->W2t.p, D, nullptr, c->G.p, D, (int)Mx, D, D)));
         // dH1 = G * (H1 > 0), row-major (in the buffer the other path uses for its transposed copy), + the Dense_0 bias gradient
         ProfScope ps(c->prof, c->stream, "dt.adapter_bwd_masks");
-        if (c->h1_ld != D) return fail("backward_adapter_tn: the unfused ReLU backward reads a contiguous H1 (ARP_DT_ADAPTER_H1_INPLACE=0)");
+        if (c->h1_ld != D) return fail("backward_adapter_tn: the unfused ReLU backward reads a contiguous H1 (extract_hi_kernel's copy)");
         hipLaunchKernelGGL((mask_copy_colsum_kernel<T>), dim3(cdiv(D, 256), prow), dim3(256), 0, c->stream, c->G.as<T>(), c->H1.as<T>(), nullptr, 1.f,
                            c->dH1T.as<T>(), c->colpart.as<float>(), (int)Mx, D);
         hipLaunchKernelGGL(colsum_kernel, dim3(cdiv(D, 64)), dim3(256), 0, c->stream, c->colpart.as<float>(), prow, D, c->g("AdapterMLP_0/Dense_0/bias"), invS);
@@ -1101,10 +1058,6 @@ template <typename T> int backward_adapter_tn(arp_dt* c, int stage) {
         ARP_HIP_OK(hipGetLastError());
     }
     if (dwi_last) ARP_TRY((tn_gemm<T>(c, "dt.image_text_input_dW", c->dzb.as<T>(), E, Yp, Kin, c->g("image_text_input/kernel"), E, Kin, Rp64, invS)));
-    if (side) {  // join: everything after the backward (norms, Adam, a later forward) is ordered behind the side stream's two GEMMs
-        ARP_HIP_OK(hipEventRecord(c->ev_side, c->side_stream));
-        ARP_HIP_OK(hipStreamWaitEvent(c->stream, c->ev_side, 0));
-    }
     return 0;
 }
 
@@ -1501,12 +1454,9 @@ int arp_dt_create(const arp_dt_cfg* cfg, arp_dt** out) {
         if (e[0] && e[1] >= '1' && e[1] <= '2') c->ac_plan2 = e[1] - '0';
         if (e[0] && e[1] && (e[2] == 'e' || e[2] == 'h' || e[2] == 'd')) { c->ac_a_exact = e[2] == 'e'; c->ac_a_dx = e[2] == 'd'; }
     }
-    if (const char* e = getenv("ARP_DT_ADAPTER_H1_INPLACE")) c->ac_h1_inplace = atoi(e) != 0;
     if (const char* e = getenv("ARP_DT_OVERLAP")) c->overlap_comm = atoi(e) != 0;
-    if (const char* e = getenv("ARP_DT_SIDE")) c->side_gemms = atoi(e) != 0;
     if (const char* e = getenv("ARP_DT_DWI_LAST")) c->dwi_last = atoi(e) != 0;
     if (const char* e = getenv("ARP_DT_MERGE")) c->merge_small = atoi(e) != 0;
-    if (const char* e = getenv("ARP_DT_PACK_EARLY")) c->pack_early = atoi(e) != 0;
     if (const char* e = getenv("ARP_DT_DY_X16")) c->dy_x16 = atoi(e) != 0;
     if (const char* e = getenv("ARP_DT_MIX_X16")) c->mix_x16 = atoi(e) != 0;
     if (const char* e = getenv("ARP_DT_ADAM_REV")) c->adam_rev = atoi(e) != 0;
@@ -1517,10 +1467,8 @@ int arp_dt_create(const arp_dt_cfg* cfg, arp_dt** out) {
         // The HIP runtime multiplexes a process's streams onto GPU_MAX_HW_QUEUES hardware queues (8 here, arp_amd/_ffi.py): two streams that land on ONE queue run
         // one after the other.  Round 6 measured what that costs: with the encoder's stream added this handle + its encoder held nine streams, the encoder's two
         // part streams shared a queue, and the step went 10.6 -> 12.4 ms (profiles/r6_n1_ab_queues.txt).  Only the compute stream exists from the start; the
-        // communication, side and copy streams are created by the first call that needs them (stream_or_create).
+        // communication and copy streams are created by the first call that needs them (stream_or_create).
         ARP_HIP_OK(hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking));
-        if (c->side_gemms) ARP_HIP_OK(hipStreamCreateWithFlags(&c->side_stream, hipStreamNonBlocking));
-        for (hipEvent_t* e : {&c->ev_fork, &c->ev_dapre, &c->ev_side}) ARP_HIP_OK(hipEventCreateWithFlags(e, hipEventDisableTiming));
         for (hipEvent_t* e : {&c->ev_b1, &c->ev_b2, &c->ev_comm, &c->bt[0].up, &c->bt[0].use, &c->bt[1].up, &c->bt[1].use, &c->bt[2].up, &c->bt[2].use})
             ARP_HIP_OK(hipEventCreateWithFlags(e, hipEventDisableTiming));
         DevBuf* fb[] = {&c->params, &c->grads, &c->mu, &c->nu};
@@ -1549,16 +1497,15 @@ int arp_dt_create(const arp_dt_cfg* cfg, arp_dt** out) {
 int arp_dt_destroy(arp_dt* c) {
     if (!c) return 0;
     (void)hipSetDevice(c->cfg.device);
-    for (hipStream_t st : {c->stream, c->comm_stream, c->side_stream, c->copy_stream[0], c->copy_stream[1], c->enc_stream})  // (an encode-ahead pass may still be in flight)
+    for (hipStream_t st : {c->stream, c->comm_stream, c->copy_stream[0], c->copy_stream[1], c->enc_stream})  // (an encode-ahead pass may still be in flight)
         if (st) (void)hipStreamSynchronize(st);
     for (auto& slot : c->graphs)
         for (auto& gr : slot)
             if (gr.exec) (void)hipGraphExecDestroy(gr.exec);
     if (c->has_comm && rccl_api()) (void)rccl_api()->CommDestroy(c->comm);
-    for (hipEvent_t e : {c->ev_fork, c->ev_dapre, c->ev_side, c->ev_enc_go, c->bt[0].enc_done, c->bt[1].enc_done, c->bt[2].enc_done})
+    for (hipEvent_t e : {c->ev_enc_go, c->bt[0].enc_done, c->bt[1].enc_done, c->bt[2].enc_done})
         if (e) (void)hipEventDestroy(e);
     if (c->enc_stream) (void)hipStreamDestroy(c->enc_stream);
-    c->part_side.release();
     for (hipEvent_t e : {c->ev_b1, c->ev_b2, c->ev_comm, c->bt[0].up, c->bt[0].use, c->bt[1].up, c->bt[1].use, c->bt[2].up, c->bt[2].use})
         if (e) (void)hipEventDestroy(e);
     c->prof.destroy();
@@ -1571,7 +1518,7 @@ int arp_dt_destroy(arp_dt* c) {
     for (auto* v : {&c->xs, &c->ln0, &c->qkv, &c->att, &c->hmid, &c->ln1, &c->u, &c->gl, &c->d_x1, &c->d_u, &c->d_mid, &c->d_qkv, &c->dws0, &c->dbs0,
                     &c->dws1, &c->dbs1})
         for (auto& b : *v) b.release();
-    for (hipStream_t st : {c->stream, c->comm_stream, c->side_stream, c->copy_stream[0], c->copy_stream[1]})
+    for (hipStream_t st : {c->stream, c->comm_stream, c->copy_stream[0], c->copy_stream[1]})
         if (st) (void)hipStreamDestroy(st);
     delete c;
     return 0;

@@ -147,7 +147,7 @@ struct arp_enc {
     DevBuf img_in, out;
     // ARP_MODE_F16C: per GEMM g in {in_proj, out_proj, fc1, fc2} the correction plan (0 plain, 1 weights, 2 weights + activations) and, per layer, the
     // power-of-two exponents the e2m1 (fp4) weight segments were scaled by: dW4 = fp4(dW * 2^sw_d), W4 = fp4(W * 2^sw_w)
-    bool vperm = true;  // ARP_MODE_F16C: V's columns permuted inside every head so that the attention's [hi | x4 | dx4] rows leave in whole pieces (attention.h, outc == 2); ARP_F16C_VPERM=0: round 5's stores
+    bool vperm = true;  // ARP_MODE_F16C: V's columns permuted inside every head so that the attention's [hi | x4 | dx4] rows leave in whole pieces (attention.h, outc == 2); cleared by geometry
     // Default 1110 (round 6): the weight roundings of in_proj, out_proj and fc1 corrected, fc2 plain.  Encoder-inside logits over 8 seeds (max) and the 32-sample step
     // on one box, AFTER the epilogue's x4 segment was repaired (gemm256.h; rounds 5 and 6 measured fc2's correction as noise): 1221 3.7e-4 / 10.19 ms,
     // 1121 5.4e-4, 1111 6.0e-4 / 9.82, 1220 6.4e-4 / 9.83, 1211 6.9e-4 / 9.88, 1210 6.8e-4 / 9.54, 1120 6.7e-4 / 9.76, 1110 7.0e-4 / 9.48 (profiles/r6_n1_plan_sweep.txt,
@@ -352,9 +352,8 @@ int forward_chunk_x3(arp_enc* c, arp_enc::Ws& w, hipStream_t stream, const float
         ARP_TRY((tower_gemm<f16_t, float, ACT_NONE, false, 8 + SITE_QKV>(t, "m3ae.qkv", a3, L.w_in, L.b_in, nullptr, qkv, M, 3 * D, 3 * D)));
         {
             ProfScope ps(c->prof, stream, "m3ae.attn");
-            // the (hi, lo) binary16 attention (attention.h::attn_x3_kernel) where it exists; ARP_ENC_ATTN_X3=0 keeps the exact-f32 MFMA kernel
-            static const bool attn_x3 = [] { const char* e = getenv("ARP_ENC_ATTN_X3"); return !e || atoi(e) != 0; }();
-            ARP_TRY(launch_attention<float>(stream, direct && attn_x3 ? 3 : k.attn_impl, qkv, ao, nb, N, D, k.heads, 0, 0, 0.f, direct ? a3 : nullptr));
+            // the (hi, lo) binary16 attention (attention.h::attn_x3_kernel) where it exists
+            ARP_TRY(launch_attention<float>(stream, direct ? 3 : k.attn_impl, qkv, ao, nb, N, D, k.heads, 0, 0, 0.f, direct ? a3 : nullptr));
         }
         if (!direct) ARP_TRY(split("m3ae.split", ao, M, D));
         ARP_TRY((tower_gemm<f16_t, float, ACT_NONE, true, 8 + SITE_OUT>(t, "m3ae.out_proj", a3, L.w_out, L.b_out, x, x, M, D, 3 * D)));
@@ -389,7 +388,8 @@ int gemm_c(arp_enc* c, TowerCtx& t, const char* site, const void* A, const void*
     g.mix_sb = F16C_DX_SHIFT + sw;
     if (x4_out) { g.xb_out = x4_out; g.ldxb = ld4; g.x8_shift = F16C_X_SHIFT; g.dx4_out = dx4_out; }
     ProfScope ps(*t.prof, t.stream, site);
-    if (plan == 0) return launch_gemm256_nt<f16_t, OutT, ACT, RESID, SITE>(g, t.stream);  // (no fp4 side output on this instance: plan 0 is for probing only)
+    // plan 0 (fc2's in the default plan 1110): the plain binary16 instance, which has no fp4 side output (arp_enc_create refuses a plain fc1 in front of a corrected fc2)
+    if (plan == 0) return launch_gemm256_nt<f16_t, OutT, ACT, RESID, SITE>(g, t.stream);
     return launch_gemm256_nt<f16_t, OutT, ACT, RESID, SITE, false, 1, true>(g, t.stream);
 }
 
@@ -558,7 +558,6 @@ int arp_enc_create(const arp_enc_cfg* cfg, arp_enc** out) {
         for (int i = 0; i < 4 && e[i]; ++i)
             if (e[i] >= '0' && e[i] <= '2') c->plan[i] = e[i] - '0';
     }
-    if (const char* e = getenv("ARP_F16C_VPERM")) c->vperm = atoi(e) != 0;
     if (const char* e = getenv("ARP_ENC_STREAMS")) c->n_parts = std::max(1, std::min(atoi(e), (int)arp_enc::MAX_PARTS));
     if (const char* e = getenv("ARP_ENC_SPLIT")) c->first_part = std::max(-1, atoi(e));
     if (const char* e = getenv("ARP_ENC_MIN_PART")) c->min_part_frames = std::max(1, atoi(e));

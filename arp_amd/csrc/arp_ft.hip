@@ -188,7 +188,7 @@ int ft_gemm(arp_ft* c, const char* site, const void* A, int lda, const void* W, 
     constexpr int EPB = 128 / (int)sizeof(T);
     const int nk = K / EPB;
     const int tiles = cdiv(M, 128) * cdiv(N, 128);
-    static const int wg_target = getenv("ARP_SPLITK_WGS") ? atoi(getenv("ARP_SPLITK_WGS")) : 512;  // one resident round (2 WG/CU x 256 CUs); measured best of 256..2048
+    constexpr int wg_target = 512;  // one resident round (2 WG/CU x 256 CUs); measured best of 256..2048
     int S = std::max(1, std::min(nk, wg_target / std::max(tiles, 1)));
     const int per = (nk + S - 1) / S;
     S = (nk + per - 1) / per;
@@ -222,8 +222,7 @@ int ft_gemm(arp_ft* c, const char* site, const void* A, int lda, const void* W, 
     ARP_TRY(c->part.ensure((size_t)S * M * N * 4));
     g.bias = nullptr; g.resid = nullptr; g.out = c->part.p; g.ldr = N; g.ldo = N;
     g.ksplit = S; g.slice_stride = (size_t)M * N;
-    static const int mfast = getenv("ARP_FT_MFAST") ? atoi(getenv("ARP_FT_MFAST")) : 1;
-    g.m_fast = (mfast && M <= 4 * GEMM_BM) ? 1 : 0;  // the image tower's 192 rows = two row tiles over the same weight stream
+    g.m_fast = M <= 4 * GEMM_BM ? 1 : 0;  // the image tower's 192 rows = two row tiles over the same weight stream
     ARP_TRY((launch_gemm_nt<T, float, ACT_NONE, false, SITE_FT + 1>(g, c->stream)));
     const size_t MN = (size_t)M * N;
     launch_splitk_reduce<OutT>(c->stream, c->part.as<float>(), S, MN, N, bias, act, out, resid, ldo == N ? 0 : ldo);
@@ -238,7 +237,7 @@ int ft_gemm_nn(arp_ft* c, const char* site, const void* A, int lda, const void* 
     static_assert(sizeof(T) == 2, "16-bit modes only");
     const int nk = K / 64;
     const int tiles = cdiv(M, 128) * cdiv(N, 128);
-    static const int wg_target = getenv("ARP_SPLITK_WGS") ? atoi(getenv("ARP_SPLITK_WGS")) : 512;
+    constexpr int wg_target = 512;
     int S = std::max(1, std::min(nk, wg_target / std::max(tiles, 1)));
     const int per = (nk + S - 1) / S;
     S = (nk + per - 1) / per;

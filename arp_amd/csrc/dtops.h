@@ -169,9 +169,8 @@ static __global__ __launch_bounds__(256) void splitk_reduce4_kernel(const float*
 template <typename OutT>
 static inline void launch_splitk_reduce(hipStream_t st, const float* part, int S, size_t MN, int N, const float* bias, int act, OutT* out,
                                         const float* resid = nullptr, int ldo = 0, float alpha = 1.f) {
-    static const bool wide = [] { const char* e = getenv("ARP_SPLITK_REDUCE4"); return !e || atoi(e) != 0; }();
     // (many-slab reductions only: at S = 8..32, the fine-tune head's, the step measured 3.28 ms on the narrow kernel and 3.35 on this one)
-    if (wide && (MN & 3) == 0 && (N & 3) == 0 && (ldo & 3) == 0 && S >= 64)
+    if ((MN & 3) == 0 && (N & 3) == 0 && (ldo & 3) == 0 && S >= 64)
         hipLaunchKernelGGL((splitk_reduce4_kernel<OutT>), dim3((unsigned)((MN / 4 + 15) / 16)), dim3(256), 0, st, part, S, MN, N, bias, act, out, resid, ldo, alpha);
     else
         hipLaunchKernelGGL((splitk_reduce_kernel<OutT>), dim3((unsigned)((MN + 63) / 64)), dim3(256), 0, st, part, S, MN, N, bias, act, out, resid, ldo, alpha);
@@ -300,7 +299,6 @@ static __global__ __launch_bounds__(256) void iti_x3_kernel(const float* __restr
 #pragma unroll
         for (int b = 0; b < 4; ++b) acc[a][b] = f32x4_v{0.f, 0.f, 0.f, 0.f};
     using S0 = std::integral_constant<int, 0>;
-    using S1 = std::integral_constant<int, 1>;
     auto ktile = [&](auto ST, int k) __attribute__((always_inline)) {
         constexpr int st = decltype(ST)::value;
 #pragma unroll
@@ -342,15 +340,7 @@ static __global__ __launch_bounds__(256) void iti_x3_kernel(const float* __restr
         __syncthreads();
     };
     fetch(S0{}, k0);
-    if constexpr (AHEAD == 2) {
-        fetch(S1{}, min(k0 + kstep, klast));
-        for (int k = k0; k <= klast; k += 2 * kstep) {
-            ktile(S0{}, k);
-            if (k + kstep <= klast) ktile(S1{}, k + kstep);
-        }
-    } else {
-        for (int k = k0; k <= klast; k += kstep) ktile(S0{}, k);
-    }
+    for (int k = k0; k <= klast; k += kstep) ktile(S0{}, k);
     float* out = part + (size_t)blockIdx.x * M * N;
     constexpr float inv = 1.0f / (16.f * 1024.f);
 #pragma unroll
@@ -575,10 +565,9 @@ static __global__ __launch_bounds__(256) void wc_pack_kernel(const float* __rest
     *reinterpret_cast<uint16_t*>(seg + (c >> 1)) = pack_fp4x4((v[0] - h[0]) * fd, (v[1] - h[1]) * fd, (v[2] - h[2]) * fd, (v[3] - h[3]) * fd);
     *reinterpret_cast<uint16_t*>(seg + (K >> 1) + (c >> 1)) = pack_fp4x4(v[0] * fw, v[1] * fw, v[2] * fw, v[3] * fw);
 }
-// Both adapter kernels in TWO launches per step instead of four and a memset (round 6): blockIdx.y = the tensor.  mx: per tensor 8 words -- [0] max |w - rn16(w)|,
-// [1] max |w| (float bits, accumulated with atomicMax: they must read 0 when the absmax launch starts), [2] a ticket counter, [4] / [5] the two scale exponents the
-// product reads (GemmArgs::mix_sptr).  The pack launch's LAST block -- by ticket, after every block has read the maxima -- puts [0], [1], [2] back to zero for the
-// next step: no memset node, and the same captured graph works every step.
+// Both adapter kernels in TWO launches per step instead of four and a memset (round 6): blockIdx.y = the tensor.  mx: words 8 y + 4 / 8 y + 5 hold tensor y's two
+// scale exponents, written by wc_pack2_kernel for the product (GemmArgs::mix_sptr); from word 16 on, one (max |w - rn16(w)|, max |w|) pair of float bits per absmax
+// block, which wc_pack2_kernel reduces.  Every word is overwritten each step and nothing accumulates: no memset node, and the same captured graph works every step.
 static __global__ __launch_bounds__(256) void wc_absmax2_kernel(const float* __restrict__ w0, const float* __restrict__ w1, size_t n, unsigned int* __restrict__ mx) {
     // one (max |w - rn16(w)|, max |w|) pair PER BLOCK at mx[16 + 2 (32 y + x)]: no atomics, nothing to reset (round 6: the accumulator form -- 512 atomicMax on two
     // addresses here, a 1 152-block ticket in the pack kernel to zero them again -- measured 10.8 + 17.0 us per step for 9 MB of traffic)

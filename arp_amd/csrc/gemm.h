@@ -503,9 +503,8 @@ inline int launch_gemm_nt(const GemmArgs& g, hipStream_t stream) {
     if (g.M <= 0) return 0;
     if constexpr (STAGES == 2) {
         // a grid that cannot even give every CU one workgroup, with a contraction long enough to pipeline: the four-stage instance
-        static const bool deep_ok = [] { const char* e = getenv("ARP_GEMM_DEEP"); return !e || atoi(e) != 0; }();
         const long wgs = (long)((g.M + GEMM_BM - 1) / GEMM_BM) * ((g.N + GEMM_BN - 1) / GEMM_BN) * (g.ksplit > 1 ? g.ksplit : 1);
-        if (deep_ok && wgs <= 128 && g.K / EPB >= 6) return launch_gemm_nt<T, OutT, ACT, RESID, SITE, 4>(g, stream);
+        if (wgs <= 128 && g.K / EPB >= 6) return launch_gemm_nt<T, OutT, ACT, RESID, SITE, 4>(g, stream);
     }
     if (g.N <= 0 || g.K % EPB != 0 || g.K <= 0 || g.lda % (16 / (int)sizeof(T)) != 0 || g.ldw % (16 / (int)sizeof(T)) != 0)
         return fail("gemm_nt: unsupported shape M=" + std::to_string(g.M) + " N=" + std::to_string(g.N) +

@@ -152,8 +152,7 @@ static int launch_preprocess(const ResizePlan& p, const uint8_t* frames, int n, 
     a.R = p.R; a.P = P; a.kmax_h = p.kmax_h; a.kmax_v = p.kmax_v; a.TR = p.TR; a.max_rows = p.max_rows;
     // short filters + dword-aligned rows: the register-unpacking instance; anything else: the generic one
     const bool fast = p.kmax_h <= 8 && p.kmax_v <= 8 && ((p.cw * 3) & 3) == 0 && !getenv("ARP_PREPROCESS_GENERIC");
-    int kt = std::max(p.kmax_h, p.kmax_v);
-    if (const char* e = getenv("ARP_PRE_KT")) kt = std::max(kt, atoi(e));  // A/B: force a longer instance (8 = the round-2 kernel)
+    const int kt = std::max(p.kmax_h, p.kmax_v);
     auto kern = !fast ? preprocess_kernel<T, LAYOUT> : (kt <= 5 ? preprocess_fast_kernel<T, LAYOUT, 5> : (kt <= 6 ? preprocess_fast_kernel<T, LAYOUT, 6> : preprocess_fast_kernel<T, LAYOUT, 8>));
     ARP_HIP_OK(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
                                    (int)p.lds_bytes));

@@ -233,8 +233,6 @@ static int launch_qkv_attn_impl(QkvAttnArgs g, hipStream_t stream) {
     g.fpt = 256 / g.N;
     if (g.nq <= 0 || g.nq > g.N) g.nq = g.N;
     g.scale = 1.0f / sqrtf(64.0f);
-    static const int group_env = getenv("ARP_QA_GROUP_M") ? atoi(getenv("ARP_QA_GROUP_M")) : 0;
-    if (group_env > 0) g.group_m = group_env;
     auto kern = qkv_attn_kernel<T>;
     static bool attr_set = false;
     if (!attr_set) {

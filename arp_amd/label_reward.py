@@ -245,26 +245,6 @@ def _open_store(data_path, mode="a"):
     raise ValueError(f"unsupported data file {data_path!r}: pass store=<mapping of arrays> instead")
 
 
-def _big_buffer(n_elems, dtype):
-    """A frame buffer of ~200 MB that is filled once per batch and dropped at the end of the pass.  ARP_LABEL_HUGEPAGES=1 asks for
-    transparent huge pages (anonymous memory + MADV_HUGEPAGE): 49 k page faults going in and an munmap of as many pages coming out cost
-    ~9 ms each per buffer with 4 KiB pages (six buffers: 50 ms of a 220 ms file pass).  OFF by default -- measured on the MI355X host
-    it is a loss: 0.81 s instead of 0.21 s for the 8192-row pass (2 MiB pages zeroed inside the faults of 32 inflate threads, with
-    the host's `defrag = madvise` compaction in the way); on an idle 8-core box the same switch took first touch from 885 to 130 ms."""
-    nbytes = int(n_elems) * np.dtype(dtype).itemsize
-    try:
-        import mmap
-        if nbytes >= (8 << 20) and hasattr(mmap, "MADV_HUGEPAGE") and os.environ.get("ARP_LABEL_HUGEPAGES", "0") == "1":
-            mm = mmap.mmap(-1, nbytes + (2 << 20))
-            mm.madvise(mmap.MADV_HUGEPAGE)
-            base = np.frombuffer(mm, np.uint8)
-            off = (-base.ctypes.data) % (2 << 20)  # start on a 2 MiB boundary: every huge page of the range is whole
-            return base[off : off + nbytes].view(dtype)
-    except (OSError, ValueError, ImportError):
-        pass
-    return np.empty(int(n_elems), dtype)
-
-
 _FRAME_POOL = []  # frame buffers of earlier label_store passes in this process (dropping one costs ~9 ms of munmap; a later pass --
                   # the next image key, the next demonstration file -- takes them back).  release_frame_buffers() empties it.
 
@@ -277,7 +257,7 @@ def _take_frame_buffer(n_elems, dtype):
     for i, b in enumerate(_FRAME_POOL):
         if b.dtype == np.dtype(dtype) and b.size >= n_elems:
             return _FRAME_POOL.pop(i)
-    return _big_buffer(n_elems, dtype)
+    return np.empty(int(n_elems), dtype)
 
 
 class RowSink:
@@ -433,20 +413,10 @@ def label_store(store, clip_model, compute_reward, image_keys="ob", model_type="
             # the next is submitted, so the GPU does not drain between batches (a synchronous call pays the pipeline's fill and drain)
             pipelined = (model_type == "clip" and getattr(clip_model, "label_submit", None) is not None and os.environ.get("ARP_LABEL_PIPELINE", "1") != "0"
                          and max(sum(b - a for a, b in g) for g in groups) <= getattr(clip_model, "max_batch", 0))
-            pinned = []
             bufs = []
             for _ in range(min(len(groups) + 1, 5 if pipelined else 4)):  # filling + two read ahead + one in flight + the one being submitted
                 buf = _take_frame_buffer(max(sum(b - a for a, b in g) for g in groups) * frame_elems, ds.dtype)
                 bufs.append(buf)
-                # (ARP_LABEL_PIN=1 pins the buffers -- arp_host_register.  Measured, and therefore OFF by default: registering 200 MB costs
-                # ~15 ms per buffer while the staged pageable upload already runs at the link rate, 56.5 against 57.4 GB/s, and overlaps the
-                # pass equally well: profiles/r3_seam_probe.txt)
-                if getattr(clip_model, "pin_host", None) is not None and os.environ.get("ARP_LABEL_PIN", "0") == "1":
-                    try:
-                        clip_model.pin_host(buf)
-                        pinned.append(buf)
-                    except Exception:
-                        pass
                 free.put(buf)
 
             def read(g):
@@ -499,8 +469,6 @@ def label_store(store, clip_model, compute_reward, image_keys="ob", model_type="
             if inflight is not None:
                 emit(inflight[1], clip_model.label_collect(inflight[0]))
                 free.put(inflight[2])
-            for buf in pinned:
-                clip_model.unpin_host(buf)
             del _FRAME_POOL[: max(0, len(_FRAME_POOL) + len(bufs) - 6)]
             _FRAME_POOL.extend(bufs)
             if timing:

@@ -32,6 +32,37 @@ def test_abi_exports_every_declared_symbol():
     assert _ffi.lib.arp_version() >= 100
 
 
+def _env_reads():
+    names = set()
+    csrc = os.path.join(ROOT, "arp_amd", "csrc")
+    for f in sorted(os.listdir(csrc)):
+        if f.endswith((".hip", ".h", ".cpp")):
+            names |= set(re.findall(r'\bgetenv\("(ARP_[A-Z0-9_]+)"', open(os.path.join(csrc, f)).read()))
+    pkg = os.path.join(ROOT, "arp_amd")
+    for f in sorted(os.listdir(pkg)):
+        if f.endswith(".py"):
+            names |= set(re.findall(r'\bos\.environ(?:\.get\(|\.setdefault\(|\[)\s*"(ARP_[A-Z0-9_]+)"', open(os.path.join(pkg, f)).read()))
+    return names
+
+
+def _switch_table():
+    txt = open(os.path.join(ROOT, "INTEGRATION.md")).read()
+    sec = txt.split("\n## Runtime switches", 1)[1].split("\n## ", 1)[0]
+    names = set()
+    for line in sec.splitlines():
+        if line.startswith("|"):
+            names |= set(re.findall(r"\bARP_[A-Z0-9_]+", line.split("|")[1]))
+    return names
+
+
+def test_switch_table_lists_every_runtime_switch():
+    """INTEGRATION.md's "Runtime switches" table names exactly the ARP_* environment variables the library and the package read."""
+    read, listed = _env_reads(), _switch_table()
+    assert len(read) >= 40
+    assert not read - listed, f"read but not in INTEGRATION.md's switch table: {sorted(read - listed)}"
+    assert not listed - read, f"in INTEGRATION.md's switch table but read nowhere: {sorted(listed - read)}"
+
+
 def test_no_cpu_fallback():
     """Without a GPU the product path must fail loudly, never compute on the CPU."""
     from arp_amd import _ffi, clip
