@@ -10,8 +10,11 @@ no collective on the data path; `value` = frames labelled by all ranks / max-ove
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
 
-Prints ONE JSON line on rank 0 with the contract keys plus `roofline` (dominant kernel, HIP-event
-timed per launch) and `cpu_baseline` (torch-CPU port of the same pass, timed on this host).
+A plain run sets up, warms up, times the steps, writes --dump-outputs and prints ONE JSON line on rank 0
+with the contract keys and the workload.  --full adds everything else the benchmark measures and checks:
+the secondary benches, `cpu_baseline` (torch-CPU port of the same pass, timed on this host), the parity
+gate against the oracle, the host-fed seam, `roofline` (dominant kernel, HIP-event timed per launch), the
+held clock, the single-stream pass and the bf16 parity line.
 """
 import argparse
 import json
@@ -326,7 +329,7 @@ def run_secondary(a):
     extra = {}
     for name, args in runs.items():
         cmd = [sys.executable, os.path.abspath(__file__), "--gpus", "1", "--steps", str(a.steps), "--warmup", str(a.warmup), "--cpu-seconds",
-               str(cpu_s.get(name, 0)), "--no-secondary"] + args
+               str(cpu_s.get(name, 0)), "--no-secondary", "--full"] + args
         try:
             r = subprocess.run(cmd, cwd=ROOT, capture_output=True, text=True, timeout=900, env=dict(os.environ, ARP_BENCH_CHILD="1"))
             line = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
@@ -361,6 +364,32 @@ def summarize_extra(extra, seam):
             e = {"file_to_file_frames_per_s": d.get("value"), "later_pass": d.get("later_pass_frames_per_s"), "rows": d.get("rows")}
         out[name] = e
     return out
+
+
+def label_headline(a, world, elapsed, nsplit):
+    """The label path's contract keys and workload: the whole line of a plain run, the head of the --full report"""
+    return {
+        "metric": "frames/sec CLIP reward-labelled (256x256 ViT-B/32)" if a.model == "ViT-B/32" else f"frames/sec CLIP reward-labelled (256x256 {a.model})",
+        "value": world * a.batch * a.steps / elapsed,
+        "unit": "frames/s",
+        "n_gpus": world,
+        "steps": a.steps,
+        "warmup": a.warmup,
+        "ms_per_step": elapsed / a.steps * 1e3,
+        "higher_is_better": True,
+        "scaling": "weak",
+        "vs_baseline": None,
+        "dtype": a.mode,
+        "data": "synthetic",
+        "config": {"workload": f"CLIP {a.model} reward labelling, batch {a.batch} synthetic 256x256x3 uint8 frames per GPU resident in HBM "
+                               f"(BASELINE.json configs[1]), random-init weights, text tower cached", "frames_per_gpu_per_step": a.batch,
+                   "operands": {"f16": "IEEE half MFMA operands (same 2.5 PF dense rate as bf16), f32 accumulate / residual / LayerNorm / softmax; "
+                                       "rewards within north_star's 1e-4 of the fp32 oracle -- bf16 operands are not (alt_dtype)",
+                                "bf16": "bf16 MFMA operands, f32 accumulate / residual / LayerNorm / softmax",
+                                "f32": "f32-input MFMA"}[a.mode] + (" -- PLUS c_fc / c_proj of blocks 1..11 on e4m3 operands (--fp8-mlp: NOT the "
+                                "headline configuration; see parity)" if a.fp8_mlp else ""),
+                   "parallelism": f"shard{world} (no collective)", "streams_per_gpu": nsplit},
+    }
 
 
 def gather_rates(dist, world, units, elapsed_local):
@@ -1028,10 +1057,15 @@ def main():
     ap.add_argument("--mode", default=None, choices=["bf16", "f16", "f32"],
                     help="GEMM operand type; default f16 for the label path (same MFMA rate as bf16, rewards within 1e-4 of the fp32 "
                          "reference -- bf16 gives 3-8e-4), bf16 for the policy / finetune paths")
+    ap.add_argument("--full", action="store_true",
+                    help="label path: besides the headline figure, everything else the benchmark measures and checks -- the secondary benches "
+                         "(--all-secondary), the CPU baseline, the parity gate against the oracle, the host-fed seam, the per-launch profiled repeat "
+                         "(roofline), the held clock, the single-stream pass, the bf16 parity line -- reported as compact secondary lines and a "
+                         "headline line with those blocks.  The other --path benches always run in full")
     ap.add_argument("--no-alt-bf16", dest="alt_bf16", action="store_false",
-                    help="label path, f16 mode: skip the bf16-operand parity check reported as alt_dtype")
-    ap.add_argument("--cpu-seconds", type=float, default=15.0, help="0 disables the cpu_baseline leg")
-    ap.add_argument("--parity-frames", type=int, default=8, help="frames checked against the oracle before timing (rank 0)")
+                    help="label path, f16 mode, with --full: skip the bf16-operand parity check reported as alt_dtype")
+    ap.add_argument("--cpu-seconds", type=float, default=15.0, help="0 disables the cpu_baseline leg (label path: a --full leg)")
+    ap.add_argument("--parity-frames", type=int, default=8, help="frames checked against the oracle before timing (rank 0; label path: with --full)")
     ap.add_argument("--streams", type=int, default=2, help="label path: N = each batch is labelled in N contiguous parts on N HIP streams of "
                     "the same GPU (one half's LayerNorm/attention/GEMM tails overlap the other half's GEMMs); 1 = single stream")
     ap.add_argument("--h5-rows", type=int, default=4096, help="--path h5: rows (= labelled frames) of the generated demonstration file")
@@ -1061,10 +1095,10 @@ def main():
     ap.add_argument("--with-encoder", action="store_true", help="policy path: run the frozen M3AE ViT-B/16 encoder inside the step "
                     "(frames in, the reference's own boundary; SURVEY row N1) instead of feeding pre-computed encodings")
     ap.add_argument("--all-secondary", dest="all_secondary", action="store_true", default=True,
-                    help="label path, 1 GPU (default ON): after the headline line is measured, run the policy / policy --with-encoder / finetune / "
-                         "ViT-B/16 benches as child processes and append their JSON lines under `extra`, so that one driver run carries them")
-    ap.add_argument("--no-secondary", dest="all_secondary", action="store_false", help="headline line only")
-    ap.add_argument("--timed-only", action="store_true", help="label path: only the warm-up, the timed steps and the per-launch profiled repeat of the "
+                    help="label path, 1 GPU, with --full (default ON): before the headline line is measured, run the policy / policy --with-encoder / "
+                         "finetune / ViT-B/16 benches as child processes and append their JSON lines under `extra`, so that one run carries them")
+    ap.add_argument("--no-secondary", dest="all_secondary", action="store_false", help="with --full: no secondary benches")
+    ap.add_argument("--timed-only", action="store_true", help="label path, with --full: only the warm-up, the timed steps and the per-launch profiled repeat of the "
                     "same steps -- no seam calls, no isolated single-stream pass, no bf16 parity handle -- so that a rocprofv3 --stats run of this "
                     "command averages exactly the launches `roofline.avg_launch_ms` averages (scripts/prof_label.sh)")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
@@ -1092,12 +1126,12 @@ def main():
     a.gpus = world  # under torch.distributed.run / spawn_ranks the environment is authoritative
 
     cpu = None
-    if rank == 0 and world == 1 and a.cpu_seconds > 0:
+    if a.full and rank == 0 and world == 1 and a.cpu_seconds > 0:
         cpu = cpu_baseline(a.model, a.cpu_seconds)
     # The secondary benches run as child processes BEFORE this process touches the GPU (a process that has initialised the GPU must
-    # not fork + exec another program on this pool), one after the other, each alone on the device; the headline bench follows.
+    # not fork + exec another program), one after the other, each alone on the device; the headline bench follows.
     extra = None
-    if rank == 0 and world == 1 and a.all_secondary and a.model == "ViT-B/32" and not a.fp8_mlp and a.batch == 1024 and a.mode == "f16":
+    if a.full and rank == 0 and world == 1 and a.all_secondary and a.model == "ViT-B/32" and not a.fp8_mlp and a.batch == 1024 and a.mode == "f16":
         extra = run_secondary(a)
 
     dist = None
@@ -1119,7 +1153,7 @@ def main():
 
     # parity gate on a few frames (rank 0): the thing timed below is the thing checked here
     parity = None
-    if rank == 0 and a.parity_frames > 0:
+    if a.full and rank == 0 and a.parity_frames > 0:
         from oracle import clip_np
         ocfg = clip_np.ClipConfig(patch=cfg.patch)
         fr = synth.procgen_like_frames(a.parity_frames, seed=1)
@@ -1158,8 +1192,9 @@ def main():
     barrier()
     elapsed = t1 - t0
     ev_ms = clip.elapsed_ms(e0, e1)
-    per_rank = gather_rates(dist, world, a.batch * a.steps, elapsed)
-    ranks_seen = label_ranks_seen(dist, rank, world, local_rank)
+    if a.full:
+        per_rank = gather_rates(dist, world, a.batch * a.steps, elapsed)
+        ranks_seen = label_ranks_seen(dist, rank, world, local_rank)
     if dist is not None:
         import torch
         t = torch.tensor([elapsed], dtype=torch.float64)
@@ -1169,6 +1204,14 @@ def main():
     assert np.isfinite(rewards).all(), "non-finite rewards"
     if a.dump_outputs:  # d_rewards still holds the last timed step's rewards (nothing has been enqueued since)
         dump_outputs(a.dump_outputs, {"rewards" if rank == 0 else f"rewards_rank{rank}": rewards})
+    nsplit = max(1, min(a.streams, a.batch // 128))  # parts a batch is labelled in, one HIP stream each (label_dev in arp_clip.hip)
+    if not a.full:  # a plain run: the headline line alone
+        if rank == 0:
+            emit(json.dumps(sig(label_headline(a, world, elapsed, nsplit))))
+        model.close()
+        if dist is not None:
+            dist.destroy_process_group()
+        return
 
     # ---- the S2 seam as the reference calls it (label_reward.py:132-146: host frames in, host rewards out), OUTSIDE the timed
     # region: arp_clip_label incl. the H2D upload over PCIe and the D2H of the rewards.  Never `value`.
@@ -1240,7 +1283,6 @@ def main():
         model.profile(True)
     # isolated per-kernel figures: the same steps on ONE stream (no other kernel shares the chip with a launch)
     iso = None
-    nsplit = max(1, min(a.streams, a.batch // 128))  # parts a batch is labelled in, one HIP stream each (label_dev in arp_clip.hip)
     if nsplit > 1 and not a.timed_only:
         model.set_streams(1)
         step()
@@ -1288,34 +1330,15 @@ def main():
                     traffic = traffic * (-(-a.batch // nsplit)) / rec["frames_per_launch"]
             except Exception:
                 traffic = None
-        fps = world * a.batch * a.steps / elapsed
+        out = label_headline(a, world, elapsed, nsplit)
+        fps = out["value"]
         flops_frame = clip.flops_per_frame(cfg)
         exec_flops = flops_frame - (0 if os.environ.get("ARP_CLS_ONLY") == "0" else 2.0 * (cfg.tokens - 1) * 9 * cfg.width * cfg.width)
         kname = {"vit.qkv_attn": "qkv_attn_kernel"}.get(dom, "gemm2w_kernel" if os.environ.get("ARP_GEMM") == "3" else "gemm256_nt_kernel")
         total_ms = sum(v["ms"] for v in prof.values())
-        out = {
-            "metric": "frames/sec CLIP reward-labelled (256x256 ViT-B/32)" if a.model == "ViT-B/32" else f"frames/sec CLIP reward-labelled (256x256 {a.model})",
-            "value": fps,
-            "unit": "frames/s",
-            "n_gpus": world,
-            "steps": a.steps,
-            "warmup": a.warmup,
-            "ms_per_step": elapsed / a.steps * 1e3,
-            "higher_is_better": True,
-            "scaling": "weak",
-            "vs_baseline": None,
-            "dtype": a.mode,
-            "data": "synthetic",
+        out.update({
             # the secondary lines of this run in brief (the full lines are under `extra` at the end; a log tail may cut them off)
             "extra_summary": summarize_extra(extra, seam),
-            "config": {"workload": f"CLIP {a.model} reward labelling, batch {a.batch} synthetic 256x256x3 uint8 frames per GPU resident in HBM "
-                                   f"(BASELINE.json configs[1]), random-init weights, text tower cached", "frames_per_gpu_per_step": a.batch,
-                       "operands": {"f16": "IEEE half MFMA operands (same 2.5 PF dense rate as bf16), f32 accumulate / residual / LayerNorm / softmax; "
-                                           "rewards within north_star's 1e-4 of the fp32 oracle -- bf16 operands are not (alt_dtype)",
-                                    "bf16": "bf16 MFMA operands, f32 accumulate / residual / LayerNorm / softmax",
-                                    "f32": "f32-input MFMA"}[a.mode] + (" -- PLUS c_fc / c_proj of blocks 1..11 on e4m3 operands (--fp8-mlp: NOT the "
-                                    "headline configuration; see parity)" if a.fp8_mlp else ""),
-                       "parallelism": f"shard{world} (no collective)", "streams_per_gpu": nsplit},
             "roofline": {"bound": "mfma", "achieved": achieved, "peak": peak, "unit": "TFLOP/s", "frac": achieved / peak,
                          "traffic": traffic, "traffic_stale": traffic_stale, "mfma_util_pct": mfma_util,
                          "traffic_source": None if traffic is None else "profiles/pmc_traffic.json: committed rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes of this kernel, scaled to this launch's frames; NOT measured in this run",
@@ -1349,7 +1372,7 @@ def main():
             "sites_total_ms_per_step": total_ms / a.steps,
             "per_rank_frames_per_s": [round(v, 1) for v in per_rank],
             "ranks_seen": ranks_seen,
-        }
+        })
         if os.environ.get("ARP_BENCH_CHILD"):
             emit(json.dumps(out))
         else:

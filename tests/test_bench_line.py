@@ -37,6 +37,21 @@ def test_headline_of_the_round4_object_fits_and_keeps_the_contract():
     assert "workload" in head["config"]
 
 
+def test_a_plain_run_prints_the_contract_keys_of_the_full_headline():
+    """without --full the label path prints label_headline alone; --full builds its headline on the same object (round 6's run as the pin)"""
+    import argparse
+    full = json.load(open(os.path.join(ROOT, "profiles", "r6_bench_full.json")))
+    a = argparse.Namespace(model="ViT-B/32", batch=1024, steps=20, warmup=5, mode="f16", fp8_mlp=False)
+    head = bench.label_headline(a, 1, full["ms_per_step"] * 20 / 1e3, full["config"]["streams_per_gpu"])
+    assert list(head) == CONTRACT
+    assert head["value"] == pytest.approx(full["value"], rel=1e-9) and head["ms_per_step"] == pytest.approx(full["ms_per_step"], rel=1e-12)
+    for k in CONTRACT:
+        if k not in ("value", "ms_per_step"):
+            assert head[k] == full[k], k
+    line = json.dumps(bench.sig(head))
+    assert len(line) <= bench.HEADLINE_LIMIT and json.loads(line)["value"] == pytest.approx(full["value"], rel=1e-4)
+
+
 def test_every_secondary_line_fits_and_names_its_numbers():
     _, extra = r4_objects()
     for name, d in extra.items():
