@@ -37,7 +37,11 @@ class ClipCfg(C.Structure):
 class DtCfg(C.Structure):
     _fields_ = [(n, C.c_int32) for n in (
         "emb", "depth", "heads", "mlp_ratio", "n_actions", "window", "enc_tokens", "enc_dim", "use_adapter", "mode",
-        "device", "world", "rank")] + [(n, C.c_float) for n in ("lambda_ret", "weight_decay", "clip_norm", "b1", "b2", "eps")] + [("alibi_bias", C.c_int32)]
+        "device", "world", "rank")] + [(n, C.c_float) for n in ("lambda_ret", "weight_decay", "clip_norm", "b1", "b2", "eps")] + [("alibi_bias", C.c_int32), ("model", C.c_int32)]
+
+
+# arp_dt_cfg.model (include/arp_hip.h): which policy a handle trains
+DT_MODELS = {"ARPDT": 0, "BC": 1}
 
 
 class FtCfg(C.Structure):

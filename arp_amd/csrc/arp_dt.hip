@@ -201,7 +201,10 @@ struct arp_dt {
     DevBuf colpart0;   // the dH1 GEMM's column partials when the small reductions are deferred (backward_adapter_tn)
     DevBuf dres_part;  // per-workgroup d loss / d res partials of adapter_dy_kernel
     int R() const { return B * cfg.window; }
-    int L() const { return 3 * cfg.window; }
+    // model BC (the InstructRL baseline, arp_dt/BC.py): two tokens per time step [image, action] instead of ARP-DT's three
+    bool bc() const { return cfg.model == ARP_DT_MODEL_BC; }
+    int tps() const { return bc() ? 2 : 3; }
+    int L() const { return tps() * cfg.window; }
     float* p(const std::string& n) { return params.as<float>() + infos[index.at(n)].off; }
     float* g(const std::string& n) { return grads.as<float>() + infos[index.at(n)].off; }
 };
@@ -238,7 +241,8 @@ void build_layout(arp_dt* c) {
     add_param(c, v, "image_text_input/kernel", {(int64_t)k.enc_tokens * D, E});
     add_param(c, v, "image_text_input/bias", {E});
     add_param(c, v, "action_input/embedding", {k.n_actions, E});
-    add_param(c, v, "rtg_input/kernel", {1, E});
+    const bool bc = k.model == ARP_DT_MODEL_BC;  // BC.py:87-100: no rtg_input, no return_outputs_*; otherwise ARP-DT's tree
+    if (!bc) add_param(c, v, "rtg_input/kernel", {1, E});
     for (int i = 0; i < k.depth; ++i) {
         const std::string p = "policy/Block_" + std::to_string(i) + "/";
         for (const char* ln : {"LayerNorm_0", "LayerNorm_1"}) {
@@ -255,6 +259,7 @@ void build_layout(arp_dt* c) {
     add_param(c, v, "policy/LayerNorm_0/scale", {E});
     add_param(c, v, "policy/LayerNorm_0/bias", {E});
     for (auto hn : {std::make_pair(std::string("action_outputs_0"), k.n_actions), std::make_pair(std::string("return_outputs_0"), 1)}) {
+        if (bc && hn.first == "return_outputs_0") continue;
         add_param(c, v, hn.first + "/layers_0/kernel", {E, E});
         add_param(c, v, hn.first + "/layers_0/bias", {E});
         add_param(c, v, hn.first + "/layers_2/kernel", {E, hn.second});
@@ -432,14 +437,15 @@ template <typename T> int refresh_shadows(arp_dt* c) {
     return 0;
 }
 
-// The fused kernel covers the shipped geometry family: up to 16 tokens per sample, widths in MFMA-tile multiples.
+// The fused kernel covers the shipped geometry family: up to 16 tokens per sample (ARP-DT: window <= 5, BC: window <= 8), widths in MFMA-tile multiples.
 bool fused_eligible(const arp_dt_cfg& k) {
     if (const char* e = getenv("ARP_DT_FUSED"))
         if (atoi(e) == 0) return false;
     const int E = k.emb, H = k.mlp_ratio * k.emb;
     // instantiated geometries: the shipped one (E = 128, mlp_ratio 4) and the half-width one the tests use
     const bool shape = (E == 128 && H == 512) || (E == 64 && H == 256);
-    return shape && 3 * k.window <= 16 && k.n_actions <= 16 && k.depth <= PF_MAX_DEPTH && E % k.heads == 0 && (E / k.heads) % 16 == 0 &&
+    const int tps = k.model == ARP_DT_MODEL_BC ? 2 : 3;
+    return shape && tps * k.window <= 16 && k.n_actions <= 16 && k.depth <= PF_MAX_DEPTH && E % k.heads == 0 && (E / k.heads) % 16 == 0 &&
            pf_lds_bytes(E, H, k.heads, k.depth) <= 160 * 1024;
 }
 
@@ -466,8 +472,9 @@ std::vector<float> alibi_slopes(int n) {
 
 int build_fused_plan(arp_dt* c) {
     const arp_dt_cfg& k = c->cfg;
-    const int E = k.emb, H = k.mlp_ratio * E, T = k.window, L = 3 * T, NA = k.n_actions, depth = k.depth;
+    const int E = k.emb, H = k.mlp_ratio * E, T = k.window, L = c->L(), NA = k.n_actions, depth = k.depth;
     const int R = c->B * T, BL = c->B * L;
+    const bool bc = c->bc();  // (no rtg_input, no return head: their pointers stay null and the BC kernel never reads them)
     PfArgs& a = c->pf;
     memset(&a, 0, sizeof(a));
     a.T = T; a.L = L; a.E = E; a.H = H; a.heads = k.heads; a.NA = NA; a.depth = depth; a.do_bwd = 1; a.R = R; a.lambda = k.lambda_ret;
@@ -475,8 +482,8 @@ int build_fused_plan(arp_dt* c) {
         const std::vector<float> sl = alibi_slopes(k.heads);
         for (int h = 0; h < 16; ++h) a.alibi[h] = (k.alibi_bias && h < k.heads) ? sl[h] : 0.f;
     }
-    a.img = c->img.as<float>(); a.rtg = c->bt[c->cur].rtg.as<float>(); a.action = c->bt[c->cur].action.as<int>();
-    a.Wr = c->p("rtg_input/kernel"); a.emb = c->p("action_input/embedding");
+    a.img = c->img.as<float>(); a.rtg = bc ? nullptr : c->bt[c->cur].rtg.as<float>(); a.action = c->bt[c->cur].action.as<int>();
+    a.Wr = bc ? nullptr : c->p("rtg_input/kernel"); a.emb = c->p("action_input/embedding");
     std::vector<SmallGemm> gj;
     std::vector<ColSumJob> cj;
     // dW[Nout, Kin] = dY[rows, Nout]^T . X[rows, Kin]
@@ -507,7 +514,7 @@ int build_fused_plan(arp_dt* c) {
     }
     a.lnfw = c->p("policy/LayerNorm_0/scale"); a.lnfb = c->p("policy/LayerNorm_0/bias");
     a.wa0 = c->p("action_outputs_0/layers_0/kernel"); a.ba0 = c->p("action_outputs_0/layers_0/bias"); a.wa2 = c->p("action_outputs_0/layers_2/kernel");
-    a.wr0 = c->p("return_outputs_0/layers_0/kernel"); a.br0 = c->p("return_outputs_0/layers_0/bias"); a.wr2 = c->p("return_outputs_0/layers_2/kernel");
+    if (!bc) { a.wr0 = c->p("return_outputs_0/layers_0/kernel"); a.br0 = c->p("return_outputs_0/layers_0/bias"); a.wr2 = c->p("return_outputs_0/layers_2/kernel"); }
     {
         // fragment-major copies (nt for the forward, nn for the backward) of every weight pf_lin_nt / pf_lin_nn stream; filled by
         // pf_pack_kernel at the head of every launch of the fused kernel (the parameters change every step)
@@ -518,7 +525,8 @@ int build_fused_plan(arp_dt* c) {
         for (int i = 0; i < depth; ++i) {
             want(a.blk[i].wqkv, 3 * E, E); want(a.blk[i].wo, E, E); want(a.blk[i].wfc1, H, E); want(a.blk[i].wfc2, E, H);
         }
-        want(a.wa0, E, E); want(a.wr0, E, E);
+        want(a.wa0, E, E);
+        if (!bc) want(a.wr0, E, E);
         ARP_TRY(c->pf_pack.ensure(total * 4));
         float* base = c->pf_pack.as<float>();
         int maxq = 0;
@@ -532,7 +540,8 @@ int build_fused_plan(arp_dt* c) {
             b.wqkv_nt = jobs[4 * i].nt; b.wqkv_nn = jobs[4 * i].nn; b.wo_nt = jobs[4 * i + 1].nt; b.wo_nn = jobs[4 * i + 1].nn;
             b.wfc1_nt = jobs[4 * i + 2].nt; b.wfc1_nn = jobs[4 * i + 2].nn; b.wfc2_nt = jobs[4 * i + 3].nt; b.wfc2_nn = jobs[4 * i + 3].nn;
         }
-        a.wa0_nt = jobs[4 * depth].nt; a.wa0_nn = jobs[4 * depth].nn; a.wr0_nt = jobs[4 * depth + 1].nt; a.wr0_nn = jobs[4 * depth + 1].nn;
+        a.wa0_nt = jobs[4 * depth].nt; a.wa0_nn = jobs[4 * depth].nn;
+        if (!bc) { a.wr0_nt = jobs[4 * depth + 1].nt; a.wr0_nn = jobs[4 * depth + 1].nn; }
         ARP_TRY(c->pf_jobs.ensure(jobs.size() * sizeof(PfPackJob)));
         ARP_HIP_OK(hipMemcpy(c->pf_jobs.p, jobs.data(), jobs.size() * sizeof(PfPackJob), hipMemcpyHostToDevice));
         c->pf_njobs = (int)jobs.size();
@@ -544,10 +553,13 @@ int build_fused_plan(arp_dt* c) {
     a.dtok = c->dtok.as<float>(); a.dz = c->dz.as<float>(); a.loss_part = c->loss_part.as<float>();
     add_dw(a.dlogits, a.ha, c->g("action_outputs_0/layers_2/kernel"), NA, E, R);
     add_dw(a.dha, a.a_in, c->g("action_outputs_0/layers_0/kernel"), E, E, R);
-    add_dw(a.dret, a.hr, c->g("return_outputs_0/layers_2/kernel"), 1, E, R);
-    add_dw(a.dhr, a.r_in, c->g("return_outputs_0/layers_0/kernel"), E, E, R);
+    if (!bc) {
+        add_dw(a.dret, a.hr, c->g("return_outputs_0/layers_2/kernel"), 1, E, R);
+        add_dw(a.dhr, a.r_in, c->g("return_outputs_0/layers_0/kernel"), E, E, R);
+    }
     add_cs(a.dwsf, c->g("policy/LayerNorm_0/scale"), BL, E); add_cs(a.dbsf, c->g("policy/LayerNorm_0/bias"), BL, E);
-    add_cs(a.dha, c->g("action_outputs_0/layers_0/bias"), R, E); add_cs(a.dhr, c->g("return_outputs_0/layers_0/bias"), R, E);
+    add_cs(a.dha, c->g("action_outputs_0/layers_0/bias"), R, E);
+    if (!bc) add_cs(a.dhr, c->g("return_outputs_0/layers_0/bias"), R, E);
     add_cs(a.dz, c->g("image_text_input/bias"), R, E);
     std::vector<int> gp(1, 0), cp(1, 0);
     for (auto& g : gj) gp.push_back(gp.back() + cdiv(g.M, 32) * cdiv(g.N, 32));
@@ -565,6 +577,10 @@ int build_fused_plan(arp_dt* c) {
         ARP_HIP_OK(hipFuncSetAttribute(reinterpret_cast<const void*>(policy_fused_kernel<64, 256>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
         ARP_HIP_OK(hipFuncSetAttribute(reinterpret_cast<const void*>(policy_fused_kernel<128, 512, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
         ARP_HIP_OK(hipFuncSetAttribute(reinterpret_cast<const void*>(policy_fused_kernel<64, 256, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+        ARP_HIP_OK(hipFuncSetAttribute(reinterpret_cast<const void*>(policy_fused_bc_kernel<128, 512>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+        ARP_HIP_OK(hipFuncSetAttribute(reinterpret_cast<const void*>(policy_fused_bc_kernel<64, 256>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+        ARP_HIP_OK(hipFuncSetAttribute(reinterpret_cast<const void*>(policy_fused_bc_kernel<128, 512, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+        ARP_HIP_OK(hipFuncSetAttribute(reinterpret_cast<const void*>(policy_fused_bc_kernel<64, 256, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
         attr_set = true;
     }
     return 0;
@@ -575,7 +591,7 @@ int ensure_buffers(arp_dt* c, int B) {
     const arp_dt_cfg& k = c->cfg;
     const size_t e = c->esz();
     const int E = k.emb, D = k.enc_dim, H = k.mlp_ratio * E, T = k.window, NA = k.n_actions;
-    const size_t R = (size_t)B * T, Mx = R * k.enc_tokens, BL = R * 3, Kin = (size_t)k.enc_tokens * D;
+    const size_t R = (size_t)B * T, Mx = R * k.enc_tokens, BL = R * c->tps(), Kin = (size_t)k.enc_tokens * D;
     const size_t Mxp = (Mx + 63) / 64 * 64, Rp = (R + 63) / 64 * 64;
     // (the batch slots size their own buffers: stage_slot)
     // TN path: these are GEMM operands whose contraction index is the ROW -- rows up to the next multiple of 64 must read as zeros
@@ -631,7 +647,7 @@ int ensure_buffers(arp_dt* c, int B) {
 int policy_fused(arp_dt* c, bool do_bwd) {
     const arp_dt_cfg& k = c->cfg;
     c->pf.do_bwd = do_bwd ? 1 : 0;
-    c->pf.rtg = c->bt[c->cur].rtg.as<float>();  // the CURRENT batch slot's labels (the plan was built when the geometry last changed)
+    c->pf.rtg = c->bc() ? nullptr : c->bt[c->cur].rtg.as<float>();  // the CURRENT batch slot's labels (the plan was built when the geometry last changed)
     c->pf.action = c->bt[c->cur].action.as<int>();
     // the scaled operand-type copy of dz (the TN backward's first operand) straight from the kernel instead of a transpose_mask launch behind it
     const bool dzb_here = do_bwd && c->merge_small && c->use_tn() && k.mode != ARP_MODE_F32 && c->dzb.p;
@@ -641,7 +657,12 @@ int policy_fused(arp_dt* c, bool do_bwd) {
     c->dzb_from_pf = dzb_here;
     const size_t lds = pf_lds_bytes(k.emb, k.mlp_ratio * k.emb, k.heads, k.depth);
     hipLaunchKernelGGL(pf_pack_kernel, dim3(c->pf_pack_blocks, c->pf_njobs), dim3(256), 0, c->stream, static_cast<const PfPackJob*>(c->pf_jobs.p));
-    if (k.emb == 128 && c->pf_x3) hipLaunchKernelGGL((policy_fused_kernel<128, 512, true>), dim3(c->B), dim3(PF_THREADS), lds, c->stream, c->pf);
+    if (c->bc()) {  // the same body with two tokens per time step (policy_fused.h)
+        if (k.emb == 128 && c->pf_x3) hipLaunchKernelGGL((policy_fused_bc_kernel<128, 512, true>), dim3(c->B), dim3(PF_THREADS), lds, c->stream, c->pf);
+        else if (k.emb == 128) hipLaunchKernelGGL((policy_fused_bc_kernel<128, 512>), dim3(c->B), dim3(PF_THREADS), lds, c->stream, c->pf);
+        else if (c->pf_x3) hipLaunchKernelGGL((policy_fused_bc_kernel<64, 256, true>), dim3(c->B), dim3(PF_THREADS), lds, c->stream, c->pf);
+        else hipLaunchKernelGGL((policy_fused_bc_kernel<64, 256>), dim3(c->B), dim3(PF_THREADS), lds, c->stream, c->pf);
+    } else if (k.emb == 128 && c->pf_x3) hipLaunchKernelGGL((policy_fused_kernel<128, 512, true>), dim3(c->B), dim3(PF_THREADS), lds, c->stream, c->pf);
     else if (k.emb == 128) hipLaunchKernelGGL((policy_fused_kernel<128, 512>), dim3(c->B), dim3(PF_THREADS), lds, c->stream, c->pf);
     else if (c->pf_x3) hipLaunchKernelGGL((policy_fused_kernel<64, 256, true>), dim3(c->B), dim3(PF_THREADS), lds, c->stream, c->pf);
     else hipLaunchKernelGGL((policy_fused_kernel<64, 256>), dim3(c->B), dim3(PF_THREADS), lds, c->stream, c->pf);
@@ -884,8 +905,9 @@ template <typename T> int forward(arp_dt* c, bool with_bwd = false) {
         ARP_TRY(policy_fused(c, with_bwd));
     } else {
         ProfScope ps(c->prof, c->stream, "dt.policy_fwd");
-        hipLaunchKernelGGL(tokens_fwd_kernel, dim3(cdiv((size_t)R * E, 256)), dim3(256), 0, c->stream, c->img.as<float>(), c->bt[c->cur].rtg.as<float>(),
-                           c->bt[c->cur].action.as<int>(), c->p("rtg_input/kernel"), c->p("action_input/embedding"), c->xs[0].as<float>(), R, E);
+        const bool bc = c->bc();
+        hipLaunchKernelGGL(tokens_fwd_kernel, dim3(cdiv((size_t)R * E, 256)), dim3(256), 0, c->stream, c->img.as<float>(), bc ? nullptr : c->bt[c->cur].rtg.as<float>(),
+                           c->bt[c->cur].action.as<int>(), bc ? nullptr : c->p("rtg_input/kernel"), c->p("action_input/embedding"), c->xs[0].as<float>(), R, E, c->tps());
         ARP_HIP_OK(hipGetLastError());
         for (int i = 0; i < depth; ++i) {
             const std::string p = "policy/Block_" + std::to_string(i) + "/";
@@ -905,15 +927,17 @@ template <typename T> int forward(arp_dt* c, bool with_bwd = false) {
         }
         ARP_TRY(ln_fwd(c, c->xs[depth].as<float>(), c->p("policy/LayerNorm_0/scale"), c->p("policy/LayerNorm_0/bias"), c->hf.as<float>(), BL, E));
         hipLaunchKernelGGL(heads_gather_kernel, dim3(cdiv((size_t)R * E, 256)), dim3(256), 0, c->stream, c->hf.as<float>(), c->a_in.as<float>(),
-                           c->r_in.as<float>(), R, E);
+                           c->r_in.as<float>(), R, E, c->tps());
         ARP_TRY(linear_fwd(c, c->a_in.as<float>(), c->p("action_outputs_0/layers_0/kernel"), c->p("action_outputs_0/layers_0/bias"), nullptr,
                            c->ha.as<float>(), R, E, E, ACT_RELU));
         ARP_TRY(linear_fwd(c, c->ha.as<float>(), c->p("action_outputs_0/layers_2/kernel"), nullptr, nullptr, c->logits.as<float>(), R, NA, E));
-        ARP_TRY(linear_fwd(c, c->r_in.as<float>(), c->p("return_outputs_0/layers_0/kernel"), c->p("return_outputs_0/layers_0/bias"), nullptr,
-                           c->hr.as<float>(), R, E, E, ACT_RELU));
-        ARP_TRY(linear_fwd(c, c->hr.as<float>(), c->p("return_outputs_0/layers_2/kernel"), nullptr, nullptr, c->ret.as<float>(), R, 1, E));
-        hipLaunchKernelGGL(loss_kernel, dim3(1), dim3(256), 0, c->stream, c->logits.as<float>(), c->ret.as<float>(), c->bt[c->cur].action.as<int>(),
-                           c->bt[c->cur].rtg.as<float>(), R, NA, k.lambda_ret, c->metrics.as<float>(), c->dlogits.as<float>(), c->dret.as<float>());
+        if (!bc) {
+            ARP_TRY(linear_fwd(c, c->r_in.as<float>(), c->p("return_outputs_0/layers_0/kernel"), c->p("return_outputs_0/layers_0/bias"), nullptr,
+                               c->hr.as<float>(), R, E, E, ACT_RELU));
+            ARP_TRY(linear_fwd(c, c->hr.as<float>(), c->p("return_outputs_0/layers_2/kernel"), nullptr, nullptr, c->ret.as<float>(), R, 1, E));
+        }
+        hipLaunchKernelGGL(loss_kernel, dim3(1), dim3(256), 0, c->stream, c->logits.as<float>(), bc ? nullptr : c->ret.as<float>(), c->bt[c->cur].action.as<int>(),
+                           bc ? nullptr : c->bt[c->cur].rtg.as<float>(), R, NA, k.lambda_ret, c->metrics.as<float>(), c->dlogits.as<float>(), c->dret.as<float>());
         ARP_HIP_OK(hipGetLastError());
     }
     return 0;
@@ -1089,16 +1113,20 @@ template <typename T> int backward(arp_dt* c, int stage = 0) {
             PfGradsArgs a;
             a.gtab = c->gtab.as<SmallGemm>(); a.gprefix = c->gprefix.as<int>(); a.n_gemm = c->n_gemm; a.gemm_tiles = c->gemm_tiles;
             a.ctab = c->ctab.as<ColSumJob>(); a.cprefix = c->cprefix.as<int>(); a.n_cs = c->n_cs; a.cs_tiles = c->cs_tiles;
-            a.dtok = c->dtok.as<float>(); a.rtg = c->bt[c->cur].rtg.as<float>(); a.action = c->bt[c->cur].action.as<int>();
-            a.dWr = c->g("rtg_input/kernel"); a.demb = c->g("action_input/embedding"); a.R = R; a.E = E; a.NA = NA;
+            const bool bc = c->bc();
+            a.dtok = c->dtok.as<float>(); a.rtg = bc ? nullptr : c->bt[c->cur].rtg.as<float>(); a.action = c->bt[c->cur].action.as<int>();
+            a.dWr = bc ? nullptr : c->g("rtg_input/kernel"); a.demb = c->g("action_input/embedding"); a.R = R; a.E = E; a.NA = NA; a.tps = c->tps();
             a.loss_part = c->loss_part.as<float>(); a.B = c->B; a.lambda = k.lambda_ret; a.metrics = c->metrics.as<float>();
-            hipLaunchKernelGGL(pf_param_grads_kernel, dim3(c->gemm_tiles + c->cs_tiles + NA + 2), dim3(256), 0, st, a);
+            // blocks: NA embedding sums (+ the rtg projection's, ARP-DT), the loss reduction, the column sums, the weight-gradient tiles
+            hipLaunchKernelGGL(pf_param_grads_kernel, dim3(c->gemm_tiles + c->cs_tiles + NA + (bc ? 0 : 1) + 1), dim3(256), 0, st, a);
             ARP_HIP_OK(hipGetLastError());
         } else {
         hipLaunchKernelGGL(grouped_small_gemm_kernel, dim3(c->gemm_tiles), dim3(256), 0, st, c->gtab.as<SmallGemm>(), c->gprefix.as<int>(), c->n_gemm);
         hipLaunchKernelGGL(grouped_colsum_kernel, dim3(c->cs_tiles), dim3(256), 0, st, c->ctab.as<ColSumJob>(), c->cprefix.as<int>(), c->n_cs);
-        hipLaunchKernelGGL(tokens_bwd_par_kernel, dim3(NA + 1), dim3(TOKB_THREADS), 0, st, c->dtok.as<float>(), c->bt[c->cur].rtg.as<float>(), c->bt[c->cur].action.as<int>(),
-                           c->g("rtg_input/kernel"), c->g("action_input/embedding"), R, E, NA);
+        if (c->bc()) hipLaunchKernelGGL(tokens_bwd_par_kernel, dim3(NA), dim3(TOKB_THREADS), 0, st, c->dtok.as<float>(), nullptr, c->bt[c->cur].action.as<int>(),
+                                        nullptr, c->g("action_input/embedding"), R, E, NA, 2);
+        else hipLaunchKernelGGL(tokens_bwd_par_kernel, dim3(NA + 1), dim3(TOKB_THREADS), 0, st, c->dtok.as<float>(), c->bt[c->cur].rtg.as<float>(), c->bt[c->cur].action.as<int>(),
+                                c->g("rtg_input/kernel"), c->g("action_input/embedding"), R, E, NA, 3);
         ARP_HIP_OK(hipGetLastError());
         }
     } else {
@@ -1109,13 +1137,16 @@ template <typename T> int backward(arp_dt* c, int stage = 0) {
         ARP_TRY(ew_bwd(c, c->t1.as<float>(), c->ha.as<float>(), c->dha.as<float>(), (size_t)R * E, EW_RELU_BWD));
         ARP_TRY(linear_bwd(c, c->a_in.as<float>(), c->p("action_outputs_0/layers_0/kernel"), c->dha.as<float>(), c->g("action_outputs_0/layers_0/kernel"),
                            c->g("action_outputs_0/layers_0/bias"), c->da_in.as<float>(), R, E, E));
-        ARP_TRY(linear_bwd(c, c->hr.as<float>(), c->p("return_outputs_0/layers_2/kernel"), c->dret.as<float>(), c->g("return_outputs_0/layers_2/kernel"),
-                           nullptr, c->t1.as<float>(), R, 1, E));
-        ARP_TRY(ew_bwd(c, c->t1.as<float>(), c->hr.as<float>(), c->dhr.as<float>(), (size_t)R * E, EW_RELU_BWD));
-        ARP_TRY(linear_bwd(c, c->r_in.as<float>(), c->p("return_outputs_0/layers_0/kernel"), c->dhr.as<float>(), c->g("return_outputs_0/layers_0/kernel"),
-                           c->g("return_outputs_0/layers_0/bias"), c->dr_in.as<float>(), R, E, E));
+        const bool bc = c->bc();
+        if (!bc) {
+            ARP_TRY(linear_bwd(c, c->hr.as<float>(), c->p("return_outputs_0/layers_2/kernel"), c->dret.as<float>(), c->g("return_outputs_0/layers_2/kernel"),
+                               nullptr, c->t1.as<float>(), R, 1, E));
+            ARP_TRY(ew_bwd(c, c->t1.as<float>(), c->hr.as<float>(), c->dhr.as<float>(), (size_t)R * E, EW_RELU_BWD));
+            ARP_TRY(linear_bwd(c, c->r_in.as<float>(), c->p("return_outputs_0/layers_0/kernel"), c->dhr.as<float>(), c->g("return_outputs_0/layers_0/kernel"),
+                               c->g("return_outputs_0/layers_0/bias"), c->dr_in.as<float>(), R, E, E));
+        }
         hipLaunchKernelGGL(heads_scatter_kernel, dim3(cdiv((size_t)R * E, 256)), dim3(256), 0, c->stream, c->da_in.as<float>(), c->dr_in.as<float>(),
-                           c->dhf.as<float>(), R, E);
+                           c->dhf.as<float>(), R, E, c->tps());
         ARP_TRY(ln_bwd(c, c->xs[depth].as<float>(), c->p("policy/LayerNorm_0/scale"), c->dhf.as<float>(), dh, 0, c->g("policy/LayerNorm_0/scale"),
                        c->g("policy/LayerNorm_0/bias"), BL, E));
         for (int i = depth - 1; i >= 0; --i) {
@@ -1143,8 +1174,8 @@ template <typename T> int backward(arp_dt* c, int stage = 0) {
             ARP_TRY(ln_bwd(c, c->xs[i].as<float>(), c->p(p + "LayerNorm_0/scale"), c->t3.as<float>(), dh, 1, c->g(p + "LayerNorm_0/scale"),
                            c->g(p + "LayerNorm_0/bias"), BL, E));
         }
-        hipLaunchKernelGGL(tokens_bwd_kernel, dim3(cdiv(E, 256)), dim3(256), 0, c->stream, dh, c->bt[c->cur].rtg.as<float>(), c->bt[c->cur].action.as<int>(),
-                           c->dimg.as<float>(), c->g("rtg_input/kernel"), c->g("action_input/embedding"), R, E, NA);
+        hipLaunchKernelGGL(tokens_bwd_kernel, dim3(cdiv(E, 256)), dim3(256), 0, c->stream, dh, bc ? nullptr : c->bt[c->cur].rtg.as<float>(), c->bt[c->cur].action.as<int>(),
+                           c->dimg.as<float>(), bc ? nullptr : c->g("rtg_input/kernel"), c->g("action_input/embedding"), R, E, NA, c->tps());
         ARP_TRY(ew_bwd(c, c->dimg.as<float>(), c->img.as<float>(), c->dz.as<float>(), (size_t)R * E, EW_TANH_BWD));
         hipLaunchKernelGGL(colsum_kernel, dim3(cdiv(E, 64)), dim3(256), 0, c->stream, c->dz.as<float>(), R, E, c->g("image_text_input/bias"));
         ARP_HIP_OK(hipGetLastError());
@@ -1401,7 +1432,7 @@ template <typename T> int step_impl(arp_dt* c, float lr, float* aux) {
         const float l2 = s[1], pen = c->cfg.weight_decay * 0.5f * l2;
         aux[0] = m[0] * inv + pen;   // loss (incl. the L2 penalty)
         aux[1] = m[1] * inv * 100.f; // acc * 100
-        aux[2] = m[2] * inv;         // trans_loss
+        aux[2] = c->bc() ? 0.f : m[2] * inv;  // trans_loss (BC: 0, the model has no such output -- main_procgen.py:120 output.get("trans_loss", 0.0))
         aux[3] = m[3] * inv;         // return_loss
         aux[4] = pen;                // weight_penalty
         aux[5] = l2;                 // weight_l2
@@ -1426,7 +1457,9 @@ int arp_dt_create(const arp_dt_cfg* cfg, arp_dt** out) {
     if (hd != 16 && hd != 32 && hd != 64) return fail("head_dim must be 16, 32 or 64");
     const int kq = k.mode == ARP_MODE_F32 ? 32 : 64;
     if (k.enc_dim % kq || k.emb % kq) return fail("enc_dim and emb must be multiples of " + std::to_string(kq));
-    if (k.window <= 0 || 3 * k.window > 64) return fail("window must be in 1..21");
+    if (k.model != ARP_DT_MODEL_ARPDT && k.model != ARP_DT_MODEL_BC) return fail("model must be ARP_DT_MODEL_ARPDT (0) or ARP_DT_MODEL_BC (1)");
+    const int tps = k.model == ARP_DT_MODEL_BC ? 2 : 3;
+    if (k.window <= 0 || tps * k.window > 64) return fail(std::string("window must be in 1..") + (tps == 3 ? "21" : "32"));
     if (k.depth <= 0 || k.n_actions <= 0 || k.enc_tokens <= 0 || k.mlp_ratio <= 0) return fail("bad geometry");
     int ndev = 0;
     ARP_HIP_OK(hipGetDeviceCount(&ndev));
@@ -1600,7 +1633,8 @@ static int stage_slot(arp_dt* c, int si, hipStream_t st, const float* enc, const
         if (action[i] < 0 || action[i] >= c->cfg.n_actions) return fail("action id out of range");
     arp_dt::BatchSlot& b = c->bt[si];
     ARP_TRY(b.action.ensure((size_t)R * 4));
-    ARP_TRY(b.rtg.ensure((size_t)R * 4));
+    const bool with_rtg = c->cfg.model != ARP_DT_MODEL_BC;  // BC.encode reads no rtg (a non-NULL one is ignored)
+    if (with_rtg) ARP_TRY(b.rtg.ensure((size_t)R * 4));
     const size_t Mx = (size_t)R * c->cfg.enc_tokens;
     ARP_TRY(b.enc32.ensure(Mx * c->cfg.enc_dim * 4));  // with frames in: the encoder's output buffer
     if (frames) {
@@ -1613,14 +1647,15 @@ static int stage_slot(arp_dt* c, int si, hipStream_t st, const float* enc, const
         ARP_HIP_OK(hipMemcpyAsync(b.enc32.p, enc, Mx * c->cfg.enc_dim * 4, hipMemcpyHostToDevice, st));
     }
     ARP_HIP_OK(hipMemcpyAsync(b.action.p, action, (size_t)R * 4, hipMemcpyHostToDevice, st));
-    ARP_HIP_OK(hipMemcpyAsync(b.rtg.p, rtg, (size_t)R * 4, hipMemcpyHostToDevice, st));
+    if (with_rtg) ARP_HIP_OK(hipMemcpyAsync(b.rtg.p, rtg, (size_t)R * 4, hipMemcpyHostToDevice, st));
     b.B = B;
     b.images = frames != nullptr;
     return 0;
 }
 
 int arp_dt_set_batch(arp_dt* c, const float* enc, const int32_t* action, const float* rtg, int B) {
-    if (!c || !enc || !action || !rtg || B <= 0) return fail("bad argument");
+    if (!c || !enc || !action || B <= 0) return fail("bad argument");
+    if (!rtg && !c->bc()) return fail("rtg is NULL (only model BC takes no return-to-go)");
     ARP_HIP_OK(hipSetDevice(c->cfg.device));
     c->cur = 2;  // the synchronous slot
     if (c->bt[2].enc_ahead && c->enc_stream) ARP_HIP_OK(hipStreamSynchronize(c->enc_stream));  // (an encode-ahead pass still writing the buffer about to be filled)
@@ -1637,7 +1672,8 @@ int arp_dt_set_batch(arp_dt* c, const float* enc, const int32_t* action, const f
 // reads, so it may be called from another host thread while arp_dt_train_step runs.  The copy waits (on the GPU) for the last
 // step that read this slot; arp_dt_select_batch makes the compute stream wait for the copy.
 static int upload_async(arp_dt* c, int slot, const float* enc, const float* frames, const int32_t* action, const float* rtg, int B) {
-    if (!c || (!enc && !frames) || !action || !rtg || B <= 0 || slot < 0 || slot > 1) return fail("bad argument");
+    if (!c || (!enc && !frames) || !action || B <= 0 || slot < 0 || slot > 1) return fail("bad argument");
+    if (!rtg && !c->bc()) return fail("rtg is NULL (only model BC takes no return-to-go)");
     if (frames && !c->enc) return fail("no encoder attached: call arp_dt_attach_encoder first");
     ARP_HIP_OK(hipSetDevice(c->cfg.device));
     arp_dt::BatchSlot& b = c->bt[slot];
@@ -1686,6 +1722,9 @@ int arp_dt_select_batch(arp_dt* c, int slot) {
 
 int arp_dt_attach_encoder(arp_dt* c, arp_enc* enc) {
     if (!c || !enc) return fail("null argument");
+    // The reference's InstructRL encoder sees the BERT-tokenized instruction beside the frame (BC.py:286-321: 1 + 256 + 77 tokens); this encoder is
+    // M3AE's image path alone, so a BC policy behind it would be a model the reference never trains.
+    if (c->bc()) return fail("model BC takes encodings (enc_tokens per frame, the instruction's text tokens included): the image-only encoder cannot be attached");
     int tokens = 0, width = 0, res = 0, dev = 0;
     ARP_TRY(enc_geometry(enc, &tokens, &width, &res, &dev));
     if (tokens != c->cfg.enc_tokens || width != c->cfg.enc_dim) return fail("encoder geometry does not match enc_tokens / enc_dim");
@@ -1696,7 +1735,7 @@ int arp_dt_attach_encoder(arp_dt* c, arp_enc* enc) {
 
 int arp_dt_set_batch_images(arp_dt* c, const float* images, const int32_t* action, const float* rtg, int B) {
     if (!c || !images || !action || !rtg || B <= 0) return fail("bad argument");
-    if (!c->enc) return fail("no encoder attached: call arp_dt_attach_encoder first");
+    if (!c->enc) return fail("no encoder attached: call arp_dt_attach_encoder first");  // (never the case for model BC: arp_dt_attach_encoder refuses it)
     ARP_HIP_OK(hipSetDevice(c->cfg.device));
     c->cur = 2;  // the synchronous slot
     if (c->bt[2].enc_ahead && c->enc_stream) ARP_HIP_OK(hipStreamSynchronize(c->enc_stream));  // (an encode-ahead pass still reading the frames about to be replaced)
@@ -1725,6 +1764,7 @@ int arp_dt_encode_ahead(arp_dt* c, int slot) {
 int arp_dt_forward(arp_dt* c, float* action_logits, float* return_pred, float* metrics) {
     if (!c) return fail("null handle");
     if (c->B <= 0) return fail("no batch staged: call arp_dt_set_batch first");
+    if (return_pred && c->bc()) return fail("model BC has no return head: return_pred must be NULL");
     ARP_HIP_OK(hipSetDevice(c->cfg.device));
     // (replayed as a hipGraph from the third call of a geometry on: ~25 dependent launches, host-bound at batch 1)
     ARP_TRY(c->cfg.mode == ARP_MODE_BF16 ? fwd_bwd_graphed<bf16_t>(c, 3) : (c->cfg.mode == ARP_MODE_F16 ? fwd_bwd_graphed<f16_t>(c, 3) : fwd_bwd_graphed<float>(c, 3)));
@@ -1733,6 +1773,7 @@ int arp_dt_forward(arp_dt* c, float* action_logits, float* return_pred, float* m
     if (return_pred) ARP_HIP_OK(hipMemcpyAsync(return_pred, c->ret.p, (size_t)R * 4, hipMemcpyDeviceToHost, c->stream));
     if (metrics) ARP_HIP_OK(hipMemcpyAsync(metrics, c->metrics.p, 16, hipMemcpyDeviceToHost, c->stream));
     ARP_HIP_OK(hipStreamSynchronize(c->stream));
+    if (metrics && c->bc()) metrics[2] = metrics[3] = 0.f;  // BC outputs {action_pred, loss, acc} (BC.py:181): no trans_loss / return_loss
     return 0;
 }
 
@@ -1780,7 +1821,7 @@ int arp_dt_val_step(arp_dt* c, float* aux4) {
     ARP_HIP_OK(hipStreamSynchronize(c->stream));
     const float inv = 1.0f / (float)std::max(c->cfg.world, 1);
     aux4[0] = m[0] * inv;          // loss (no L2 penalty: val_fn returns the model's loss)
-    aux4[1] = m[2] * inv;          // trans_loss
+    aux4[1] = c->bc() ? 0.f : m[2] * inv;  // trans_loss (BC: 0, main_procgen.py:155)
     aux4[2] = m[3] * inv;          // return_loss
     aux4[3] = m[1] * inv * 100.f;  // acc * 100
     return 0;

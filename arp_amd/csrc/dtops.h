@@ -959,50 +959,60 @@ static __global__ __launch_bounds__(64) void attn_bwd_small_kernel(const float* 
 
 // ---- token assembly (arp_dt/ARPDT.py:159-172,278-293): per time step [image, rtg, action] -------------
 // tok[(b*T + t)*3 + 0] = img[b*T+t];  +1 = rtg[b*T+t] * Wr;  +2 = Emb[action[b*T+t]]
+// tps = 2 (model BC, arp_dt/BC.py:141-142): per time step [image, action], rtg and Wr unused
 static __global__ __launch_bounds__(256) void tokens_fwd_kernel(const float* __restrict__ img, const float* __restrict__ rtg,
                                                          const int* __restrict__ action, const float* __restrict__ Wr,
-                                                         const float* __restrict__ emb, float* __restrict__ tok, int R, int E) {
+                                                         const float* __restrict__ emb, float* __restrict__ tok, int R, int E, int tps) {
     const int i = blockIdx.x * 256 + threadIdx.x;
     if (i >= R * E) return;
     const int r = i / E, e = i - r * E;
-    tok[((size_t)r * 3 + 0) * E + e] = img[i];
-    tok[((size_t)r * 3 + 1) * E + e] = rtg[r] * Wr[e];
-    tok[((size_t)r * 3 + 2) * E + e] = emb[(size_t)action[r] * E + e];
+    tok[((size_t)r * tps + 0) * E + e] = img[i];
+    if (tps == 3) tok[((size_t)r * 3 + 1) * E + e] = rtg[r] * Wr[e];
+    tok[((size_t)r * tps + tps - 1) * E + e] = emb[(size_t)action[r] * E + e];
 }
-// backward: dimg = dtok[.,0];  dWr[e] = sum_r rtg[r]*dtok[r,1,e];  dEmb[a,e] = sum_{r: action=a} dtok[r,2,e]
+// backward: dimg = dtok[.,0];  dWr[e] = sum_r rtg[r]*dtok[r,1,e];  dEmb[a,e] = sum_{r: action=a} dtok[r,2,e]   (tps = 2: no dWr, the action token is 1)
 static __global__ __launch_bounds__(256) void tokens_bwd_kernel(const float* __restrict__ dtok, const float* __restrict__ rtg,
                                                          const int* __restrict__ action, float* __restrict__ dimg,
-                                                         float* __restrict__ dWr, float* __restrict__ demb, int R, int E, int n_actions) {
+                                                         float* __restrict__ dWr, float* __restrict__ demb, int R, int E, int n_actions, int tps) {
     const int e = blockIdx.x * 256 + threadIdx.x;
     if (e >= E) return;
     float wr = 0.f;
     for (int a = 0; a < n_actions; ++a) demb[(size_t)a * E + e] = 0.f;
     for (int r = 0; r < R; ++r) {
-        dimg[(size_t)r * E + e] = dtok[((size_t)r * 3 + 0) * E + e];
-        wr += rtg[r] * dtok[((size_t)r * 3 + 1) * E + e];
-        demb[(size_t)action[r] * E + e] += dtok[((size_t)r * 3 + 2) * E + e];
+        dimg[(size_t)r * E + e] = dtok[((size_t)r * tps + 0) * E + e];
+        if (tps == 3) wr += rtg[r] * dtok[((size_t)r * 3 + 1) * E + e];
+        demb[(size_t)action[r] * E + e] += dtok[((size_t)r * tps + tps - 1) * E + e];
     }
-    dWr[e] = wr;
+    if (tps == 3) dWr[e] = wr;
 }
 
 // gather / scatter of the head inputs (arp_dt/ARPDT.py:203-205): action head <- rtg-token rows (1::3),
-// return head <- image-token rows (0::3)
+// return head <- image-token rows (0::3).  tps = 2 (BC.py:166): action head <- image-token rows (0::2), no return head (r_in unused)
 static __global__ __launch_bounds__(256) void heads_gather_kernel(const float* __restrict__ hf, float* __restrict__ a_in, float* __restrict__ r_in,
-                                                           int R, int E) {
+                                                           int R, int E, int tps) {
     const int i = blockIdx.x * 256 + threadIdx.x;
     if (i >= R * E) return;
     const int r = i / E, e = i - r * E;
-    r_in[i] = hf[((size_t)r * 3 + 0) * E + e];
-    a_in[i] = hf[((size_t)r * 3 + 1) * E + e];
+    if (tps == 3) {
+        r_in[i] = hf[((size_t)r * 3 + 0) * E + e];
+        a_in[i] = hf[((size_t)r * 3 + 1) * E + e];
+    } else {
+        a_in[i] = hf[((size_t)r * 2 + 0) * E + e];
+    }
 }
 static __global__ __launch_bounds__(256) void heads_scatter_kernel(const float* __restrict__ da_in, const float* __restrict__ dr_in,
-                                                            float* __restrict__ dhf, int R, int E) {
+                                                            float* __restrict__ dhf, int R, int E, int tps) {
     const int i = blockIdx.x * 256 + threadIdx.x;
     if (i >= R * E) return;
     const int r = i / E, e = i - r * E;
-    dhf[((size_t)r * 3 + 0) * E + e] = dr_in[i];
-    dhf[((size_t)r * 3 + 1) * E + e] = da_in[i];
-    dhf[((size_t)r * 3 + 2) * E + e] = 0.f;
+    if (tps == 3) {
+        dhf[((size_t)r * 3 + 0) * E + e] = dr_in[i];
+        dhf[((size_t)r * 3 + 1) * E + e] = da_in[i];
+        dhf[((size_t)r * 3 + 2) * E + e] = 0.f;
+    } else {
+        dhf[((size_t)r * 2 + 0) * E + e] = da_in[i];
+        dhf[((size_t)r * 2 + 1) * E + e] = 0.f;
+    }
 }
 
 // ---- elementwise backward helpers -----------------------------------------------------------------------
@@ -1032,6 +1042,7 @@ static __global__ __launch_bounds__(256) void gelu_fwd_kernel(const float* __res
 
 // ---- losses (arp_dt/ARPDT.py:238-261,498-507), single block; also the gradients w.r.t. logits / return ---
 // metrics: [0] loss = trans + lambda*ret, [1] acc (fraction), [2] trans_loss, [3] return_loss
+// ret == nullptr (model BC, arp_dt/BC.py:175-181,230-241): the cross-entropy alone, no squared error, dret / rtg unused
 static __global__ __launch_bounds__(256) void loss_kernel(const float* __restrict__ logits, const float* __restrict__ ret,
                                                    const int* __restrict__ action, const float* __restrict__ rtg, int R, int NA,
                                                    float lambda, float* __restrict__ metrics, float* __restrict__ dlogits,
@@ -1051,9 +1062,11 @@ static __global__ __launch_bounds__(256) void loss_kernel(const float* __restric
         ce += lse - l[lab];
         hit += (am == lab) ? 1.f : 0.f;
         for (int c = 0; c < NA; ++c) dlogits[(size_t)r * NA + c] = (expf(l[c] - lse) - (c == lab ? 1.f : 0.f)) / ((float)R * NA);
-        const float d = ret[r] - rtg[r];
-        se += d * d;
-        dret[r] = lambda * 2.f * d / (float)R;
+        if (ret) {
+            const float d = ret[r] - rtg[r];
+            se += d * d;
+            dret[r] = lambda * 2.f * d / (float)R;
+        }
     }
     ce = wave_sum(ce); hit = wave_sum(hit); se = wave_sum(se);
     if ((threadIdx.x & 63) == 0) { red[0][threadIdx.x >> 6] = ce; red[1][threadIdx.x >> 6] = hit; red[2][threadIdx.x >> 6] = se; }

@@ -1,7 +1,8 @@
 // The 12-token policy transformer of path (2), forward AND the activation half of backward, as ONE kernel:
 // one 512-thread workgroup per sample keeps the sample's tokens in LDS from token assembly to the loss and
 // back down to d(image embedding).  (Reference: arp_dt/ARPDT.py:159-222,238-261 tokens, heads, losses;
-// arp_dt/layers.py:11-166 Transformer/Block/Attention/FeedForward.)
+// arp_dt/layers.py:11-166 Transformer/Block/Attention/FeedForward.)  The InstructRL baseline (arp_dt/BC.py) runs the same body with two tokens
+// per time step: policy_fused_bc_kernel, up to 8 time steps.
 //
 // Why: at B = 32 samples per GPU the transformer is 384 token rows x E = 128 -- about 1 GFLOP per step spread over
 // ~85 dependent launches of a few microseconds each (0.9 ms of a 2.1 ms step).  Per sample nothing couples the
@@ -584,8 +585,13 @@ __device__ __forceinline__ float pf_gelu_grad(float r) {  // d/du of the tanh-ap
     return 0.5f * (1.f + t) + 0.5f * r * (1.f - t * t) * c * (1.f + 3.f * a * r * r);
 }
 
-template <int E, int H, bool X3 = false>
-static __global__ __launch_bounds__(PF_THREADS) void policy_fused_kernel(PfArgs a) {  // X3: the big linears on (hi, lo) binary16 pairs (pf_lin_x3)
+// X3: the big linears on (hi, lo) binary16 pairs (pf_lin_x3).  TPS: tokens per time step -- 3 for ARP-DT ([image, rtg, action], ARPDT.py:159-172),
+// 2 for the InstructRL baseline (model BC, arp_dt/BC.py:141-142: [image, action], the action head on the image-token rows 0::2 (:166), no return head,
+// no return loss (:87-100,181)).  One body, two kernels: policy_fused_kernel (TPS 3) and policy_fused_bc_kernel (TPS 2).
+template <int E, int H, bool X3, int TPS>
+__device__ __forceinline__ void policy_fused_body(const PfArgs& a) {
+    static_assert(TPS == 2 || TPS == 3, "tokens per time step");
+    constexpr int AROW = TPS == 3 ? 1 : 0;  // the action head's token within a time step: the rtg token (ARP-DT) / the image token (BC)
     extern __shared__ __attribute__((aligned(16))) float pf_sm[];
     const int L = a.L, T = a.T, NA = a.NA, heads = a.heads;
     const int hd = E / heads;
@@ -620,16 +626,17 @@ static __global__ __launch_bounds__(PF_THREADS) void policy_fused_kernel(PfArgs 
         }
     }
     for (int e = tid; e < E; e += PF_THREADS) {
-        sVt[e] = a.lnfw[e]; sVt[E + e] = a.lnfb[e]; sVt[2 * E + e] = a.ba0[e]; sVt[3 * E + e] = a.br0[e]; sVt[4 * E + e] = a.Wr[e];
+        sVt[e] = a.lnfw[e]; sVt[E + e] = a.lnfb[e]; sVt[2 * E + e] = a.ba0[e];
+        if constexpr (TPS == 3) { sVt[3 * E + e] = a.br0[e]; sVt[4 * E + e] = a.Wr[e]; }
     }
     __syncthreads();
-    // ---- token assembly: per time step [image, rtg, action] (ARPDT.py:159-172,278-293) ----------------------
+    // ---- token assembly: per time step [image, rtg, action] (ARPDT.py:159-172,278-293); BC: [image, action] -------
     for (int idx = tid; idx < L * E; idx += PF_THREADS) {
         const int i = idx / E, e = idx - i * E;
-        const int t = i / 3, m = i - 3 * t;
+        const int t = i / TPS, m = i - TPS * t;
         float v;
         if (m == 0) v = a.img[(r0 + t) * E + e];
-        else if (m == 1) v = a.rtg[r0 + t] * sVt[4 * E + e];
+        else if (TPS == 3 && m == 1) v = a.rtg[r0 + t] * sVt[4 * E + e];
         else v = a.emb[(size_t)a.action[r0 + t] * E + e];
         sX[i * ldE + e] = v;
         a.blk[0].x[(t0 + i) * E + e] = v;
@@ -683,7 +690,8 @@ static __global__ __launch_bounds__(PF_THREADS) void policy_fused_kernel(PfArgs 
         __syncthreads();
         pf_save_rows(sX, ldE, E, xnext + t0 * E, L, tid);
     }
-    // ---- final LayerNorm, head inputs (ARPDT.py:203-205: action head <- rtg tokens 1::3, return head <- image tokens 0::3)
+    // ---- final LayerNorm, head inputs (ARPDT.py:203-205: action head <- rtg tokens 1::3, return head <- image tokens 0::3; BC.py:166: action
+    //      head <- image tokens 0::2, no return head)
     pf_ln_fwd(sX, sY, ldE, sVt, sVt + E, E, nullptr, 0, wave, lane);
     float* hA = sU;               // a_in  [16][ldE]
     float* hHa = sU + 16 * ldE;   // relu(layers_0(a_in))
@@ -694,13 +702,15 @@ static __global__ __launch_bounds__(PF_THREADS) void policy_fused_kernel(PfArgs 
         const int t = idx / E, c = idx - t * E;
         float va = 0.f, vr = 0.f;
         if (t < T) {
-            va = sY[(3 * t + 1) * ldE + c];
-            vr = sY[(3 * t) * ldE + c];
+            va = sY[(TPS * t + AROW) * ldE + c];
             a.a_in[(r0 + t) * E + c] = va;
-            a.r_in[(r0 + t) * E + c] = vr;
+            if constexpr (TPS == 3) {
+                vr = sY[(3 * t) * ldE + c];
+                a.r_in[(r0 + t) * E + c] = vr;
+            }
         }
         hA[t * ldE + c] = va;
-        hR[t * ldE + c] = vr;
+        if constexpr (TPS == 3) hR[t * ldE + c] = vr;
     }
     __syncthreads();
     pf_lin_nt<E, E, ldE, X3>(hA, a.wa0_nt, wave, lane, [&](int i, int n, f32x4_v v) {
@@ -710,6 +720,7 @@ static __global__ __launch_bounds__(PF_THREADS) void policy_fused_kernel(PfArgs 
         *reinterpret_cast<float4*>(hHa + i * ldE + n) = make_float4(v[0], v[1], v[2], v[3]);
         if (i < T) store4g(a.ha + (r0 + i) * E + n, v);
     });
+    if constexpr (TPS == 3)
     pf_lin_nt<E, E, ldE, X3>(hR, a.wr0_nt, wave, lane, [&](int i, int n, f32x4_v v) {
         const float4 bb = *reinterpret_cast<const float4*>(sVt + 3 * E + n);
         v[0] = fmaxf(v[0] + bb.x, 0.f); v[1] = fmaxf(v[1] + bb.y, 0.f); v[2] = fmaxf(v[2] + bb.z, 0.f); v[3] = fmaxf(v[3] + bb.w, 0.f);
@@ -727,6 +738,7 @@ static __global__ __launch_bounds__(PF_THREADS) void policy_fused_kernel(PfArgs 
                 if (i < T) a.logits[(r0 + i) * NA + n + r] = v[r];
             }
     });
+    if constexpr (TPS == 3)
     pf_lin_nt_small<E, ldE>(hHr, a.wr2, 1, wave, lane, [&](int i, int n, f32x4_v v) {
         if (n == 0) {
             sQ[i * ldW + 16] = v[0];
@@ -753,10 +765,13 @@ static __global__ __launch_bounds__(PF_THREADS) void policy_fused_kernel(PfArgs 
             sA[t * ldE + c] = d;
             a.dlogits[(r0 + t) * NA + c] = d;
         }
-        const float dr = l[16] - a.rtg[r0 + t];
-        const float dd = a.lambda * 2.f * dr / (float)a.R;
-        sM[t * ldE] = dd;
-        a.dret[r0 + t] = dd;
+        float dr = 0.f;  // (BC: no return prediction, no squared error)
+        if constexpr (TPS == 3) {
+            dr = l[16] - a.rtg[r0 + t];
+            const float dd = a.lambda * 2.f * dr / (float)a.R;
+            sM[t * ldE] = dd;
+            a.dret[r0 + t] = dd;
+        }
         // per-sample partials, combined over t in a fixed order by lane 0 below
         sS[t * 4 + 0] = lse - l[lab];
         sS[t * 4 + 1] = (am == lab) ? 1.f : 0.f;
@@ -783,6 +798,7 @@ static __global__ __launch_bounds__(PF_THREADS) void policy_fused_kernel(PfArgs 
         *reinterpret_cast<float4*>(hDha + i * ldE + c) = make_float4(v[0], v[1], v[2], v[3]);
         if (i < T) store4g(a.dha + (r0 + i) * E + c, v);
     });
+    if constexpr (TPS == 3)
     pf_lin_nn_small<E, ldE>(sM, a.wr2, 1, wave, lane, [&](int i, int c, f32x4_v v) {
         const float4 hh = *reinterpret_cast<const float4*>(hHr + i * ldE + c);
         v[0] = hh.x > 0.f ? v[0] : 0.f; v[1] = hh.y > 0.f ? v[1] : 0.f; v[2] = hh.z > 0.f ? v[2] : 0.f; v[3] = hh.w > 0.f ? v[3] : 0.f;
@@ -790,11 +806,12 @@ static __global__ __launch_bounds__(PF_THREADS) void policy_fused_kernel(PfArgs 
         if (i < T) store4g(a.dhr + (r0 + i) * E + c, v);
     });
     __syncthreads();
-    for (int i = tid; i < 16 * ldE; i += PF_THREADS) sA[i] = 0.f;  // sA <- d(hf): rows 3t+1 <- d a_in, rows 3t <- d r_in
+    for (int i = tid; i < 16 * ldE; i += PF_THREADS) sA[i] = 0.f;  // sA <- d(hf): rows 3t+1 <- d a_in, rows 3t <- d r_in (BC: rows 2t <- d a_in)
     __syncthreads();
     pf_lin_nn<E, E, ldE, X3>(hDha, a.wa0_nn, wave, lane, [&](int i, int c, f32x4_v v) {
-        if (i < T) *reinterpret_cast<float4*>(sA + (3 * i + 1) * ldE + c) = make_float4(v[0], v[1], v[2], v[3]);
+        if (i < T) *reinterpret_cast<float4*>(sA + (TPS * i + AROW) * ldE + c) = make_float4(v[0], v[1], v[2], v[3]);
     });
+    if constexpr (TPS == 3)
     pf_lin_nn<E, E, ldE, X3>(hDhr, a.wr0_nn, wave, lane, [&](int i, int c, f32x4_v v) {
         if (i < T) *reinterpret_cast<float4*>(sA + (3 * i) * ldE + c) = make_float4(v[0], v[1], v[2], v[3]);
     });
@@ -863,8 +880,8 @@ static __global__ __launch_bounds__(PF_THREADS) void policy_fused_kernel(PfArgs 
         const int i = idx / E, e = idx - i * E;
         const float g = sY[i * ldE + e];
         a.dtok[(t0 + i) * E + e] = g;
-        const int t = i / 3;
-        if (i - 3 * t == 0) {
+        const int t = i / TPS;
+        if (i - TPS * t == 0) {
             const float y = a.img[(r0 + t) * E + e];
             const float dzv = pin_f32(g * (1.f - y * y));  // (ONE f32 value for both stores: common.h)
             a.dz[(r0 + t) * E + e] = dzv;
@@ -880,6 +897,10 @@ static __global__ __launch_bounds__(PF_THREADS) void policy_fused_kernel(PfArgs 
         }
     }
 }
+template <int E, int H, bool X3 = false>
+static __global__ __launch_bounds__(PF_THREADS) void policy_fused_kernel(PfArgs a) { policy_fused_body<E, H, X3, 3>(a); }
+template <int E, int H, bool X3 = false>
+static __global__ __launch_bounds__(PF_THREADS) void policy_fused_bc_kernel(PfArgs a) { policy_fused_body<E, H, X3, 2>(a); }
 
 // metrics: [0] loss = trans + lambda*ret, [1] acc (fraction), [2] trans_loss, [3] return_loss  (as loss_kernel)
 static __global__ void loss_finish_kernel(const float* __restrict__ part, int B, int R, int NA, float lambda, float* __restrict__ metrics) {
@@ -959,7 +980,7 @@ static __global__ __launch_bounds__(256) void grouped_small_gemm_kernel(const Sm
     grouped_small_gemm_block(tab, tile_prefix, n, (int)blockIdx.x);
 }
 // embedding / rtg-projection gradients from d tokens: block a < NA sums the action-token rows whose action is a, block NA the
-// rtg-token rows weighted by rtg (same sums as tokens_bwd_kernel, no read-modify-write chain).  The rows are split over 1024 / E thread
+// rtg-token rows weighted by rtg (tps = 2, model BC: the action token is row 1 of each step and there is no rtg block) (same sums as tokens_bwd_kernel, no read-modify-write chain).  The rows are split over 1024 / E thread
 // groups and every row's value is LOADED unconditionally (selected afterwards), so the loads of an unrolled batch are in flight
 // together: one thread walking all R rows with a load behind each `action[r] == a` test took 31 us of the 0.9 ms step at R = 128.
 // Fixed summation order (group g: rows g, g + G, ...; then groups 0..G-1).
@@ -967,12 +988,12 @@ constexpr int TOKB_THREADS = 1024;
 // NT = 1024: the stand-alone launch; NT = 256: one block of pf_param_grads_kernel (G = 256 / E row groups, deeper unroll: 32 rows' loads in flight per lane)
 template <int NT>
 __device__ __forceinline__ void tokens_bwd_block(int a, const float* __restrict__ dtok, const float* __restrict__ rtg, const int* __restrict__ action,
-                                                 float* __restrict__ dWr, float* __restrict__ demb, int R, int E, int n_actions) {
+                                                 float* __restrict__ dWr, float* __restrict__ demb, int R, int E, int n_actions, int tps) {
     // The summation order is that of TOKB_THREADS threads whatever NT is: G = TOKB_THREADS / E row groups (group g: rows g, g + G, ...), then groups 0..G-1.
     // A smaller block gives each thread TOKB_THREADS / NT of the groups (their loads all independent), so both launch forms produce the same bits.
     __shared__ float red[TOKB_THREADS];
     const bool is_act = a < n_actions;
-    const int tok = is_act ? 2 : 1;
+    const int tok = is_act ? tps - 1 : 1;
     if (E <= NT && NT % E == 0) {
         constexpr int PER = TOKB_THREADS / NT;
         const int G = TOKB_THREADS / E, grp0 = (threadIdx.x / E) * PER, e = threadIdx.x % E;
@@ -991,7 +1012,7 @@ __device__ __forceinline__ void tokens_bwd_block(int a, const float* __restrict_
 #pragma unroll
                     for (int q = 0; q < PER; ++q) {
                         const int rc = min(r0 + u * G + grp0 + q, R - 1);
-                        xv[u][q] = dtok[((size_t)rc * 3 + tok) * E + e];
+                        xv[u][q] = dtok[((size_t)rc * tps + tok) * E + e];
                         if constexpr (decltype(ACT_)::value) wv[u][q] = __int_as_float(action[rc]);
                         else wv[u][q] = rtg[rc];
                     }
@@ -1025,7 +1046,7 @@ __device__ __forceinline__ void tokens_bwd_block(int a, const float* __restrict_
         float s = 0.f;
 #pragma unroll 8
         for (int r = 0; r < R; ++r) {
-            const float x = dtok[((size_t)r * 3 + tok) * E + e];
+            const float x = dtok[((size_t)r * tps + tok) * E + e];
             s += is_act ? (action[r] == a ? x : 0.f) : rtg[r] * x;
         }
         if (is_act) demb[(size_t)a * E + e] = s;
@@ -1033,8 +1054,8 @@ __device__ __forceinline__ void tokens_bwd_block(int a, const float* __restrict_
     }
 }
 static __global__ __launch_bounds__(TOKB_THREADS) void tokens_bwd_par_kernel(const float* __restrict__ dtok, const float* __restrict__ rtg, const int* __restrict__ action,
-                                                             float* __restrict__ dWr, float* __restrict__ demb, int R, int E, int n_actions) {
-    tokens_bwd_block<TOKB_THREADS>((int)blockIdx.x, dtok, rtg, action, dWr, demb, R, E, n_actions);
+                                                             float* __restrict__ dWr, float* __restrict__ demb, int R, int E, int n_actions, int tps) {
+    tokens_bwd_block<TOKB_THREADS>((int)blockIdx.x, dtok, rtg, action, dWr, demb, R, E, n_actions, tps);
 }
 struct ColSumJob { const float* in; float* out; int R, C; };
 static __global__ __launch_bounds__(256) void grouped_colsum_kernel(const ColSumJob* __restrict__ tab, const int* __restrict__ tile_prefix, int n) {
@@ -1049,14 +1070,15 @@ static __global__ __launch_bounds__(256) void grouped_colsum_kernel(const ColSum
 struct PfGradsArgs {
     const SmallGemm* gtab; const int* gprefix; int n_gemm, gemm_tiles;
     const ColSumJob* ctab; const int* cprefix; int n_cs, cs_tiles;
-    const float *dtok, *rtg; const int* action; float *dWr, *demb; int R, E, NA;
+    const float *dtok, *rtg; const int* action; float *dWr, *demb; int R, E, NA, tps;  // tps 2 (BC): NA token blocks (no rtg block), else NA + 1
     const float* loss_part; int B; float lambda; float* metrics;
 };
 static __global__ __launch_bounds__(256) void pf_param_grads_kernel(PfGradsArgs a) {
     // the blocks with the longest dependent chains first (they are dispatched first): embedding sums, column sums, then the MFMA tiles
     int b = (int)blockIdx.x;
-    if (b <= a.NA) { tokens_bwd_block<256>(b, a.dtok, a.rtg, a.action, a.dWr, a.demb, a.R, a.E, a.NA); return; }
-    b -= a.NA + 1;
+    const int ntok = a.NA + (a.tps == 3 ? 1 : 0);
+    if (b < ntok) { tokens_bwd_block<256>(b, a.dtok, a.rtg, a.action, a.dWr, a.demb, a.R, a.E, a.NA, a.tps); return; }
+    b -= ntok;
     if (b >= 1 && b <= a.cs_tiles) {
         b -= 1;
         const int p = grouped_job_index(a.cprefix, a.n_cs, b);

@@ -7,7 +7,9 @@ import numpy as np
 
 
 def policy_param_shapes(cfg):
+    """cfg.model "BC" (the InstructRL baseline, arp_dt/BC.py:87-100): the same tree without rtg_input and the return head."""
     E, D, H = cfg.emb, cfg.enc_dim, cfg.mlp_ratio * cfg.emb
+    bc = getattr(cfg, "model", "ARPDT") == "BC"
     s = {}
     if cfg.use_adapter:
         for i in (0, 1):
@@ -17,7 +19,8 @@ def policy_param_shapes(cfg):
     s["image_text_input/kernel"] = (cfg.enc_tokens * D, E)
     s["image_text_input/bias"] = (E,)
     s["action_input/embedding"] = (cfg.n_actions, E)
-    s["rtg_input/kernel"] = (1, E)
+    if not bc:
+        s["rtg_input/kernel"] = (1, E)
     for i in range(cfg.depth):
         p = f"policy/Block_{i}/"
         for ln in ("LayerNorm_0", "LayerNorm_1"):
@@ -31,7 +34,7 @@ def policy_param_shapes(cfg):
         s[p + "FeedForward_0/fc2/kernel"] = (H, E)
     s["policy/LayerNorm_0/scale"] = (E,)
     s["policy/LayerNorm_0/bias"] = (E,)
-    for head, n in (("action_outputs_0", cfg.n_actions), ("return_outputs_0", 1)):
+    for head, n in (("action_outputs_0", cfg.n_actions),) + (() if bc else (("return_outputs_0", 1),)):
         s[head + "/layers_0/kernel"] = (E, E)
         s[head + "/layers_0/bias"] = (E,)
         s[head + "/layers_2/kernel"] = (E, n)

@@ -15,7 +15,7 @@ stands in).  ``state`` is a :class:`TrainState` wrapping the device-resident par
 step counter; like the reference's donated state it is consumed by the call and the returned one must be
 used.  ``batch`` keeps the reference's keys: ``batch["image"]`` holds, per image key, the frozen encoder
 output ``[B, T, tokens, dim]`` (the boundary of this round: BASELINE.json configs[3] feeds pre-computed
-encodings), ``batch["action"]`` int ``[B, T]``, ``batch["rtg"]`` per key ``[B, T, 1]``.
+encodings), ``batch["action"]`` int ``[B, T]``, ``batch["rtg"]`` per key ``[B, T, 1]`` (none for ``PolicyConfig(model="BC")``).
 All compute is in libarp_hip.so; there is no CPU fallback.
 """
 import ctypes as C
@@ -51,6 +51,20 @@ class PolicyConfig:
     b1: float = 0.9
     b2: float = 0.999
     eps: float = 1e-8
+    # main_procgen.py:406-427: "ARPDT" (use_vl=True), or "BC" -- the InstructRL baseline (use_vl=False, vl_type="BC": arp_dt/BC.py), the same transformer
+    # on two tokens per time step [image, action], no return-to-go input, no return head, the cross-entropy alone
+    model: str = "ARPDT"
+
+    def __post_init__(self):
+        if self.model not in _ffi.DT_MODELS:
+            raise ValueError(f"PolicyConfig.model must be one of {sorted(_ffi.DT_MODELS)}, not {self.model!r}")
+
+
+def _dt_cfg(cfg, mode, device):
+    """The C configuration (arp_dt_cfg) of a policy configuration."""
+    return _ffi.DtCfg(cfg.emb, cfg.depth, cfg.heads, cfg.mlp_ratio, cfg.n_actions, cfg.window, cfg.enc_tokens, cfg.enc_dim, int(cfg.use_adapter), mode,
+                      device, 1, 0, cfg.lambda_ret, cfg.weight_decay, cfg.clip_norm, cfg.b1, cfg.b2, cfg.eps, int(getattr(cfg, "alibi_bias", False)),
+                      _ffi.DT_MODELS[getattr(cfg, "model", "ARPDT")])
 
 
 class PolicyTrainer:
@@ -63,9 +77,8 @@ class PolicyTrainer:
         (arp_dt_set_adapter_corrections) -- what the encoder-inside step (row N1, encoder mode "f16c") pairs with."""
         _ffi.require_gpu()
         self.cfg = cfg
-        c = _ffi.DtCfg(cfg.emb, cfg.depth, cfg.heads, cfg.mlp_ratio, cfg.n_actions, cfg.window, cfg.enc_tokens, cfg.enc_dim,
-                       int(cfg.use_adapter), {"bf16": MODE_BF16, "f16": MODE_F16, "f32": MODE_F32}[mode], device, 1, 0, cfg.lambda_ret,
-                       cfg.weight_decay, cfg.clip_norm, cfg.b1, cfg.b2, cfg.eps, int(getattr(cfg, "alibi_bias", False)))
+        c = _dt_cfg(cfg, {"bf16": MODE_BF16, "f16": MODE_F16, "f32": MODE_F32}[mode], device)
+        self.bc = getattr(cfg, "model", "ARPDT") == "BC"
         h = C.c_void_p()
         check(lib.arp_dt_create(C.byref(c), C.byref(h)))
         self._h = h
@@ -131,28 +144,38 @@ class PolicyTrainer:
         check(lib.arp_dt_set_step(self._h, int(v)))
 
     # -- compute --------------------------------------------------------------------------------------
-    def set_batch(self, enc, action, rtg):
+    def _rtg(self, rtg, B, T):
+        """(array, pointer) of the return-to-go: None / NULL for model BC, which reads none (BC.encode); for ARP-DT a missing rtg reaches the
+        library as NULL and is refused there."""
+        if self.bc or rtg is None:
+            return None, None
+        rtg = np.require(np.asarray(rtg, dtype=np.float32), requirements="C")
+        if rtg.size != B * T:
+            raise ValueError(f"batch shapes: rtg {rtg.shape}, expected {B * T} values")
+        return rtg, _ffi.as_ptr(rtg, C.c_float)
+
+    def set_batch(self, enc, action, rtg=None):
         enc = np.require(np.asarray(enc, dtype=np.float32), requirements="C")
         action = np.require(np.asarray(action, dtype=np.int32), requirements="C")
-        rtg = np.require(np.asarray(rtg, dtype=np.float32), requirements="C")
         B, T = action.shape
-        if enc.shape != (B, T, self.cfg.enc_tokens, self.cfg.enc_dim) or rtg.size != B * T or T != self.cfg.window:
-            raise ValueError(f"batch shapes: enc {enc.shape}, action {action.shape}, rtg {rtg.shape}")
-        check(lib.arp_dt_set_batch(self._h, _ffi.as_ptr(enc, C.c_float), _ffi.as_ptr(action, C.c_int32), _ffi.as_ptr(rtg, C.c_float), B))
+        if enc.shape != (B, T, self.cfg.enc_tokens, self.cfg.enc_dim) or T != self.cfg.window:
+            raise ValueError(f"batch shapes: enc {enc.shape}, action {action.shape}")
+        rtg, rp = self._rtg(rtg, B, T)
+        check(lib.arp_dt_set_batch(self._h, _ffi.as_ptr(enc, C.c_float), _ffi.as_ptr(action, C.c_int32), rp, B))
         self._B = B
 
     # -- two device-resident batch slots: the reference's prefetch_to_device(..., 2) (main_procgen.py:703) ----------------------
-    def upload_async(self, slot, enc, action, rtg, images=False):
+    def upload_async(self, slot, enc, action, rtg=None, images=False):
         """Enqueue the host -> device copy of a batch into slot 0 / 1 on the handle's copy stream.  Safe to call from another
         thread while :meth:`train_step` runs on the other slot.  The arrays must stay alive until :meth:`select` (kept here)."""
         enc = np.require(np.asarray(enc, dtype=np.float32), requirements="C")
         action = np.require(np.asarray(action, dtype=np.int32), requirements="C")
-        rtg = np.require(np.asarray(rtg, dtype=np.float32), requirements="C")
         B, T = action.shape
-        if rtg.size != B * T or T != self.cfg.window or (not images and enc.shape != (B, T, self.cfg.enc_tokens, self.cfg.enc_dim)):
-            raise ValueError(f"batch shapes: enc {enc.shape}, action {action.shape}, rtg {rtg.shape}")
+        if T != self.cfg.window or (not images and enc.shape != (B, T, self.cfg.enc_tokens, self.cfg.enc_dim)):
+            raise ValueError(f"batch shapes: enc {enc.shape}, action {action.shape}")
+        rtg, rp = self._rtg(rtg, B, T)
         fn = lib.arp_dt_upload_batch_images_async if images else lib.arp_dt_upload_batch_async
-        check(fn(self._h, int(slot), _ffi.as_ptr(enc, C.c_float), _ffi.as_ptr(action, C.c_int32), _ffi.as_ptr(rtg, C.c_float), B))
+        check(fn(self._h, int(slot), _ffi.as_ptr(enc, C.c_float), _ffi.as_ptr(action, C.c_int32), rp, B))
         self._inflight = getattr(self, "_inflight", {})
         self._inflight[int(slot)] = (enc, action, rtg, B)
 
@@ -174,7 +197,8 @@ class PolicyTrainer:
 
     def attach_encoder(self, encoder):
         """Put the frozen M3AE encoder (arp_amd.m3ae.M3AEEncoder) inside the step: the boundary then is the
-        reference's own -- batch["image"] holds frames, not encodings (ARPDT.py:413-462)."""
+        reference's own -- batch["image"] holds frames, not encodings (ARPDT.py:413-462).  Refused for model BC: the reference's InstructRL
+        encoder reads the instruction's text tokens beside the frame (BC.py:286-321), this one is image-only."""
         check(lib.arp_dt_attach_encoder(self._h, encoder._h))
         self._encoder = encoder
 
@@ -189,9 +213,13 @@ class PolicyTrainer:
         self._B = B
 
     def forward(self):
-        """ARPDT.__call__ (ARPDT.py:152-236) on the staged batch."""
+        """ARPDT.__call__ (ARPDT.py:152-236) on the staged batch; model BC: BC.__call__ (BC.py:135-181), {action_pred, loss, acc}."""
         B, T, NA = self._B, self.cfg.window, self.cfg.n_actions
         logits = np.empty((B, T, NA), np.float32)
+        if self.bc:
+            m = np.empty(4, np.float32)
+            check(lib.arp_dt_forward(self._h, _ffi.as_ptr(logits, C.c_float), None, _ffi.as_ptr(m, C.c_float)))
+            return {"action_pred": logits, "loss": float(m[0]), "acc": float(m[1])}
         ret = np.empty((B, T, 1), np.float32)
         m = np.empty(4, np.float32)
         check(lib.arp_dt_forward(self._h, _ffi.as_ptr(logits, C.c_float), _ffi.as_ptr(ret, C.c_float), _ffi.as_ptr(m, C.c_float)))
@@ -208,13 +236,15 @@ class PolicyTrainer:
         else:
             self.set_batch(enc, action, rtg)
 
-    def greedy_action(self, enc, action, rtg):
+    def greedy_action(self, enc, action, rtg=None):
         """ARPDT.greedy_action (ARPDT.py:488-492): argmax of the LAST time step's action logits."""
         self._set_batch_any(enc, action, rtg)
         return self.forward()["action_pred"][:, -1, :].argmax(-1)
 
     def greedy_return(self, enc, action, rtg):
-        """ARPDT.greedy_return (ARPDT.py:494-495): symexp(return_pred) (utils.py symexp = sign(x)(exp|x| - 1))."""
+        """ARPDT.greedy_return (ARPDT.py:494-495): symexp(return_pred) (utils.py symexp = sign(x)(exp|x| - 1)).  BC has none."""
+        if self.bc:
+            raise ValueError("model BC has no return head: greedy_return exists for ARP-DT only (BC.py defines greedy_action alone)")
         self._set_batch_any(enc, action, rtg)
         r = self.forward()["return_pred"]
         return np.sign(r) * (np.exp(np.abs(r)) - 1.0)
@@ -310,7 +340,9 @@ def _batch_arrays(batch, use_symlog=False):
     (arp_dt/ARPDT.py:251-258,281-293).  Both uses see the same array, so the transform is applied here, once, on the host."""
     image = batch["image"]
     enc = next(iter(image.values())) if isinstance(image, dict) else image
-    rtg = batch["rtg"]
+    rtg = batch.get("rtg")
+    if rtg is None:  # (a BC batch: BC.encode reads no return-to-go)
+        return np.asarray(enc), np.asarray(batch["action"]), None
     views = [np.asarray(v, np.float32) for v in rtg.values()] if isinstance(rtg, dict) else [np.asarray(rtg, np.float32)]
     if use_symlog:
         views = [symlog(v) for v in views]
@@ -406,8 +438,7 @@ def bucket_plan(cfg):
     """Flat-gradient ranges ``[(lo, hi)] * 4`` of the data-parallel step's two all-reduce buckets (bucket 1 = ranges 0, 1:
     image_text_input's kernel + everything the transformer owns, launched while the adapter's backward still runs; bucket 2 =
     ranges 2, 3) and the flat parameter count.  Needs no GPU."""
-    c = _ffi.DtCfg(cfg.emb, cfg.depth, cfg.heads, cfg.mlp_ratio, cfg.n_actions, cfg.window, cfg.enc_tokens, cfg.enc_dim, int(cfg.use_adapter),
-                   MODE_F16, 0, 1, 0, cfg.lambda_ret, cfg.weight_decay, cfg.clip_norm, cfg.b1, cfg.b2, cfg.eps)
+    c = _dt_cfg(cfg, MODE_F16, 0)
     r = (C.c_int64 * 8)()
     tot = C.c_int64()
     check(lib.arp_dt_bucket_plan(C.byref(c), r, C.byref(tot)))

@@ -169,7 +169,7 @@ typedef struct arp_dt_cfg {
     int32_t heads;       /* 8   */
     int32_t mlp_ratio;   /* 4   */
     int32_t n_actions;   /* 15  */
-    int32_t window;      /* 4 time steps -> 12 tokens */
+    int32_t window;      /* 4 time steps -> 12 tokens (8 for model BC) */
     int32_t enc_tokens;  /* 257 (M3AE ViT-B/16 at 256x256) */
     int32_t enc_dim;     /* 768 */
     int32_t use_adapter; /* 1   */
@@ -183,7 +183,13 @@ typedef struct arp_dt_cfg {
     float b1, b2, eps;   /* adam */
     int32_t alibi_bias;  /* config.alibi_bias (arp_dt/layers.py:74-78; off in the shipped configuration): slope_h * key_index added to the policy
                             transformer's attention scores, slopes as _get_attention_slopes (layers.py:97-110) */
+    int32_t model;       /* ARP_DT_MODEL_ARPDT (0, the default) | ARP_DT_MODEL_BC (1): the InstructRL baseline, arp_dt/BC.py (main_procgen.py:406-427
+                            with use_vl=False, vl_type="BC") -- two tokens per time step [image, action], the action head on the image-token rows
+                            0::2, no rtg_input, no return head, no return loss.  A BC handle takes rtg == NULL (and ignores a non-NULL one), wants
+                            return_pred == NULL in arp_dt_forward, reports trans_loss = return_loss = 0 (the model outputs neither:
+                            main_procgen.py:118-124,153-157 read them with output.get(..., 0.0)) and refuses arp_dt_attach_encoder. */
 } arp_dt_cfg;
+enum { ARP_DT_MODEL_ARPDT = 0, ARP_DT_MODEL_BC = 1 };
 
 int arp_dt_create(const arp_dt_cfg* cfg, arp_dt** out);
 int arp_dt_destroy(arp_dt* h);
@@ -194,9 +200,9 @@ int arp_dt_set_tensor(arp_dt* h, const char* name, int which, const float* data)
 int arp_dt_get_tensor(arp_dt* h, const char* name, int which, float* out); /* which = 1 after a data-parallel step: the rank MEAN */
 int arp_dt_set_step(arp_dt* h, int64_t step);
 int arp_dt_get_step(arp_dt* h, int64_t* step);
-/* Stages one per-device batch in HBM: enc f32 [B,T,enc_tokens,enc_dim], action int32 [B,T], rtg f32 [B,T,1]. */
+/* Stages one per-device batch in HBM: enc f32 [B,T,enc_tokens,enc_dim], action int32 [B,T], rtg f32 [B,T,1] (NULL allowed for model BC). */
 int arp_dt_set_batch(arp_dt* h, const float* enc, const int32_t* action, const float* rtg, int B);
-/* ARPDT.__call__ on the staged batch: logits [B,T,n_actions], return_pred [B,T,1],
+/* ARPDT.__call__ on the staged batch: logits [B,T,n_actions], return_pred [B,T,1] (must be NULL for model BC, which has no return head),
  * metrics[4] = loss, acc (fraction), trans_loss, return_loss (any pointer may be NULL). */
 int arp_dt_forward(arp_dt* h, float* action_logits, float* return_pred, float* metrics);
 /* forward + backward + L2 term; gradients readable with arp_dt_get_tensor(.., 1, ..) (parity tests) */
