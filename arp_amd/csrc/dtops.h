@@ -192,7 +192,7 @@ struct iti_nomix_t {};
 // y16.  Saves the mix's own pass: it read a + x and wrote y16 + a 101 MB f32 copy that this kernel then read back (303 + 202 MB -> 303 MB at B = 32).
 // X16 (with the mix only): x comes from its operand-type copy x16 (what fc1 and the backward read) instead of the f32 encodings -- 50 MB less per step at B = 32.
 // The mix's value is rounded to the operand type for the backward anyway and its skip term weighs (1 - res) (0.018 at the initial residual_weight = 4), so
-// x's own rounding is at most as large as the adapter output's, which has always been there (arp_dt.hip ARP_DT_MIX_X16).
+// x's own rounding is at most as large as the adapter output's, which has always been there (16-seed logits 8.73e-4 against 8.74e-4).
 // ADX (round 6, with a binary16 Amix): adx holds, per adapter output value, the e2m1 code of its binary16 ROUNDING ERROR times 2^F16C_DX_SHIFT (two per byte, the layout
 // fc2's epilogue writes as GemmArgs::dx4_out) -- the mix is formed on a_hi + 2^-13 fp4: the adapter output to ~2^-14 instead of 2^-12 for 12.6 MB more than the binary16
 // hand-off, where the f32 hand-off costs 50 MB more here and the f32 read-modify epilogue in fc2 (arp_dt.hip, ARP_DT_ADAPTER_PLAN "d").
@@ -454,7 +454,7 @@ __global__ __launch_bounds__(256) void transpose_mask_kernel(const TI* __restric
 template <typename T, typename TA = T>  // TA = float: the adapter output before its rounding to the operand type (arp_dt.hip `adapter_c`)
 static __global__ __launch_bounds__(256) void adapter_mix_kernel(const TA* __restrict__ a, const float* __restrict__ x, const float* __restrict__ rw,
                                                           T* __restrict__ y, size_t n, float* __restrict__ y32 = nullptr) {
-    // y32 (optional): the un-rounded mix, for the f32 image_text_input of the precise mode (arp_dt.hip, ARP_DT_ITI_F32)
+    // y32 (optional): the un-rounded mix in f32
     const float res = 1.0f / (1.0f + expf(-rw[0]));
     const size_t i = ((size_t)blockIdx.x * 256 + threadIdx.x) * 4;
     if (i + 3 < n) {

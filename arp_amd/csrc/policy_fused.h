@@ -9,8 +9,8 @@
 // samples except the parameter gradients, so:
 //   * this kernel does everything per-sample and SAVES, for every linear layer, its input X and its output
 //     gradient dY (and per-row LayerNorm scale/bias contributions);
-//   * the parameter gradients dW = dY^T X, db = colsum(dY) are then produced for all layers at once by two
-//     grouped launches (grouped_small_gemm_kernel / grouped_colsum_kernel): fixed-order, no atomics.
+//   * the parameter gradients dW = dY^T X, db = colsum(dY) are then produced for all layers at once by one
+//     grouped launch (pf_param_grads_kernel): fixed-order, no atomics.
 //
 // Matmuls run on v_mfma_f32_16x16x4_f32 (true fp32) with the 16-row token block as one MFMA operand and the weight
 // rows streamed from L2 as the other, in both the NT (forward, W[out][in] rows along the contraction) and NN
@@ -964,7 +964,6 @@ __device__ __forceinline__ int grouped_job_index(const int* __restrict__ tile_pr
     const int bound = lane + 1 < n ? tile_prefix[lane + 1] : 0x7fffffff;
     return __builtin_amdgcn_readfirstlane(__popcll(__ballot(bid >= bound)));
 }
-__device__ __forceinline__ int grouped_job_index(const int* __restrict__ tile_prefix, int n) { return grouped_job_index(tile_prefix, n, (int)blockIdx.x); }
 
 __device__ __forceinline__ void grouped_small_gemm_block(const SmallGemm* __restrict__ tab, const int* __restrict__ tile_prefix, int n, int bid) {
     const int p = grouped_job_index(tile_prefix, n, bid);
@@ -976,6 +975,8 @@ __device__ __forceinline__ void grouped_small_gemm_block(const SmallGemm* __rest
     else
         small_gemm_tile(g, local % nbx, local / nbx);
 }
+// No launch of the step uses this kernel any more (pf_param_grads_kernel runs its blocks).  It stays defined because hipcc schedules the shared
+// grouped_small_gemm_block differently inside pf_param_grads_kernel without it, and that kernel is to keep its instructions in this change.
 static __global__ __launch_bounds__(256) void grouped_small_gemm_kernel(const SmallGemm* __restrict__ tab, const int* __restrict__ tile_prefix, int n) {
     grouped_small_gemm_block(tab, tile_prefix, n, (int)blockIdx.x);
 }
@@ -985,7 +986,8 @@ static __global__ __launch_bounds__(256) void grouped_small_gemm_kernel(const Sm
 // together: one thread walking all R rows with a load behind each `action[r] == a` test took 31 us of the 0.9 ms step at R = 128.
 // Fixed summation order (group g: rows g, g + G, ...; then groups 0..G-1).
 constexpr int TOKB_THREADS = 1024;
-// NT = 1024: the stand-alone launch; NT = 256: one block of pf_param_grads_kernel (G = 256 / E row groups, deeper unroll: 32 rows' loads in flight per lane)
+// NT = 256: one block of pf_param_grads_kernel (G = 256 / E row groups, deeper unroll: 32 rows' loads in flight per lane), in the summation order of the
+// 1024-thread launch it replaced
 template <int NT>
 __device__ __forceinline__ void tokens_bwd_block(int a, const float* __restrict__ dtok, const float* __restrict__ rtg, const int* __restrict__ action,
                                                  float* __restrict__ dWr, float* __restrict__ demb, int R, int E, int n_actions, int tps) {
@@ -1053,17 +1055,7 @@ __device__ __forceinline__ void tokens_bwd_block(int a, const float* __restrict_
         else dWr[e] = s;
     }
 }
-static __global__ __launch_bounds__(TOKB_THREADS) void tokens_bwd_par_kernel(const float* __restrict__ dtok, const float* __restrict__ rtg, const int* __restrict__ action,
-                                                             float* __restrict__ dWr, float* __restrict__ demb, int R, int E, int n_actions, int tps) {
-    tokens_bwd_block<TOKB_THREADS>((int)blockIdx.x, dtok, rtg, action, dWr, demb, R, E, n_actions, tps);
-}
 struct ColSumJob { const float* in; float* out; int R, C; };
-static __global__ __launch_bounds__(256) void grouped_colsum_kernel(const ColSumJob* __restrict__ tab, const int* __restrict__ tile_prefix, int n) {
-    const int p = grouped_job_index(tile_prefix, n);
-    const ColSumJob j = tab[p];
-    colsum_tile(j.in, j.R, j.C, j.out, blockIdx.x - tile_prefix[p]);
-}
-
 // Everything that turns the fused kernel's saved activation gradients into parameter gradients and metrics, in ONE launch: the grouped weight-gradient
 // tiles, the grouped column sums, the embedding / rtg-projection sums and the loss reduction were four dependent launches (16 + 6 + 8 + 4.5 us and three
 // boundaries on the step's critical path); none of them reads another's output, so their blocks share a grid and the launch lasts as long as its longest part.

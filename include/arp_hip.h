@@ -238,8 +238,10 @@ int arp_dt_comm_unique_id(void* id128);
 int arp_dt_comm_init(arp_dt* h, const void* id128, int world, int rank);
 int arp_dt_broadcast_state(arp_dt* h);
 /* ARP_MODE_F16 only: the adapter's two FORWARD products (models/adapter/layers.py:19-30) with their binary16 operand roundings corrected on the scaled fp4 MFMA
- * (ARP_MODE_F16C's product) and the adapter output handed to the residual mix in f32: takes the policy's own share out of the encoder-inside logit error
- * (row N1) for ~0.1 ms per step.  Off by default (ARP_DT_ADAPTER_C=1 turns it on at create); the backward is unchanged. */
+ * (ARP_MODE_F16C's product) and the adapter output handed to the residual mix inside image_text_input's operand load (binary16 + the e2m1 code of its
+ * rounding error; ARP_DT_ADAPTER_PLAN): takes the policy's own share out of the encoder-inside logit error (row N1) for ~0.1 ms per step.  On by default in
+ * f16 where enc_dim is a multiple of 256 and >= 512 (ARP_DT_ADAPTER_C=0 turns it off at create); the backward is unchanged.  May be called at any time:
+ * the next calls run eagerly and capture the step's chain again. */
 int arp_dt_set_adapter_corrections(arp_dt* h, int on);
 /* test hook: the bytes of a named intermediate device buffer of the last forward ("Xc", "H1c", "W1c", "W2c", "wc_scal", "A32", "A", "Adx", "Y", "img", "H1", "Xb");
    copies min(bytes, size), returns the buffer's size or -1 */

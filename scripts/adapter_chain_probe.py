@@ -18,7 +18,6 @@ import numpy as np
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 os.environ.setdefault("ARP_DT_ADAPTER_PLAN", "22e")
-os.environ.setdefault("ARP_DT_MIX_X16", "0")
 from arp_amd import _ffi, synth_policy as S  # noqa: E402
 from arp_amd.train import PolicyConfig, PolicyTrainer  # noqa: E402
 

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Where does the f16 policy's logit / return error come from once the adapter's operand roundings are corrected?  CPU emulation of the adapter
 (scripts/adapter_plan_emulate.py) says full corrections leave 1-2e-4; the GPU reads 3.9e-4 (logits) / 6.6e-4 (return) over 16 seeds.  Bisect on the GPU:
-the same seeds with the fused transformer on the f32 MFMA (ARP_PF_X3=0), image_text_input on the f32-MFMA GEMM (ARP_DT_ITI_X3=0), both.  Needs a GPU.
+the same seeds with the fused transformer on the f32 MFMA (ARP_PF_X3=0) and as one kernel per op (ARP_DT_FUSED=0).  Needs a GPU.
 
     python scripts/policy_floor_probe.py [n_seeds]
 """
@@ -27,10 +27,9 @@ for seed in range(n):
     cases.append((P, enc, act, rtg, ref["action_pred"].numpy(), ref["return_pred"].numpy()))
     print(f"# oracle seed {seed}: |return_pred| max {np.abs(cases[-1][5]).max():.3f}, |logits| max {np.abs(cases[-1][4]).max():.3f}", flush=True)
 CONFIGS = [("f16 default", "f16", False, {}), ("f16 + corrections", "f16", True, {}), ("f16 + corrections, transformer on f32 MFMA", "f16", True, {"ARP_PF_X3": "0"}),
-           ("f16 + corrections, iti on f32 MFMA", "f16", True, {"ARP_DT_ITI_X3": "0"}), ("f16 + corrections, both", "f16", True, {"ARP_PF_X3": "0", "ARP_DT_ITI_X3": "0"}),
            ("f16 + corrections, per-op transformer", "f16", True, {"ARP_DT_FUSED": "0"}), ("f32", "f32", False, {})]
 for name, mode, corr, env in CONFIGS:
-    for k in ("ARP_PF_X3", "ARP_DT_ITI_X3", "ARP_DT_FUSED"):
+    for k in ("ARP_PF_X3", "ARP_DT_FUSED"):
         os.environ.pop(k, None)
     os.environ.update(env)
     tr = PolicyTrainer(cfg, mode=mode, adapter_corrections=corr)
