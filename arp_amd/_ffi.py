@@ -22,6 +22,7 @@ if os.environ.get("ARP_LIB"):
 
 MODE_F32, MODE_BF16, MODE_F16, MODE_F16X3, MODE_F16C = 0, 1, 2, 3, 4
 ACT_NONE, ACT_QGELU, ACT_RELU, ACT_TANH, ACT_GELU_TANH = 0, 1, 2, 3, 4
+ATTN_OUT_PLAIN, ATTN_OUT_E4M3, ATTN_OUT_F16C, ATTN_OUT_SPLIT3 = 0, 1, 2, 3  # arp_op_attention_forms
 
 
 class ArpError(RuntimeError):
@@ -210,6 +211,8 @@ SIGNATURES = {
     "arp_op_adapter_dy": (_i, [_i, _fp, _fp, _fp, _fp, _f, _fp, _fp, _fp, _i, _i, _i, _i]),
     "arp_op_layernorm": (_i, [_fp, _fp, _fp, _fp, _i, _i, _f]),
     "arp_op_attention": (_i, [_i, _i, _fp, _fp, _i, _i, _i, _i, _i]),
+    "arp_op_attention_forms": (_i, [_i, _i, _fp, _vp, C.c_size_t, _i, _i, _i, _i, _i, _i, _i, _f, _i]),
+    "arp_op_qkv_attention": (_i, [_i, _fp, _fp, _fp, _vp, C.c_size_t, _i, _i, _i, _i, _i, _i]),
 }
 
 for _name, (_res, _args) in SIGNATURES.items():

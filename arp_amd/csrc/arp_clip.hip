@@ -237,12 +237,7 @@ static int load_tower(arp_clip* c, const std::string& prefix, int d, int layers,
             const HostTensor *w, *b;
             ARP_TRY(get_staged(c, p + "attn.in_proj_weight", {3 * d, d}, &w)); ARP_TRY(get_staged(c, p + "attn.in_proj_bias", {3 * d}, &b));
             std::vector<float> wp((size_t)3 * d * d), bp((size_t)3 * d);
-            for (int hh = 0; hh < heads; ++hh)
-                for (int j = 0; j < 192; ++j) {
-                    const int src = (j >> 6) * d + hh * 64 + (j & 63);
-                    memcpy(&wp[(size_t)(hh * 192 + j) * d], &w->data[(size_t)src * d], (size_t)d * 4);
-                    bp[hh * 192 + j] = b->data[src];
-                }
+            qkv_head_major(w->data.data(), b->data.data(), d, heads, wp.data(), bp.data());  // (hm: d = heads * 64)
             ARP_TRY(upload_mat(c, wp.data(), 3 * d, d, false, &L.w_in_hm, wmode)); ARP_TRY(upload_f32(c, bp, &L.b_in_hm));
         }
         ARP_TRY(get_staged(c, p + "attn.out_proj.weight", {d, d}, &t)); ARP_TRY(upload_mat(c, t->data.data(), d, d, false, &L.w_out, wmode));
@@ -1610,6 +1605,95 @@ int arp_op_attention(int mode, int impl, const float* qkv, float* out, int B, in
     if (mode == ARP_MODE_F16) return op_attn<f16_t>(impl, qkv, out, B, N, D, heads, causal);
     return mode == ARP_MODE_BF16 ? op_attn<bf16_t>(impl, qkv, out, B, N, D, heads, causal)
                                  : op_attn<float>(impl, qkv, out, B, N, D, heads, causal);
+}
+
+}  // extern "C"
+
+// ---- every output form of launch_attention, and the fused QKV + attention kernel, on a byte buffer the caller fills (include/arp_hip.h) ---------------------
+// `out` goes up before the launch and comes back after it whatever the launcher returned: the caller sees the bytes the kernel left alone.
+template <typename T>
+static int op_attn_forms(int impl, const float* qkv, uint8_t* out, size_t out_bytes, int B, int N, int D, int heads, int causal, int nq, int form,
+                         float out_scale, int outc) {
+    const size_t rows = (size_t)B * N, ld = (size_t)3 * D;
+    size_t row_bytes = 0;
+    if (form == ARP_ATTN_OUT_PLAIN) row_bytes = (size_t)D * sizeof(T);
+    else if (form == ARP_ATTN_OUT_E4M3 && sizeof(T) == 2 && out_scale != 0.f) row_bytes = (size_t)D;
+    else if (form == ARP_ATTN_OUT_F16C && std::is_same_v<T, f16_t> && (outc & 3) != 0 && (outc & 3) != 3 && !(outc & ~7)) row_bytes = (size_t)3 * D;
+    else if (form == ARP_ATTN_OUT_SPLIT3 && sizeof(T) == 4) row_bytes = (size_t)6 * D;
+    else return fail("attention_forms: this output form does not exist in this mode (e4m3: 16-bit modes and a scale; [hi | x4 | dx4]: f16 and outc 1, 2, 5 or 6; (hi, lo, hi): f32)");
+    if (out_bytes < rows * row_bytes) return fail("attention_forms: output buffer shorter than B * N rows");
+    DevBuf dq, dout;
+    auto body = [&]() -> int {
+        const float* src = qkv;
+        std::vector<float> permuted;
+        if (form == ARP_ATTN_OUT_F16C && (outc & 3) == 2) {
+            if (attn_vperm_applies(N, D / heads)) {  // what the encoder's weight loader does to in_proj's V columns (arp_enc.hip)
+                permuted.resize(rows * ld);
+                for (size_t r = 0; r < rows; ++r)
+                    for (int o = 0; o < 3 * D; ++o) permuted[r * ld + o] = qkv[r * ld + attn_vperm_col(o, D)];
+                src = permuted.data();
+            } else {
+                outc = (outc & 4) | 1;
+            }
+        }
+        ARP_TRY(to_dev<T>(src, rows * ld, dq));
+        ARP_TRY(dout.ensure(std::max<size_t>(out_bytes, 16)));
+        ARP_HIP_OK(hipMemcpy(dout.p, out, out_bytes, hipMemcpyHostToDevice));
+        const int rc = launch_attention<T>(nullptr, impl, dq.as<T>(), dout.as<T>(), B, N, D, heads, causal, nq, form == ARP_ATTN_OUT_E4M3 ? out_scale : 0.f,
+                                           form == ARP_ATTN_OUT_SPLIT3 ? dout.as<f16_t>() : nullptr, form == ARP_ATTN_OUT_F16C ? outc : 0);
+        ARP_HIP_OK(hipDeviceSynchronize());
+        ARP_HIP_OK(hipMemcpy(out, dout.p, out_bytes, hipMemcpyDeviceToHost));
+        return rc;
+    };
+    const int rc = body();
+    dq.release(); dout.release();
+    return rc;
+}
+
+template <typename T>
+static int op_qkv_attn(const float* A, const float* W, const float* bias, uint8_t* out, size_t out_bytes, int B, int N, int K, int heads, int causal, int nq) {
+    const int D = heads * 64;
+    const size_t rows = (size_t)B * N;
+    if (out_bytes < rows * D * sizeof(T)) return fail("qkv_attention: output buffer shorter than B * N rows");
+    DevBuf dA, dW, dB, dout;
+    auto body = [&]() -> int {
+        std::vector<float> wp((size_t)3 * D * K), bp((size_t)3 * D);
+        qkv_head_major(W, bias, K, heads, wp.data(), bp.data());
+        ARP_TRY(to_dev<T>(A, rows * K, dA)); ARP_TRY(to_dev<T>(wp.data(), wp.size(), dW)); ARP_TRY(to_dev<float>(bp.data(), bp.size(), dB));
+        ARP_TRY(dout.ensure(std::max<size_t>(out_bytes, 16)));
+        ARP_HIP_OK(hipMemcpy(dout.p, out, out_bytes, hipMemcpyHostToDevice));
+        QkvAttnArgs q;
+        q.A = dA.p; q.W = dW.p; q.bias = dB.as<float>(); q.out = dout.p;
+        q.B = B; q.N = N; q.K = K; q.heads = heads; q.lda = K; q.ldw = K; q.ldo = D; q.fpt = 0; q.nq = nq; q.causal = causal; q.scale = 0.f;
+        const int rc = launch_qkv_attn<T>(q, nullptr);
+        ARP_HIP_OK(hipDeviceSynchronize());
+        ARP_HIP_OK(hipMemcpy(out, dout.p, out_bytes, hipMemcpyDeviceToHost));
+        return rc;
+    };
+    const int rc = body();
+    dA.release(); dW.release(); dB.release(); dout.release();
+    return rc;
+}
+
+extern "C" {
+
+int arp_op_attention_forms(int mode, int impl, const float* qkv, void* out, size_t out_bytes, int B, int N, int D, int heads, int causal, int nq, int form,
+                           float out_scale, int outc) {
+    if (!qkv || !out || B <= 0 || N <= 0 || D <= 0 || heads <= 0 || D % heads) return fail("bad argument");
+    uint8_t* o = static_cast<uint8_t*>(out);
+    if (mode == ARP_MODE_F16) return op_attn_forms<f16_t>(impl, qkv, o, out_bytes, B, N, D, heads, causal, nq, form, out_scale, outc);
+    if (mode == ARP_MODE_BF16) return op_attn_forms<bf16_t>(impl, qkv, o, out_bytes, B, N, D, heads, causal, nq, form, out_scale, outc);
+    if (mode == ARP_MODE_F32) return op_attn_forms<float>(impl, qkv, o, out_bytes, B, N, D, heads, causal, nq, form, out_scale, outc);
+    return fail("attention_forms: mode must be f32, bf16 or f16");
+}
+
+int arp_op_qkv_attention(int mode, const float* A, const float* W, const float* bias, void* out, size_t out_bytes, int B, int N, int K, int heads, int causal,
+                         int nq) {
+    if (!A || !W || !bias || !out || B <= 0 || N <= 0 || K <= 0 || heads <= 0) return fail("bad argument");
+    uint8_t* o = static_cast<uint8_t*>(out);
+    if (mode == ARP_MODE_F16) return op_qkv_attn<f16_t>(A, W, bias, o, out_bytes, B, N, K, heads, causal, nq);
+    if (mode == ARP_MODE_BF16) return op_qkv_attn<bf16_t>(A, W, bias, o, out_bytes, B, N, K, heads, causal, nq);
+    return fail("qkv_attention: 16-bit modes only");
 }
 
 }  // extern "C"

@@ -625,9 +625,9 @@ int arp_enc_finalize_weights(arp_enc* c) {
     // the block GEMMs' weights: operand type, or ARP_MODE_F16C's [W_hi | dW4 (| W4)] rows (e2m1 segments) with their per-tensor scales
     // f16c with vperm: output column o of in_proj's V third (o = 2 D + head * 64 + d') carries the ORIGINAL column 2 D + head * 64 + pi(d'), pi = the swap of
     // bits [5:4] and [3:2] (an involution): the MFMA attention then holds sixteen consecutive original columns per lane (attention.h, outc == 2)
-    const bool vp = f16c && c->vperm && D / k.heads == 64 && c->tokens() > 64;  // (the attention instances of <= 64 tokens keep round 5's stores: attention.h)
+    const bool vp = f16c && c->vperm && attn_vperm_applies(c->tokens(), D / k.heads);  // (the attention instances of <= 64 tokens keep round 5's stores: tower.h)
     c->vperm = vp;
-    auto vperm_col = [&](int o) { return o < 2 * D ? o : (o & ~63) | ((o >> 2) & 3) << 4 | ((o >> 4) & 3) << 2 | (o & 3); };
+    auto vperm_col = [&](int o) { return attn_vperm_col(o, D); };
     std::vector<float> permuted;
     auto up_w = [&](const HostTensor* ht, int in, int out_, int gi, int layer, void** dst) -> int {
         const float* src = ht->data.data();

@@ -22,6 +22,8 @@
 // Every q/k/v value is the same MFMA chain, rounded to the operand type at the same point, as in the unfused path, and the
 // attention code is attn_mfma_kernel's: the output is bit-identical to gemm256 + attn_mfma (tests/test_clip_gpu.py).
 #pragma once
+#include <cstring>
+
 #include "common.h"
 
 namespace arp {
@@ -43,6 +45,19 @@ struct QkvAttnArgs {
 // usable when: 16-bit operands, head_dim 64, N <= 64, K a multiple of 64
 inline bool qkv_attn_supported(int N, int D, int heads, int elem_size) {
     return elem_size == 2 && heads > 0 && D == heads * 64 && N >= 1 && N <= 64 && D % 64 == 0 && (256 / N) * N >= 192;
+}
+
+// Head-major in-proj weight and bias of the fused kernel from the reference's order (w [3 D, K], b [3 D], q | k | v along the rows, D = heads * 64):
+// row h * 192 + j of wp / bp = row (j / 64) * D + h * 64 + j % 64 of w / b.  The weight loader (arp_clip.hip::load_tower) and arp_op_qkv_attention both
+// build their operands with this function.
+inline void qkv_head_major(const float* w, const float* b, int K, int heads, float* wp, float* bp) {
+    const int D = heads * 64;
+    for (int hh = 0; hh < heads; ++hh)
+        for (int j = 0; j < 192; ++j) {
+            const int src = (j >> 6) * D + hh * 64 + (j & 63);
+            memcpy(&wp[(size_t)(hh * 192 + j) * K], &w[(size_t)src * K], (size_t)K * 4);
+            bp[hh * 192 + j] = b[src];
+        }
 }
 
 // defined in qkvattn.hip (its own translation unit: the kernel is compiled once, not once per includer)

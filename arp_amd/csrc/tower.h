@@ -354,6 +354,12 @@ static inline bool attn_mfma_has(int N, int hd) {
     const int NT = ((N + 31) / 32) * 2;
     return hd == 64 && (NT == 2 || NT == 4 || NT == 6 || NT == 8 || NT == 14 || NT == 18);
 }
+// ARP_MODE_F16C's V permutation (attention.h, (outc & 3) == 2): the MFMA attention stores whole 16-column pieces when the producer of qkv has permuted V's
+// columns inside every head -- column o of the V third carries the ORIGINAL column attn_vperm_col(o), the swap of bits [5:4] and [3:2] of the column inside its
+// head (an involution).  Only the instances of more than 64 tokens have that store: at 64 tokens or fewer (and at any other head_dim) V stays as it is and
+// the attention is launched with outc & 3 == 1.  The encoder's weight loader and arp_op_attention_forms both go through these two functions.
+static inline bool attn_vperm_applies(int N, int hd) { return hd == 64 && N > 64; }
+static inline int attn_vperm_col(int o, int D) { return o < 2 * D ? o : (o & ~63) | ((o >> 2) & 3) << 4 | ((o >> 4) & 3) << 2 | (o & 3); }
 constexpr float FP8_S_A = 16.f;  // activation scale of the attention output as an fp8 operand
 
 // ln_1 -> in_proj -> attention -> out_proj (+ residual) with both projections on fp8 operands (TowerCtx::fp8_attn)

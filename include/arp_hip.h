@@ -471,6 +471,26 @@ int arp_op_gemm_bench(int mode, int kernel, int act, int resid, int out_f32, int
 int arp_op_layernorm(const float* x, const float* w, const float* b, float* out, int rows, int D, float eps);
 /* qkv [B*N, 3*D] -> out [B*N, D]; impl 0 = MFMA (bf16 mode, head_dim 64 only), 1 = VALU. */
 int arp_op_attention(int mode, int impl, const float* qkv, float* out, int B, int N, int D, int heads, int causal);
+/* Everything the product's attention launcher takes (csrc/tower.h::launch_attention): nq (query rows produced per sample; 0 = N) and the output form.
+ * `out` is a raw byte buffer of out_bytes >= B * N rows which the CALLER fills: it is uploaded before the launch and downloaded after it, also when the
+ * launcher refuses (its error is returned unchanged), so the caller sees every byte the kernel did not write.  Rows per form:
+ *   ARP_ATTN_OUT_PLAIN   D values of the mode's type (f32 / bf16 / binary16)
+ *   ARP_ATTN_OUT_E4M3    D bytes, e4m3 of out_scale * value                                 (16-bit modes, the MFMA kernel)
+ *   ARP_ATTN_OUT_F16C    3 D bytes [hi: binary16 x D | x4: e2m1 x D | dx4: e2m1 x D]        (ARP_MODE_F16, the MFMA kernel); outc as the encoder passes it:
+ *                        1 or 2, + 4 = no dx4 segment.  With outc & 3 == 2 the entry permutes V's columns as the encoder's weight loader does, under the
+ *                        loader's rule (head_dim 64 and more than 64 tokens; otherwise V stays and the launch gets outc & 3 == 1): pass V unpermuted.
+ *   ARP_ATTN_OUT_SPLIT3  3 D binary16 values [hi | lo | hi]                                 (ARP_MODE_F32, the MFMA kernels: impl 0 and 3) */
+#define ARP_ATTN_OUT_PLAIN 0
+#define ARP_ATTN_OUT_E4M3 1
+#define ARP_ATTN_OUT_F16C 2
+#define ARP_ATTN_OUT_SPLIT3 3
+int arp_op_attention_forms(int mode, int impl, const float* qkv, void* out, size_t out_bytes, int B, int N, int D, int heads, int causal, int nq, int form,
+                           float out_scale, int outc);
+/* The fused QKV projection + attention kernel (csrc/qkvattn.h; 16-bit modes, head_dim 64, N <= 64, K % 64 == 0): A [B*N, K], in-proj weight W [3 D, K] and
+ * bias [3 D] in the reference's order (q | k | v, D = heads * 64) -- the entry builds the head-major operands with the weight loader's own function.
+ * out: caller-filled byte buffer as above, rows of D values of the mode's type. */
+int arp_op_qkv_attention(int mode, const float* A, const float* W, const float* bias, void* out, size_t out_bytes, int B, int N, int K, int heads, int causal,
+                         int nq);
 
 #ifdef __cplusplus
 }

@@ -11,11 +11,11 @@ import numpy as np
 import pytest
 
 from conftest import bf16_round
+from lowbits import BF16, F16, _GRID, _bits16, _fp4_codes, _pack_nibbles, _quant_fp4, _unpack_nibbles, _val16
 
 pytestmark = pytest.mark.gpu
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-F16, BF16 = 2, 1
 S16 = np.uint16(0x7E5A)        # sentinel: a NaN in binary16, ~7e37 in bf16 -- neither is ever a result here
 S8 = np.uint8(0xA5)
 S32 = np.uint32(0x7FC0DEAD)   # an f32 NaN
@@ -23,59 +23,12 @@ S32 = np.uint32(0x7FC0DEAD)   # an f32 NaN
 
 # ---- host-side helpers ----------------------------------------------------------------------------------------------------------------------
 
-def _bits16(x, mode):
-    """f32 / f64 values -> the nearest-even 16-bit words (bf16 via f32: a double rounding only within an f32 ulp of a midpoint)"""
-    if mode == F16:
-        return np.asarray(x, np.float64).astype(np.float16).view(np.uint16)
-    return (bf16_round(np.asarray(x, np.float32)).view(np.uint32) >> 16).astype(np.uint16)
-
-
-def _val16(b, mode):
-    b = np.asarray(b, np.uint16)
-    if mode == F16:
-        return b.view(np.float16).astype(np.float64)
-    return (b.astype(np.uint32) << 16).view(np.float32).astype(np.float64)
-
-
 def _act(x, name):
     if name.endswith("c_fc") and name.startswith("vit"):
         return x / (1.0 + np.exp(-1.702 * x))
     if name.endswith("c_fc"):
         return 0.5 * x * (1 + np.tanh(0.7978845608028654 * (x + 0.044715 * x ** 3)))
     return x
-
-
-_GRID = np.array([0.0, 0.5, 1.0, 1.5, 2.0, 3.0, 4.0, 6.0])
-
-
-def _quant_fp4(x):
-    """OCP e2m1 with round-to-nearest-even, saturating at 6 (as tests/test_ops_gpu.py::_quant_fp4)"""
-    x = np.asarray(x, np.float64)
-    a = np.abs(x)
-    idx = np.clip(np.searchsorted(_GRID, a, side="left"), 1, 7)
-    lo, hi = _GRID[idx - 1], _GRID[idx]
-    mid = 0.5 * (lo + hi)
-    q = np.where(a < mid, lo, np.where(a > mid, hi, np.where((idx - 1) % 2 == 0, lo, hi)))
-    return np.sign(x) * np.minimum(q, 6.0)
-
-
-def _fp4_codes(v):
-    """e2m1 values (already on the grid) -> 4-bit codes"""
-    v = np.asarray(v, np.float64)
-    return (np.searchsorted(_GRID, np.abs(v)) | np.where(v < 0, 8, 0)).astype(np.uint8)
-
-
-def _pack_nibbles(codes):
-    """[R, K] codes -> [R, K / 2] bytes, value 2j in the low nibble"""
-    return (codes[:, 0::2] | (codes[:, 1::2] << 4)).astype(np.uint8)
-
-
-def _unpack_nibbles(b):
-    b = np.asarray(b, np.uint8)
-    codes = np.empty((b.shape[0], b.shape[1] * 2), np.uint8)
-    codes[:, 0::2], codes[:, 1::2] = b & 15, b >> 4
-    mag = _GRID[codes & 7]
-    return np.where(codes & 8, -mag, mag)
 
 
 def _check16(got_bits, v, noise, mode, what, stats=None):
