@@ -1952,6 +1952,91 @@ template <typename T> int op_gemm_tn(int tile256, int ksplit, const float* A, co
     return rc;
 }
 
+// launch_splitk_reduce<OutT> on host slabs: `out` (and `resid`) are [M, ldo ? ldo : N]; out goes up before the launch and comes back whole
+template <typename OutT>
+int op_splitk_reduce(const float* part, int S, int M, int N, const float* bias, int act, const float* resid, float* out, int ldo, float alpha) {
+    DevBuf st, dP, dB, dR, dO;
+    auto body = [&]() -> int {
+        const size_t MN = (size_t)M * N, on = (size_t)M * (ldo ? ldo : N);
+        ARP_TRY(dP.ensure((size_t)S * MN * 4));
+        ARP_HIP_OK(hipMemcpy(dP.p, part, (size_t)S * MN * 4, hipMemcpyHostToDevice));
+        if (bias) ARP_TRY(upload_as<float>(st, dB, bias, (size_t)N));
+        if (resid) ARP_TRY(upload_as<float>(st, dR, resid, on));
+        ARP_TRY(upload_as<OutT>(st, dO, out, on));
+        launch_splitk_reduce<OutT>(nullptr, dP.as<float>(), S, MN, N, bias ? dB.as<float>() : nullptr, act, dO.as<OutT>(), resid ? dR.as<float>() : nullptr, ldo, alpha);
+        ARP_HIP_OK(hipGetLastError());
+        return download_from<OutT>(st, dO, out, on);
+    };
+    const int rc = body();
+    for (DevBuf* b : {&st, &dP, &dB, &dR, &dO}) b->release();
+    return rc;
+}
+
+constexpr int OP_BWD_GUARD_ROWS = 128;  // rows of N floats behind the last slab (a whole row tile: what a missing row guard would reach)
+
+// One backward product as the trainers run it: kind 0 / 1 = tn_gemm's 128- / 256-tile kernel, 2 = ft_gemm_nn's NN kernel.  T = the staging type of the
+// operands (float: the launcher refuses the 32-bit mode itself), OutT = the stored type of `out`.  Operand buffers hold exactly the strided extent.
+struct OpGemmBwd {
+    int kind, tcode, ksplit;
+    const float* A; int lda;
+    const float* B; int ldb;
+    const float* resid; float* out; int ldo;
+    float* slabs;
+    int M, N, K;
+    float alpha;
+};
+template <typename T, typename OutT> int op_gemm_bwd(const OpGemmBwd& a) {
+    DevBuf st, dA, dB, dR, dP, dO;
+    auto body = [&]() -> int {
+        const auto [kind, tcode, ksplit, A, lda, B, ldb, resid, out, ldo, slabs, M, N, K, alpha] = a;
+        const bool nn = kind == 2;
+        const size_t MN = (size_t)M * N, on = (size_t)M * (ldo ? ldo : N);
+        const size_t an = nn ? (size_t)(M - 1) * lda + K : (size_t)(K - 1) * lda + M, bn = (size_t)(K - 1) * ldb + N;
+        const size_t pn = (size_t)ksplit * MN + (size_t)OP_BWD_GUARD_ROWS * N;
+        ARP_TRY(upload_as<T>(st, dA, A, an));
+        ARP_TRY(upload_as<T>(st, dB, B, bn));
+        if (resid) ARP_TRY(upload_as<float>(st, dR, resid, on));
+        ARP_TRY(upload_as<OutT>(st, dO, out, on));
+        const bool split = nn || ksplit > 1;
+        if (split) {
+            ARP_TRY(dP.ensure(pn * 4));
+            if (slabs) ARP_HIP_OK(hipMemcpy(dP.p, slabs, pn * 4, hipMemcpyHostToDevice));
+        }
+        GemmTnArgs g;
+        g.A = dA.p; g.B = dB.p; g.M = M; g.N = N; g.K = K; g.lda = lda; g.ldb = ldb; g.ksplit = ksplit;
+        int rc;
+        if (nn) {
+            g.out = dP.as<float>(); g.ldo = N; g.slice_stride = MN; g.alpha = 1.f;
+            rc = launch_gemm_nn(tcode, g, nullptr);
+        } else {
+            g.tile256 = kind; g.xcd_slices = kind && ksplit % 8 == 0;
+            if (split) { g.out = dP.as<float>(); g.ldo = N; g.slice_stride = MN; g.alpha = 1.f; }
+            else { g.out = dO.as<float>(); g.ldo = ldo ? ldo : N; g.slice_stride = 0; g.alpha = alpha; }
+            rc = launch_gemm_tn(tcode, g, nullptr);
+        }
+        if (rc == 0) ARP_HIP_OK(hipGetLastError());
+        if (split && slabs) ARP_HIP_OK(hipMemcpy(slabs, dP.p, pn * 4, hipMemcpyDeviceToHost));
+        if (rc == 0 && split) {
+            launch_splitk_reduce<OutT>(nullptr, dP.as<float>(), ksplit, MN, N, (const float*)nullptr, (int)ACT_NONE, dO.as<OutT>(),
+                                       resid ? dR.as<float>() : nullptr, ldo == N ? 0 : ldo, alpha);
+            ARP_HIP_OK(hipGetLastError());
+        }
+        // (a refused launch still returns the device's `out`: the caller sees that nothing ran)
+        ARP_TRY(download_from<OutT>(st, dO, out, on));
+        return rc;
+    };
+    const int rc = body();
+    for (DevBuf* b : {&st, &dA, &dB, &dR, &dP, &dO}) b->release();
+    return rc;
+}
+
+template <typename T> int op_gemm_bwd_out(int out_type, const OpGemmBwd& a) {
+    if (out_type == ARP_MODE_F32) return op_gemm_bwd<T, float>(a);
+    if (out_type == ARP_MODE_BF16) return op_gemm_bwd<T, bf16_t>(a);
+    if (out_type == ARP_MODE_F16) return op_gemm_bwd<T, f16_t>(a);
+    return fail("arp_op_gemm_bwd: out_type is ARP_MODE_F32, ARP_MODE_BF16 or ARP_MODE_F16");
+}
+
 template <typename T>
 int op_gemm_relu_bwd(const float* A, const float* W, const float* mask, float* out, float* colsum, int M, int N, int K) {
     DevBuf st, dA, dW, dM, dO, dC, dS;
@@ -2024,6 +2109,37 @@ int arp_op_gemm_tn(int mode, int tile256, int ksplit, const float* A, const floa
     if (mode == ARP_MODE_F16) return op_gemm_tn<f16_t>(tile256, ksplit, A, B, out, M, N, K, alpha);
     if (mode == ARP_MODE_BF16) return op_gemm_tn<bf16_t>(tile256, ksplit, A, B, out, M, N, K, alpha);
     return fail("arp_op_gemm_tn: 16-bit modes only");
+}
+// launch_splitk_reduce<OutT> alone (dtops.h; the narrow / 4-wide kernel is the launcher's choice): out[m, n] = act(alpha * sum_s part[s, m, n] + bias[n])
+// (+ resid[m, n]), stored as out_type (ARP_MODE_F32 / BF16 / F16).  part [S][M][N] f32; out and resid [M, ldo ? ldo : N] f32 on the host -- out is
+// uploaded (rounded to out_type) before the launch and the whole buffer returned widened, so untouched elements come back as they went in.
+int arp_op_splitk_reduce(int out_type, const float* part, int S, int M, int N, const float* bias, int act, const float* resid, float* out, int ldo,
+                         float alpha) {
+    if (!part || !out || S < 1 || M <= 0 || N <= 0 || (ldo != 0 && ldo < N) || (act != ACT_NONE && act != ACT_RELU && act != ACT_TANH))
+        return fail("arp_op_splitk_reduce: bad argument");
+    if (out_type == ARP_MODE_F32) return op_splitk_reduce<float>(part, S, M, N, bias, act, resid, out, ldo, alpha);
+    if (out_type == ARP_MODE_BF16) return op_splitk_reduce<bf16_t>(part, S, M, N, bias, act, resid, out, ldo, alpha);
+    if (out_type == ARP_MODE_F16) return op_splitk_reduce<f16_t>(part, S, M, N, bias, act, resid, out, ldo, alpha);
+    return fail("arp_op_splitk_reduce: out_type is ARP_MODE_F32, ARP_MODE_BF16 or ARP_MODE_F16");
+}
+// One backward product of the trainers.  kind 0 / 1: C[M,N] = alpha * sum_k A[k,m] B[k,n] on the 128- / 256-tile TN kernel as arp_dt.hip::tn_gemm runs it
+// (A [K, lda], B [K, ldb]; ksplit == 1 stores straight into out with alpha in the kernel, otherwise slabs + the fixed-order reduce with alpha there; f32 out,
+// no resid).  kind 2: C[M,N] = alpha * sum_k A[m,k] B[k,n] (+ resid) on the NN kernel as arp_ft.hip::ft_gemm_nn runs it (A [M, lda], B [K, ldb]; always
+// slabs [ksplit][M][N] + the reduce; out_type f32 / bf16 / f16).  Operands are staged in `mode`'s type into buffers of exactly their strided extent, and the
+// requirements on the shape are left to the launchers (which also refuse ARP_MODE_F32).  out / resid [M, ldo ? ldo : N] as in arp_op_splitk_reduce; out comes
+// back whole even when the launcher refuses.  slabs (optional, [ksplit * M * N + 128 * N] f32): uploaded over the slab buffer before the GEMM and read back
+// between the GEMM and the reduce -- the raw slabs and 128 guard rows behind the last one.
+int arp_op_gemm_bwd(int kind, int mode, int out_type, int ksplit, const float* A, int lda, const float* B, int ldb, const float* resid, float* out, int ldo,
+                    float* slabs, int M, int N, int K, float alpha) {
+    if (!A || !B || !out || kind < 0 || kind > 2 || M <= 0 || N <= 0 || K <= 0 || ksplit < 1 || lda < (kind == 2 ? K : M) || ldb < N || (ldo != 0 && ldo < N))
+        return fail("arp_op_gemm_bwd: bad argument");
+    if (kind != 2 && (out_type != ARP_MODE_F32 || resid)) return fail("arp_op_gemm_bwd: the TN products store f32 and take no residual");
+    if (kind != 2 && ksplit == 1 && slabs) return fail("arp_op_gemm_bwd: a direct TN product has no slabs");
+    const OpGemmBwd a{kind, mode, ksplit, A, lda, B, ldb, resid, out, ldo, slabs, M, N, K, alpha};
+    if (mode == ARP_MODE_F32) return op_gemm_bwd_out<float>(out_type, a);
+    if (mode == ARP_MODE_BF16) return op_gemm_bwd_out<bf16_t>(out_type, a);
+    if (mode == ARP_MODE_F16) return op_gemm_bwd_out<f16_t>(out_type, a);
+    return fail("arp_op_gemm_bwd: mode is ARP_MODE_F32 (refused by the launchers), ARP_MODE_BF16 or ARP_MODE_F16");
 }
 // out[M,N] = (A[M,K] . W[N,K]^T) * (mask[M,N] > 0) in the operand type (returned widened), colsum[N] = column sums of the stored
 // values: the ReLU-backward epilogue of the 256 x 256 GEMM (gemm256.h, GemmArgs::mask).  N % 8 == 0, K % 64 == 0.

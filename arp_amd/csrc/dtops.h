@@ -11,7 +11,7 @@ namespace arp {
 
 // ---- generic small f32 GEMM:  C[M,N] (+)= act(opA(A) . opB(B) + bias)  (+ resid) -------------------
 // opA(A)[m,k] = ta ? A[k*lda + m] : A[m*lda + k];  opB(B)[k,n] = tb ? B[n*ldb + k] : B[k*ldb + n].
-// 32x32 output tile per 256-thread block (2x2 per thread), K in steps of 16 through LDS.  Used for the
+// 32x32 output tile per 256-thread block (2x2 per thread), K in steps of 64 through LDS.  Used for the
 // policy transformer (M = B*12 rows, E = 128): a few MFLOP per call, latency- not throughput-bound.
 struct SmallGemm {
     const float* A; const float* B; const float* bias; const float* resid; float* C;

@@ -430,6 +430,20 @@ int arp_op_skinny_gemm(int mode, int act, const float* A, const float* W, const 
  *   and tokens, dres[0] = sum (dz . Wi) * (A - x); E in {32, 64, 128}, D % 128 == 0. */
 int arp_op_gemm_tn(int mode, int tile256, int ksplit, const float* A, const float* B, float* out, int M, int N, int K, float alpha);
 int arp_op_gemm_relu_bwd(int mode, const float* A, const float* W, const float* mask, float* out, float* colsum, int M, int N, int K);
+/* The backward products of the two trainers and the reduce that finishes them (tests/test_backward_gemms_gpu.py).
+ * arp_op_splitk_reduce: out[m,n] = act(alpha * sum_s part[s,m,n] + bias[n]) (+ resid[m,n]) through the product's own launcher (which picks the
+ *   narrow or the 4-wide kernel), stored as out_type (ARP_MODE_F32 / BF16 / F16).  part [S][M][N]; bias, resid optional; act = 0 none, 2 ReLU,
+ *   3 tanh; out and resid are [M, ldo ? ldo : N] (ldo = 0: dense).  out is uploaded before the launch and returned whole, widened to f32.
+ * arp_op_gemm_bwd: kind 0 / 1 = the TN product C = alpha * A^T B (A [K, lda], B [K, ldb]) on the 128- / 256-tile kernel, written directly
+ *   (ksplit == 1) or as K-slice slabs + reduce, f32 out, no resid; kind 2 = the NN product C = alpha * A B (+ resid) (A [M, lda], B [K, ldb]:
+ *   dX = dY . W on a weight as it lies in memory), always slabs + reduce, out_type f32 / bf16 / f16.  mode = the operand type; the shape
+ *   requirements (and the 16-bit-only rule) are the launchers' own: a refused call returns non-zero with out as it went in.  slabs (optional,
+ *   ksplit * M * N + 128 * N floats): prefilled by the caller, returned as it stood between the GEMM and the reduce -- the raw slabs and 128
+ *   guard rows of N behind the last. */
+int arp_op_splitk_reduce(int out_type, const float* part, int S, int M, int N, const float* bias, int act, const float* resid, float* out, int ldo,
+                         float alpha);
+int arp_op_gemm_bwd(int kind, int mode, int out_type, int ksplit, const float* A, int lda, const float* B, int ldb, const float* resid, float* out,
+                    int ldo, float* slabs, int M, int N, int K, float alpha);
 int arp_op_adapter_dy(int mode, const float* dz, const float* Wi, const float* A, const float* x, float rw, float* dApre, float* colsum,
                       float* dres, int R, int E, int tokens, int D);
 /* Times `iters` launches of the GEMM on device-resident random operands (HIP events); kernel: 1 = 128x128,
