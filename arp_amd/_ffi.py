@@ -197,6 +197,18 @@ SIGNATURES = {
     "arp_dt_attach_encoder": (_i, [_vp, _vp]),
     "arp_dt_set_batch_images": (_i, [_vp, _fp, _i32p, _fp, _i]),
     "arp_dt_encode_ahead": (_i, [_vp, _i]),
+    "arp_ds_create": (_i, [C.c_int64, _i, _i, C.POINTER(_vp)]),
+    "arp_ds_destroy": (_i, [_vp]),
+    "arp_ds_upload_frames": (_i, [_vp, C.c_int64, C.c_int64, _u8p]),
+    "arp_ds_set_labels": (_i, [_vp, _i32p, _fp, _i32p, _i]),
+    "arp_ds_set_lut": (_i, [_vp, _fp]),
+    "arp_ds_alloc_encodings": (_i, [_vp, _i, _i]),
+    "arp_ds_upload_encodings": (_i, [_vp, C.c_int64, C.c_int64, _fp]),
+    "arp_ds_encode": (_i, [_vp, _vp, _i]),
+    "arp_ds_gather_debug": (_i, [_vp, _i64p, _i, _i, _fp, _i32p, _fp]),
+    "arp_ds_nbytes": (C.c_int64, [_vp]),
+    "arp_dt_upload_batch_indices_async": (_i, [_vp, _i, _vp, _i64p, _i, _i]),
+    "arp_dt_set_batch_indices": (_i, [_vp, _vp, _i64p, _i, _i]),
     "arp_h5_write_rows_deflated": (_i, [_vp, C.c_int64, C.c_int64, _vp, C.c_uint64, C.c_uint64, C.c_uint64, _i, _i]),
     "arp_h5_inflate_last_frames": (_i, [_i, _i, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), _u8p, C.c_uint64, C.c_uint64,
                                         C.POINTER(C.c_uint64), C.POINTER(C.c_uint32), _u8p, _i]),

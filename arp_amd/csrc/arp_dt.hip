@@ -17,6 +17,7 @@
 #include "../../include/arp_hip.h"
 #include "attention.h"
 #include "common.h"
+#include "ds_internal.h"
 #include "dtops.h"
 #include "enc_internal.h"
 #include "gemm.h"
@@ -85,6 +86,11 @@ struct arp_dt {
         hipEvent_t enc_done = nullptr;  // recorded on the encoder stream behind the encoder pass that filled enc32 from img32
         bool up_recorded = false;       // `up` has been recorded at least once (a slot the prefetcher has used)
         bool enc_ahead = false;         // enc32 holds (or will hold, behind enc_done) the encodings of the frames now in img32: the step does not encode again
+        // a batch named by row indices of a device-resident dataset (arp_dt_upload_batch_indices_async): the indices go through idx_pin, a small pinned
+        // staging buffer of the handle's, into idx, and gather kernels on the upload's stream fill the buffers above
+        DevBuf idx;
+        int32_t* idx_pin = nullptr;
+        int idx_cap = 0;
     } bt[3];  // 0 / 1: the prefetcher's slots (arp_dt_upload_batch*_async); 2: the synchronous arp_dt_set_batch* calls -- a validation
               // step or a greedy action in between prefetched train steps must not write into a slot the uploader thread may be filling
     int cur = 2;
@@ -1501,6 +1507,10 @@ int arp_dt_destroy(arp_dt* c) {
     for (hipEvent_t e : {c->ev_b1, c->ev_b2, c->ev_comm, c->bt[0].up, c->bt[0].use, c->bt[1].up, c->bt[1].use, c->bt[2].up, c->bt[2].use})
         if (e) (void)hipEventDestroy(e);
     c->prof.destroy();
+    for (auto& b : c->bt) {
+        b.idx.release();
+        if (b.idx_pin) (void)hipHostFree(b.idx_pin);
+    }
     DevBuf* all[] = {&c->params, &c->grads, &c->mu, &c->nu, &c->mirror, &c->W2t, &c->Wit, &c->colpart, &c->bt[0].enc32, &c->bt[0].img32, &c->bt[0].action, &c->bt[0].rtg, &c->bt[1].enc32, &c->bt[1].img32, &c->bt[1].action, &c->bt[1].rtg, &c->bt[2].enc32, &c->bt[2].img32, &c->bt[2].action, &c->bt[2].rtg, &c->Xb, &c->XbT,
                      &c->H1, &c->H1T, &c->A, &c->Y, &c->YT, &c->Xc, &c->H1c, &c->A32, &c->Adx, &c->W1c, &c->W2c, &c->wc_scal, &c->dY, &c->dApre, &c->dApreT, &c->G, &c->dH1T, &c->dzb, &c->dzT, &c->part, &c->scal, &c->img,
                      &c->hf, &c->a_in, &c->r_in, &c->ha, &c->hr, &c->logits, &c->ret, &c->metrics, &c->dlogits, &c->dret, &c->dha, &c->dhr, &c->da_in,
@@ -1676,6 +1686,77 @@ int arp_dt_select_batch(arp_dt* c, int slot) {
     c->cur = slot;
     ARP_TRY(ensure_buffers(c, b.B));
     c->use_images = b.images;
+    return 0;
+}
+
+// A batch named by B row indices of a device-resident dataset (arp_ds.hip) into slot `si`, gathered on stream `st`: frames (use_encodings == 0: the encoder-inside
+// boundary, img32 = lut[c][u]) or cached encodings (enc32), and the labels.  Every check runs on the host before anything is enqueued; the caller's idx is
+// copied into the slot's pinned staging buffer and need not outlive the call.
+static int stage_slot_indices(arp_dt* c, int si, hipStream_t st, arp_ds* ds, const int64_t* idx, int B, int use_encodings) {
+    const arp_dt_cfg& k = c->cfg;
+    int tokens = k.enc_tokens, width = k.enc_dim, res = 0, dev = k.device;
+    if (!use_encodings) {
+        if (!c->enc) return fail("no encoder attached: index batches of frames need arp_dt_attach_encoder first (or use_encodings with cached encodings)");
+        ARP_TRY(enc_geometry(c->enc, &tokens, &width, &res, &dev));
+    }
+    const bool with_rtg = k.model != ARP_DT_MODEL_BC;
+    ARP_TRY(ds_check_batch(ds, idx, B, k.window, k.device, k.n_actions, with_rtg, use_encodings ? 1 : 0, res, k.enc_tokens, k.enc_dim));
+    arp_dt::BatchSlot& b = c->bt[si];
+    const size_t R = (size_t)B * k.window;
+    ARP_TRY(b.action.ensure(R * 4));
+    if (with_rtg) ARP_TRY(b.rtg.ensure(R * 4));
+    ARP_TRY(b.enc32.ensure(R * k.enc_tokens * k.enc_dim * 4));  // with frames in: the encoder's output buffer
+    if (!use_encodings) ARP_TRY(b.img32.ensure(R * res * res * 3 * 4));
+    ARP_TRY(b.idx.ensure((size_t)B * 4));
+    if (b.idx_cap < B) {
+        if (b.idx_pin) ARP_HIP_OK(hipHostFree(b.idx_pin));
+        b.idx_pin = nullptr;
+        b.idx_cap = 0;
+        ARP_HIP_OK(hipHostMalloc((void**)&b.idx_pin, (size_t)B * 4, hipHostMallocDefault));
+        b.idx_cap = B;
+    }
+    for (int i = 0; i < B; ++i) b.idx_pin[i] = (int32_t)idx[i];
+    ARP_HIP_OK(hipMemcpyAsync(b.idx.p, b.idx_pin, (size_t)B * 4, hipMemcpyHostToDevice, st));
+    // (profiled on the synchronous slot only: the profiler belongs to the compute thread, the uploader thread must not touch it)
+    hipEvent_t t0 = si == 2 && c->prof.on ? c->prof.begin(st) : nullptr;
+    ARP_TRY(ds_gather_on(ds, st, b.idx.as<int32_t>(), B, k.window, use_encodings ? nullptr : b.img32.as<float>(), use_encodings ? b.enc32.as<float>() : nullptr,
+                         b.action.as<int32_t>(), with_rtg ? b.rtg.as<float>() : nullptr));
+    if (t0) c->prof.end(use_encodings ? "ds.gather_encodings" : "ds.gather_frames", t0, st);
+    b.B = B;
+    b.images = !use_encodings;
+    return 0;
+}
+
+// arp_dt_upload_batch*_async for a batch of row indices: same slots, same copy stream, same protocol (upload_async) -- the host waits for the slot's last
+// reader under the capture lock, `up` is recorded behind the gathers, arp_dt_select_batch / arp_dt_encode_ahead order the step and the encoder behind it.
+int arp_dt_upload_batch_indices_async(arp_dt* c, int slot, arp_ds* ds, const int64_t* idx, int B, int use_encodings) {
+    if (!c || !ds || !idx || B <= 0 || slot < 0 || slot > 1) return fail("bad argument");
+    ARP_HIP_OK(hipSetDevice(c->cfg.device));
+    arp_dt::BatchSlot& b = c->bt[slot];
+    std::lock_guard<std::mutex> capture_lock(c->capture_mu);
+    if (b.used) ARP_HIP_OK(hipEventSynchronize(b.use));
+    if (b.up_recorded) ARP_HIP_OK(hipEventSynchronize(b.up));  // (the copy that last read this slot's pinned staging buffer)
+    if (b.enc_ahead && b.enc_done) ARP_HIP_OK(hipEventSynchronize(b.enc_done));  // (an encode-ahead pass nobody consumed still writes enc32 / reads img32)
+    if (!c->copy_stream[0]) ARP_HIP_OK(hipStreamCreateWithFlags(&c->copy_stream[0], hipStreamNonBlocking));
+    ARP_TRY(stage_slot_indices(c, slot, c->copy_stream[0], ds, idx, B, use_encodings));
+    ARP_HIP_OK(hipEventRecord(b.up, c->copy_stream[0]));
+    b.up_pending = true;
+    b.up_recorded = true;
+    b.enc_ahead = false;
+    return 0;
+}
+
+// The synchronous form (slot 2, the compute stream), as arp_dt_set_batch / arp_dt_set_batch_images.
+int arp_dt_set_batch_indices(arp_dt* c, arp_ds* ds, const int64_t* idx, int B, int use_encodings) {
+    if (!c || !ds || !idx || B <= 0) return fail("bad argument");
+    ARP_HIP_OK(hipSetDevice(c->cfg.device));
+    if (c->bt[2].enc_ahead && c->enc_stream) ARP_HIP_OK(hipStreamSynchronize(c->enc_stream));
+    ARP_TRY(stage_slot_indices(c, 2, c->stream, ds, idx, B, use_encodings));  // (a refused batch leaves the staged one selected)
+    c->cur = 2;
+    c->bt[2].enc_ahead = false;
+    ARP_TRY(ensure_buffers(c, B));
+    ARP_HIP_OK(hipStreamSynchronize(c->stream));
+    c->use_images = !use_encodings;
     return 0;
 }
 

@@ -1,0 +1,16 @@
+// Internal (C++) hooks that let the policy handle fill a batch slot from a device-resident dataset (arp_ds.hip).
+#pragma once
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+struct arp_ds;
+namespace arp {
+// What a batch of indices may read, checked on the HOST before any launch (a bad index is an error string, never an out-of-bounds gather):
+// the dataset lives on `device`, labels are set (with returns-to-go if `need_rtg`), actions fit `n_actions`, every idx is in [0, n_rows), and
+// either every frame row is uploaded and the frame edge is `res` (use_encodings == 0) or every encoding row is present with geometry (tokens, dim)
+// (use_encodings > 0); use_encodings < 0: labels only.
+int ds_check_batch(arp_ds* d, const int64_t* idx, int B, int window, int device, int n_actions, bool need_rtg, int use_encodings, int res, int tokens, int dim);
+// The gathers of one batch, enqueued on `st`.  idx_dev: int32[B] in HBM.  Row of (b, t): j = max(idx[b] - (T - 1 - t), traj_start[idx[b]]).
+// frames_out f32 [B*T, res, res, 3] (= lut[c][u]) or enc_out f32 [B*T, tokens*dim], whichever is non-null; action_out int32 [B*T]; rtg_out f32 [B*T] or null.
+int ds_gather_on(arp_ds* d, hipStream_t st, const int32_t* idx_dev, int B, int T, float* frames_out, float* enc_out, int32_t* action_out, float* rtg_out);
+}  // namespace arp

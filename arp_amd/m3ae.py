@@ -43,7 +43,7 @@ class M3AEEncoder:
         "f16x3" (every GEMM operand an (hi, lo) pair of binary16 values, three 16-bit MFMAs per product, attention / LayerNorm in f32: f32-level error at
         about twice the f32 mode's speed)."""
         _ffi.require_gpu()
-        self.cfg = cfg
+        self.cfg, self.mode, self.max_frames = cfg, mode, int(max_frames) if max_frames > 0 else 128
         c = _ffi.EncCfg(cfg.patch, cfg.width, cfg.layers, cfg.heads, cfg.mlp_ratio, cfg.img_res, {"bf16": MODE_BF16, "f16": MODE_F16, "f32": MODE_F32, "f16x3": MODE_F16X3, "f16c": MODE_F16C}[mode],
                         device, max_frames, attn_impl)
         h = C.c_void_p()

@@ -202,6 +202,41 @@ class PolicyTrainer:
         check(lib.arp_dt_attach_encoder(self._h, encoder._h))
         self._encoder = encoder
 
+    # -- batches named by row indices of a device-resident dataset (arp_amd.dataset.DeviceDataset) -----------------------------------
+    def attach_dataset(self, ds, use_encodings=False):
+        """After this call ``_stage``, ``prefetch_to_device``, ``create_train_step`` / ``create_val_step``'s step functions, ``greedy_action`` and
+        ``greedy_return`` accept a batch dict whose only key is ``"index"`` (int64 row indices): HIP gather kernels build the window batch in the batch slot
+        from the set in HBM.  ``use_encodings=False``: frames, through the attached encoder inside the step; ``True``: the set's cached encodings -- the
+        encodings-in step (the only way model BC trains from a file: it takes encodings)."""
+        if getattr(ds, "window_size", None) is not None and ds.window_size != self.cfg.window:
+            raise _ffi.ArpError(f"the dataset's window is {ds.window_size}, the handle's is {self.cfg.window}")
+        if self.cfg.use_symlog:
+            raise _ffi.ArpError("use_symlog: the set holds rtg / scale, not its symlog (load the set with symlog'd returns through set_labels instead)")
+        if not use_encodings and getattr(self, "_encoder", None) is None:
+            raise _ffi.ArpError("attach_dataset(use_encodings=False) gathers frames: attach the frozen encoder first (attach_encoder)")
+        self._dataset, self._ds_use_enc = ds, bool(use_encodings)
+        ds._trainers.add(self)
+
+    def _index_args(self, index):
+        ds = getattr(self, "_dataset", None)
+        if ds is None:
+            raise _ffi.ArpError('a batch of row indices ({"index": ...}) needs attach_dataset first')
+        idx = np.require(np.asarray(index, dtype=np.int64).reshape(-1), requirements="C")
+        return ds, idx
+
+    def set_batch_indices(self, index):
+        ds, idx = self._index_args(index)
+        check(lib.arp_dt_set_batch_indices(self._h, ds._h, _ffi.as_ptr(idx, C.c_int64), len(idx), int(self._ds_use_enc)))
+        self._B = len(idx)
+
+    def upload_indices_async(self, slot, index):
+        """:meth:`upload_async` for a batch of row indices: the gathers run on the handle's copy stream.  Returns whether the slot now holds frames."""
+        ds, idx = self._index_args(index)
+        check(lib.arp_dt_upload_batch_indices_async(self._h, int(slot), ds._h, _ffi.as_ptr(idx, C.c_int64), len(idx), int(self._ds_use_enc)))
+        self._inflight = getattr(self, "_inflight", {})
+        self._inflight[int(slot)] = (None, None, None, len(idx))
+        return not self._ds_use_enc
+
     def set_batch_images(self, images, action, rtg):
         images = np.require(np.asarray(images, dtype=np.float32), requirements="C")
         action = np.require(np.asarray(action, dtype=np.int32), requirements="C")
@@ -230,18 +265,21 @@ class PolicyTrainer:
         check(lib.arp_dt_backward(self._h))
 
     def _set_batch_any(self, enc, action, rtg):
-        """encodings [B, T, tokens, dim], or -- with a frozen encoder attached -- normalised frames [B, T, H, W, 3] (row N1: what the rollout loop has)"""
-        if getattr(self, "_encoder", None) is not None and np.ndim(enc) == 5 and np.shape(enc)[-1] == 3:
+        """encodings [B, T, tokens, dim], or -- with a frozen encoder attached -- normalised frames [B, T, H, W, 3] (row N1: what the rollout loop has),
+        or -- with a dataset attached -- a batch dict whose only key is ``"index"``"""
+        if is_index_batch(enc):
+            self.set_batch_indices(enc["index"])
+        elif getattr(self, "_encoder", None) is not None and np.ndim(enc) == 5 and np.shape(enc)[-1] == 3:
             self.set_batch_images(enc, action, rtg)
         else:
             self.set_batch(enc, action, rtg)
 
-    def greedy_action(self, enc, action, rtg=None):
+    def greedy_action(self, enc, action=None, rtg=None):
         """ARPDT.greedy_action (ARPDT.py:488-492): argmax of the LAST time step's action logits."""
         self._set_batch_any(enc, action, rtg)
         return self.forward()["action_pred"][:, -1, :].argmax(-1)
 
-    def greedy_return(self, enc, action, rtg):
+    def greedy_return(self, enc, action=None, rtg=None):
         """ARPDT.greedy_return (ARPDT.py:494-495): symexp(return_pred) (utils.py symexp = sign(x)(exp|x| - 1)).  BC has none."""
         if self.bc:
             raise ValueError("model BC has no return head: greedy_return exists for ARP-DT only (BC.py defines greedy_action alone)")
@@ -332,6 +370,11 @@ def symlog(x):
     """``sign(x) * log(1 + |x|)`` (arp_dt/utils.py:445-446)."""
     x = np.asarray(x, np.float32)
     return np.sign(x) * np.log1p(np.abs(x))
+
+
+def is_index_batch(batch):
+    """A batch that names rows of an attached device-resident dataset: a dict whose only key is ``"index"``."""
+    return isinstance(batch, dict) and set(batch) == {"index"}
 
 
 def _batch_arrays(batch, use_symlog=False):
@@ -536,9 +579,13 @@ def prefetch_to_device(iterator, size, trainer, *, rank=0, world=1, device_axis=
                 slot = free.get()
                 if stop.is_set():
                     return
-                enc, act, rtg = _batch_arrays(shard_batch(batch, rank, world, device_axis), trainer.cfg.use_symlog)
-                images = getattr(trainer, "_encoder", None) is not None and enc.ndim == 5 and enc.shape[-1] == 3
-                trainer.upload_async(slot, enc, act, rtg, images=images)
+                part = shard_batch(batch, rank, world, device_axis)
+                if is_index_batch(part):  # rows of the attached dataset: gathered on the GPU into the slot
+                    images = trainer.upload_indices_async(slot, part["index"])
+                else:
+                    enc, act, rtg = _batch_arrays(part, trainer.cfg.use_symlog)
+                    images = getattr(trainer, "_encoder", None) is not None and enc.ndim == 5 and enc.shape[-1] == 3
+                    trainer.upload_async(slot, enc, act, rtg, images=images)
                 if images and os.environ.get("ARP_DT_ENCODE_AHEAD", "1") != "0" and os.environ.get("ARP_DT_ENC_EAGER", "1") != "0":
                     trainer.encode_ahead(slot)  # the frozen encoder's pass for this batch runs beside the step that is reading the OTHER slot
                 ready.put(DeviceBatch(trainer, slot, lambda s=slot: free.put(s)))
@@ -591,7 +638,11 @@ def _stage(tr, batch, rank, world, device_axis):
     if isinstance(batch, DeviceBatch):
         tr.select(batch.slot)
         return batch
-    enc, act, rtg = _batch_arrays(shard_batch(batch, rank, world, device_axis), tr.cfg.use_symlog)
+    part = shard_batch(batch, rank, world, device_axis)
+    if is_index_batch(part):
+        tr.set_batch_indices(part["index"])
+        return None
+    enc, act, rtg = _batch_arrays(part, tr.cfg.use_symlog)
     tr._set_batch_any(enc, act, rtg) if hasattr(tr, "_set_batch_any") else tr.set_batch(enc, act, rtg)  # frames in with a frozen encoder attached (row N1): set_batch_images
     return None
 

@@ -392,6 +392,32 @@ int arp_dt_set_batch_images(arp_dt* h, const float* images, const int32_t* actio
  * instead of encoding.  Callable from the uploader thread.  Without it a step encodes its own batch at its head (same stream of work, same encodings). */
 int arp_dt_encode_ahead(arp_dt* h, int slot);
 
+/* ---- a demonstration set resident in HBM: policy batches from row indices -------------------------
+ * ProcgenDataset.__getitem__ (arp_dt/data_procgen.py:180-213) reads ob[i][-T:] of a file whose rows the recorder stacks (row i adds one frame, ob[i, -1]).
+ * The handle keeps that one uint8 frame per row [n_rows, res, res, 3], per-row action / return-to-go / first row of the trajectory, and optionally one
+ * encoding per row; position t of the window of row i reads row j = max(i - (T - 1 - t), traj_start[i]).  res * res * 3 must be a multiple of 16. */
+typedef struct arp_ds arp_ds;
+int arp_ds_create(int64_t n_rows, int res, int device, arp_ds** out);
+int arp_ds_destroy(arp_ds* ds);
+int arp_ds_upload_frames(arp_ds* ds, int64_t row0, int64_t n, const uint8_t* u8_host); /* rows [row0, row0 + n), synchronous: callable chunk by chunk */
+/* rtg may be NULL (model BC reads none).  Checked here, once: actions in [0, n_actions), 0 <= traj_start[i] <= i, traj_start non-decreasing. */
+int arp_ds_set_labels(arp_ds* ds, const int32_t* action, const float* rtg, const int32_t* traj_start, int n_actions);
+/* lut[c * 256 + u]: the f32 value of byte u in channel c.  A gathered frame holds exactly these values. */
+int arp_ds_set_lut(arp_ds* ds, const float* lut768);
+int arp_ds_alloc_encodings(arp_ds* ds, int tokens, int dim); /* tokens * dim a multiple of 4 */
+int arp_ds_upload_encodings(arp_ds* ds, int64_t row0, int64_t n, const float* f32_host);
+/* Every frame through `enc` into the encoding cache, `chunk` rows at a time (<= 0: 128).  Synchronous.  Must not run beside a prefetcher or a step of a policy
+ * handle `enc` is attached to (they share the encoder's workspace). */
+int arp_ds_encode(arp_ds* ds, arp_enc* enc, int chunk);
+/* Debug read-back of the batch the indices name: f32 [B, window, res, res, 3], int32 [B, window], f32 [B, window]; each output may be NULL. */
+int arp_ds_gather_debug(arp_ds* ds, const int64_t* idx, int B, int window, float* frames_out, int32_t* action_out, float* rtg_out);
+int64_t arp_ds_nbytes(arp_ds* ds); /* HBM the handle holds */
+/* A batch named by B row indices into slot 0 / 1 (asynchronous, the protocol of arp_dt_upload_batch_async) or the synchronous slot: gather kernels on the handle's
+ * copy stream write the slot's frames (use_encodings == 0: needs an attached encoder of the dataset's res) or its encodings (use_encodings != 0: needs the cache,
+ * [enc_tokens, enc_dim] per row) and its labels.  Every index and every geometry is checked on the host first; idx need not outlive the call. */
+int arp_dt_upload_batch_indices_async(arp_dt* h, int slot, arp_ds* ds, const int64_t* idx, int B, int use_encodings);
+int arp_dt_set_batch_indices(arp_dt* h, arp_ds* ds, const int64_t* idx, int B, int use_encodings);
+
 /* ---- host I/O of path (1) (no GPU involved) -------------------------------
  * Reads n stored chunks of a gzip-chunked dataset (`ob` of data/PPG/trajectory_recorder.py:148-176: one chunk = one row =
  * num_frames frames) from file descriptor fd at addr[i] (size[i] bytes as stored; 0 = never written), inflates them on
