@@ -90,6 +90,7 @@ _i64p = C.POINTER(C.c_int64)
 SIGNATURES = {
     "arp_last_error": (C.c_char_p, []),
     "arp_version": (_i, []),
+    "arp_debug_live": (_i, [_i64p]),
     "arp_device_count": (_i, []),
     "arp_dev_malloc": (_i, [C.POINTER(_vp), C.c_size_t]),
     "arp_dev_free": (_i, [_vp]),

@@ -6,6 +6,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <map>
+#include <memory>
 #include <string>
 #include <vector>
 
@@ -40,12 +41,11 @@ struct HostTensor {
 
 using namespace arp;
 
-struct arp_clip {
+// The model as every stream of a handle sees it: configuration, flags, and raw pointers into weight allocations the primary handle owns.  Plainly copyable:
+// this, and nothing else, is what a second-stream sibling is built from.
+struct ClipModel {
     arp_clip_cfg cfg;
-    hipStream_t stream = nullptr;
-    std::map<std::string, HostTensor> staged;
     bool finalized = false;
-    std::vector<void*> owned;  // every device allocation holding weights
 
     TowerW vis, txt;
     void* conv_w = nullptr;  // T [D, 3PP]
@@ -59,47 +59,8 @@ struct arp_clip {
     // It runs once per prompt set (6 GFLOP); the multi-scale text path of the fine-tune step keeps the 16-bit weights.
     TowerW txt32;
     void* tproj_t32 = nullptr;
-    float logit_scale = 0.f;
     float* lut = nullptr;
 
-    DevBuf txt_feat;
-    int n_prompts = 0;
-    DevBuf txt_mean;        // mean of the cached (normalised) prompt vectors: the rollout loop's `isinstance(pos_text, list)` branch
-    int prompt_reduce = 0;  // 0 = prompt 0 (label_reward.py:146, quirk Q1), 1 = mean over the prompts (envs/vl_reward.py:19-22)
-    DevBuf ms_keep;         // multi-scale export buffer kept between calls of the online adapter reward (a hipMalloc per call would cost more than the head)
-
-    // workspace for `ws_frames` frames
-    int ws_frames = 0;
-    DevBuf patches, pe, x, h, qkv, ao, fc, cls_h, feat, frames_in, rewards;
-    std::map<long long, ResizePlan*> plans;
-    Profiler prof;
-    // second stream: a shallow clone (shared weights, own workspace/stream/profiler) that labels the other half of a
-    // batch concurrently, so one half's memory-bound kernels and GEMM tails overlap the other half's GEMMs
-    // multi-scale export target of the NEXT tower run (row N2); cleared after use
-    float* ms_out = nullptr;
-    int ms_ld = 0;
-    const int* ms_rows = nullptr;
-    int pre_bilinear = 0;  // next forward_chunk uses the fine-tune transform (bilinear) instead of the PIL-bicubic one
-    std::vector<arp_clip*> siblings;  // n_streams - 1 clones
-    bool is_sibling = false;
-    hipEvent_t ev_fork = nullptr;
-    std::vector<hipEvent_t> ev_join;  // one per sibling
-    // host-fed labelling (the S2 seam): every part's frames go up on ONE copy stream, back to back at the full PCIe rate, and the part's
-    // compute stream waits for its own slice only.  From pinned / registered host memory (arp_host_register) the copies are true DMA and
-    // all of them are in flight before the first kernel; from pageable memory the runtime stages them and the call order does the overlap.
-    hipStream_t copy_stream = nullptr;
-    std::vector<hipEvent_t> ev_copy;  // one per part
-    // arp_clip_label_submit / _collect: two host-fed calls in flight.  A synchronous arp_clip_label pays the pipeline's fill and drain on
-    // every call (13.3 ms per 1024 frames where back-to-back passes take 10.5 ms and the 3.5 ms upload overlaps them completely:
-    // scripts/seam_probe.py); with the next call's upload and kernels queued behind the running one the streams never drain.
-    struct LabelSlot {
-        DevBuf frames, rewards;
-        float* host = nullptr;  // pinned staging of the rewards (a D2H into pageable memory would block the submitting thread)
-        size_t host_n = 0;
-        hipEvent_t done = nullptr;
-        int n = 0;
-        bool busy = false;
-    } lslot[2];
     int gemm_force = 0;  // 0 auto, 1 force the 128x128 kernel, 2 force the 256x256 kernel (ARP_GEMM env)
     // Fold LayerNorm into the consumer GEMMs of the vision tower in bf16 mode (ARP_LN_FOLD=1).  Numerically fine
     // (cosine error 3.6e-4 vs 4.8e-4 unfused) but MEASURED SLOWER on MI355X (74.2 k vs 79.7 k frames/s): the extra
@@ -108,25 +69,78 @@ struct arp_clip {
     bool ln_fold = false;
     bool fp8_mlp = false;       // vision tower MLP GEMMs on the scaled fp8 MFMA (arp_clip_set_fp8_mlp before finalize; tower.h)
     bool fp8_attn = false;      // ... and in_proj / out_proj as well (arp_clip_set_fp8_mlp(c, 2))
-    DevBuf clock_buf;           // arp_clip_clock_probe: three u64 the clock-diagnostic c_fc instance accumulates into (owned by the primary handle)
-    unsigned long long* clock_acc = nullptr;  // null: the ordinary instances run
-    bool shared_chip = false;   // this handle's kernels run beside another part stream's (label_dev with two or more parts): tower.h picks out_proj's kernel by it
     bool qkv_fused = true;      // QKV projection + attention in one kernel (qkvattn.h) where the geometry allows; ARP_QKV_FUSED=0 disables
     bool cls_only_last = true;  // vision tower: the last block computes only what ln_post reads (tower.h); ARP_CLS_ONLY=0 disables
+    bool lat_fold = true;   // ARP_LAT_FOLD=0: reduce + LayerNorm kernels instead (seven launches per block instead of five)
+    bool skinny = true;     // ARP_SKINNY=0: the output-tiled GEMMs at every size
+    int lat_rows = 1024;    // a pass of at most this many token rows takes the latency path (ARP_SKINNY_ROWS; = the kernel's cap).  Against the
+                            // throughput kernels (profiles/r3_latency_rows.txt): +63 % at 50 rows, +51 % at 300, +29 % at 600, +5..12 % at 1000
+    bool lat_graph = true;  // ARP_CLIP_GRAPH=0: launch by launch
+    bool lat_pinned = true;
+
+    int ntok() const { return (cfg.img_res / cfg.patch) * (cfg.img_res / cfg.patch) + 1; }
+    size_t esz() const { return cfg.mode == ARP_MODE_F32 ? 4 : 2; }
+};
+
+struct arp_clip : ClipModel {
+    Stream stream;
+    std::map<std::string, HostTensor> staged;
+    std::vector<DevBuf> owned;  // every device allocation holding weights
+
+    // second stream: a sibling built from the primary's ClipModel (shared weights, own workspace / stream / profiler) that labels the other half of a
+    // batch concurrently, so one half's memory-bound kernels and GEMM tails overlap the other half's GEMMs.  What follows down to `plans` is the
+    // primary's: a sibling reads it through shared(), so a prompt set or a plan the primary re-allocates is the one every stream sees.
+    arp_clip* primary = nullptr;  // siblings only
+    arp_clip* shared() { return primary ? primary : this; }
+    float logit_scale = 0.f;
+    DevBuf txt_feat;
+    int n_prompts = 0;
+    DevBuf txt_mean;        // mean of the cached (normalised) prompt vectors: the rollout loop's `isinstance(pos_text, list)` branch
+    int prompt_reduce = 0;  // 0 = prompt 0 (label_reward.py:146, quirk Q1), 1 = mean over the prompts (envs/vl_reward.py:19-22)
+    DevBuf clock_buf;           // arp_clip_clock_probe: three u64 the clock-diagnostic c_fc instance accumulates into
+    unsigned long long* clock_acc = nullptr;  // null: the ordinary instances run
+    std::map<long long, std::unique_ptr<ResizePlan>> plans;
+
+    DevBuf ms_keep;         // multi-scale export buffer kept between calls of the online adapter reward (a hipMalloc per call would cost more than the head)
+
+    // workspace for `ws_frames` frames
+    int ws_frames = 0;
+    DevBuf patches, pe, x, h, qkv, ao, fc, cls_h, feat, frames_in, rewards;
+    Profiler prof;
+    // multi-scale export target of the NEXT tower run (row N2); cleared after use
+    float* ms_out = nullptr;
+    int ms_ld = 0;
+    const int* ms_rows = nullptr;
+    int pre_bilinear = 0;  // next forward_chunk uses the fine-tune transform (bilinear) instead of the PIL-bicubic one
+    std::vector<std::unique_ptr<arp_clip>> siblings;  // n_streams - 1 of them
+    Event ev_fork;
+    std::vector<Event> ev_join;  // one per sibling
+    // host-fed labelling (the S2 seam): every part's frames go up on ONE copy stream, back to back at the full PCIe rate, and the part's
+    // compute stream waits for its own slice only.  From pinned / registered host memory (arp_host_register) the copies are true DMA and
+    // all of them are in flight before the first kernel; from pageable memory the runtime stages them and the call order does the overlap.
+    Stream copy_stream;
+    std::vector<Event> ev_copy;  // one per part
+    // arp_clip_label_submit / _collect: two host-fed calls in flight.  A synchronous arp_clip_label pays the pipeline's fill and drain on
+    // every call (13.3 ms per 1024 frames where back-to-back passes take 10.5 ms and the 3.5 ms upload overlaps them completely:
+    // scripts/seam_probe.py); with the next call's upload and kernels queued behind the running one the streams never drain.
+    struct LabelSlot {
+        DevBuf frames, rewards;
+        PinBuf host;  // pinned staging of the rewards (a D2H into pageable memory would block the submitting thread)
+        Event done;
+        int n = 0;
+        bool busy = false;
+    } lslot[2];
+    bool shared_chip = false;   // this handle's kernels run beside another part stream's (label_dev with two or more parts): tower.h picks out_proj's kernel by it
     DevBuf stats;
     // latency path (get_torch_clip_reward): split-K slabs of the skinny GEMMs (tower.h), and the whole pass over
     // <= SKINNY_MAX_M token rows -- preprocess .. reward, ~80 launches -- replayed as ONE hipGraph per (buffers, geometry): the host then
-    // pays one graph launch instead of 80 kernel launches that each cost more host time than the kernel runs
+    // pays one graph launch instead of 80 kernel launches that each cost more host time than the kernel runs.  It never runs on a sibling
+    // (parts of >= 128 frames), whose part / lat_stats / pinned buffers stay empty.
     DevBuf part;
     DevBuf lat_stats;       // folded LayerNorm on the latency path: [rows][width / 16][2] strip sums (tower.h)
-    bool lat_fold = true;   // ARP_LAT_FOLD=0: reduce + LayerNorm kernels instead (seven launches per block instead of five)
     bool lat_f0 = false;    // the pass being enqueued: the token-assembly kernel wrote the operand copy + statistics of block 0
-    bool skinny = true;     // ARP_SKINNY=0: the output-tiled GEMMs at every size
     bool lat_h0 = false;    // ... and its token-assembly kernel already wrote ln_1 of the first block into h
-    int lat_rows = 1024;    // a pass of at most this many token rows takes the latency path (ARP_SKINNY_ROWS; = the kernel's cap).  Against the
-                            // throughput kernels (profiles/r3_latency_rows.txt): +63 % at 50 rows, +51 % at 300, +29 % at 600, +5..12 % at 1000
     bool lat_now = false;   // the pass being enqueued has at most SKINNY_MAX_M token rows (set by forward_chunk)
-    bool lat_graph = true;  // ARP_CLIP_GRAPH=0: launch by launch
     struct LatGraph {
         const uint8_t* frames;
         float* rewards;
@@ -134,18 +148,15 @@ struct arp_clip {
         hipGraph_t graph;
         hipGraphExec_t exec;
     };
-    std::vector<LatGraph> lat_graphs;
+    std::vector<LatGraph> lat_graphs;  // (destroyed by arp_clip_destroy, behind the stream's synchronisation)
     // host-fed single-frame calls: the frame is copied into pinned memory by the CPU and the preprocess kernel reads it over PCIe;
     // the reward kernel writes into pinned memory -- no copy operations on the stream at all (ARP_CLIP_PINNED=0: hipMemcpyAsync both ways)
-    uint8_t* pin_frames = nullptr;
-    size_t pin_frames_bytes = 0;
-    float* pin_rewards = nullptr;
-    size_t pin_rewards_n = 0;
-    bool lat_pinned = true;
+    PinBuf pin_frames, pin_rewards;
 
-    int ntok() const { return (cfg.img_res / cfg.patch) * (cfg.img_res / cfg.patch) + 1; }
-    size_t esz() const { return cfg.mode == ARP_MODE_F32 ? 4 : 2; }
+    arp_clip() = default;
+    explicit arp_clip(const ClipModel& m) : ClipModel(m) {}
 };
+static_assert(!std::is_copy_constructible_v<arp_clip> && std::is_copy_constructible_v<ClipModel>);
 
 namespace arp {
 
@@ -157,7 +168,7 @@ static TowerCtx ctx_of(arp_clip* c) {
     t.gemm_force = c->gemm_force;
     t.qkv_fused = c->qkv_fused;
     t.shared_chip = c->shared_chip;
-    t.clock_acc = c->clock_acc;
+    t.clock_acc = c->shared()->clock_acc;
     t.fp8_mlp = c->fp8_mlp; t.fp8_attn = c->fp8_attn;
     t.ms_out = c->ms_out; t.ms_ld = c->ms_ld; t.ms_rows = c->ms_rows;
     t.skinny = c->lat_now; t.h_ready0 = c->lat_now && c->lat_h0; t.lat_stats = c->lat_stats.as<float>(); t.lat_fold0 = c->lat_now && c->lat_f0; t.part = c->part.as<float>(); t.part_floats = c->part.bytes / 4;
@@ -165,12 +176,7 @@ static TowerCtx ctx_of(arp_clip* c) {
 }
 
 static int upload_f32(arp_clip* c, const std::vector<float>& v, float** out) {
-    void* p = nullptr;
-    ARP_HIP_OK(hipMalloc(&p, std::max<size_t>(v.size() * 4, 16)));
-    ARP_HIP_OK(hipMemcpy(p, v.data(), v.size() * 4, hipMemcpyHostToDevice));
-    c->owned.push_back(p);
-    *out = static_cast<float*>(p);
-    return 0;
+    return upload_owned(c->owned, v.data(), v.size() * 4, std::max<size_t>(v.size() * 4, 16), reinterpret_cast<void**>(out));
 }
 
 // uploads a [rows, cols] matrix in the handle's GEMM operand type (bf16 RNE or f32); optional transpose
@@ -186,22 +192,18 @@ static int upload_mat(arp_clip* c, const float* src, int rows, int cols, bool tr
             for (int q = 0; q < cols; ++q) tmp[(size_t)q * rows + r] = src[(size_t)r * cols + q];
         s = tmp.data();
     }
-    void* p = nullptr;
-    ARP_HIP_OK(hipMalloc(&p, std::max<size_t>(n * esz, 16)));
+    const size_t alloc = std::max<size_t>(n * esz, 16);
     if (mode == ARP_MODE_BF16) {
         std::vector<bf16_t> hb(n);
         for (size_t i = 0; i < n; ++i) hb[i] = host_f2bf(s[i]);
-        ARP_HIP_OK(hipMemcpy(p, hb.data(), n * 2, hipMemcpyHostToDevice));
-    } else if (mode == ARP_MODE_F16) {
+        return upload_owned(c->owned, hb.data(), n * 2, alloc, out);
+    }
+    if (mode == ARP_MODE_F16) {
         std::vector<f16_t> hb(n);
         for (size_t i = 0; i < n; ++i) hb[i] = host_f2h(s[i]);
-        ARP_HIP_OK(hipMemcpy(p, hb.data(), n * 2, hipMemcpyHostToDevice));
-    } else {
-        ARP_HIP_OK(hipMemcpy(p, s, n * 4, hipMemcpyHostToDevice));
+        return upload_owned(c->owned, hb.data(), n * 2, alloc, out);
     }
-    c->owned.push_back(p);
-    *out = p;
-    return 0;
+    return upload_owned(c->owned, s, n * 4, alloc, out);
 }
 
 static int get_staged(arp_clip* c, const std::string& name, std::vector<int64_t> shape, const HostTensor** out) {
@@ -253,13 +255,8 @@ static int load_tower(arp_clip* c, const std::string& prefix, int d, int layers,
                 const float sc = mx > 0.f ? exp2f(floorf(log2f(240.f / mx))) : 1.f;  // power of two: the largest weight lands in [120, 240]
                 std::vector<fp8_t> q(w.size());
                 for (size_t i = 0; i < w.size(); ++i) q[i] = host_f2fp8(w[i] * sc);
-                void* dp = nullptr;
-                ARP_HIP_OK(hipMalloc(&dp, q.size()));
-                ARP_HIP_OK(hipMemcpy(dp, q.data(), q.size(), hipMemcpyHostToDevice));
-                c->owned.push_back(dp);
-                *out = dp;
                 *scale = sc;
-                return 0;
+                return upload_owned(c->owned, q.data(), q.size(), q.size(), out);
             };
             const HostTensor *w1, *w2, *lw, *lb;
             float s1 = 1.f, s2 = 1.f;
@@ -291,12 +288,7 @@ static int load_tower(arp_clip* c, const std::string& prefix, int d, int layers,
             std::vector<bf16_t> wf;
             std::vector<float> cc, dd;
             auto put = [&](const std::vector<bf16_t>& m, void** out) -> int {
-                void* dp = nullptr;
-                ARP_HIP_OK(hipMalloc(&dp, m.size() * 2));
-                ARP_HIP_OK(hipMemcpy(dp, m.data(), m.size() * 2, hipMemcpyHostToDevice));
-                c->owned.push_back(dp);
-                *out = dp;
-                return 0;
+                return upload_owned(c->owned, m.data(), m.size() * 2, m.size() * 2, out);
             };
             ARP_TRY(get_staged(c, p + "attn.in_proj_weight", {3 * d, d}, &w)); ARP_TRY(get_staged(c, p + "attn.in_proj_bias", {3 * d}, &b));
             ARP_TRY(get_staged(c, p + "ln_1.weight", {d}, &lw)); ARP_TRY(get_staged(c, p + "ln_1.bias", {d}, &lb));
@@ -318,12 +310,7 @@ static int load_tower(arp_clip* c, const std::string& prefix, int d, int layers,
             std::vector<bf16_t> wf;
             std::vector<float> cc, dd;
             auto put = [&](const std::vector<bf16_t>& m, void** out) -> int {
-                void* dp = nullptr;
-                ARP_HIP_OK(hipMalloc(&dp, m.size() * 2));
-                ARP_HIP_OK(hipMemcpy(dp, m.data(), m.size() * 2, hipMemcpyHostToDevice));
-                c->owned.push_back(dp);
-                *out = dp;
-                return 0;
+                return upload_owned(c->owned, m.data(), m.size() * 2, m.size() * 2, out);
             };
             const bool half = emode == ARP_MODE_F16;
             ARP_TRY(get_staged(c, p + "attn.in_proj_weight", {3 * d, d}, &w)); ARP_TRY(get_staged(c, p + "attn.in_proj_bias", {3 * d}, &b));
@@ -399,17 +386,13 @@ static int get_plan(arp_clip* c, int H, int W, int use_crop, ResizePlan** out, b
     const long long key = ((long long)H << 32) | ((long long)W << 2) | (small ? 2 : 0) | (use_crop ? 1 : 0);
     auto it = c->plans.find(key);
     if (it != c->plans.end()) {
-        *out = it->second;
+        *out = it->second.get();
         return 0;
     }
-    ResizePlan* p = new ResizePlan();
-    const int r = build_plan(H, W, use_crop, c->cfg.img_res, *p, small ? 8 : 32);
-    if (r != 0) {
-        delete p;
-        return r;
-    }
-    c->plans[key] = p;
-    *out = p;
+    auto p = std::make_unique<ResizePlan>();
+    ARP_TRY(build_plan(H, W, use_crop, c->cfg.img_res, *p, small ? 8 : 32));
+    *out = p.get();
+    c->plans[key] = std::move(p);
     return 0;
 }
 
@@ -501,7 +484,6 @@ template <typename T> static int run_text(arp_clip* c, const int32_t* tokens, in
     const size_t e = sizeof(T);
     DevBuf tok, eot, x, h, qkv, ao, fc, hs, ms, feat_tmp;
     DevBuf& feat = out_host ? feat_tmp : c->txt_feat;
-    int rc = 0;
     std::vector<int> eot_rows(np);
     for (int p = 0; p < np; ++p) {
         int best = 0;
@@ -511,44 +493,39 @@ template <typename T> static int run_text(arp_clip* c, const int32_t* tokens, in
         for (int t = 0; t < ctx; ++t)
             if (tokens[p * ctx + t] < 0 || tokens[p * ctx + t] >= k.vocab) return fail("set_text: token id out of range");
     }
-    auto body = [&]() -> int {
-        ARP_TRY(tok.ensure((size_t)M * 4)); ARP_TRY(eot.ensure((size_t)np * 4));
-        ARP_TRY(x.ensure((size_t)M * Tw * 4)); ARP_TRY(h.ensure((size_t)M * Tw * e)); ARP_TRY(qkv.ensure((size_t)M * 3 * Tw * e));
-        ARP_TRY(ao.ensure((size_t)M * Tw * e)); ARP_TRY(fc.ensure((size_t)M * 4 * Tw * e)); ARP_TRY(hs.ensure((size_t)np * Tw * e));
-        ARP_TRY(feat.ensure((size_t)np * k.embed * 4));
-        if (ms_host) ARP_TRY(ms.ensure((size_t)np * c->txt.layers * Tw * 4));
-        ARP_HIP_OK(hipMemcpyAsync(tok.p, tokens, (size_t)M * 4, hipMemcpyHostToDevice, c->stream));
-        ARP_HIP_OK(hipMemcpyAsync(eot.p, eot_rows.data(), (size_t)np * 4, hipMemcpyHostToDevice, c->stream));
-        hipLaunchKernelGGL(text_embed_kernel, dim3((M + 3) / 4), dim3(256), 0, c->stream, tok.as<int>(), c->tok_emb, c->tpos,
-                           x.as<float>(), M, ctx, Tw);
-        ARP_HIP_OK(hipGetLastError());
-        if (ms_host) { c->ms_out = ms.as<float>(); c->ms_ld = c->txt.layers * Tw; c->ms_rows = eot.as<int>(); }
-        const int rb = run_blocks<T>(c, txt, "text", x.as<float>(), h.as<T>(), qkv.as<T>(), ao.as<T>(), fc.as<T>(), np, ctx, 1);
-        c->ms_out = nullptr; c->ms_rows = nullptr;
-        ARP_TRY(rb);
-        // ln_final, EOT row, text_projection (arp_dt/models/openai/layers.py:367-369)
+    ARP_TRY(tok.ensure((size_t)M * 4)); ARP_TRY(eot.ensure((size_t)np * 4));
+    ARP_TRY(x.ensure((size_t)M * Tw * 4)); ARP_TRY(h.ensure((size_t)M * Tw * e)); ARP_TRY(qkv.ensure((size_t)M * 3 * Tw * e));
+    ARP_TRY(ao.ensure((size_t)M * Tw * e)); ARP_TRY(fc.ensure((size_t)M * 4 * Tw * e)); ARP_TRY(hs.ensure((size_t)np * Tw * e));
+    ARP_TRY(feat.ensure((size_t)np * k.embed * 4));
+    if (ms_host) ARP_TRY(ms.ensure((size_t)np * c->txt.layers * Tw * 4));
+    ARP_HIP_OK(hipMemcpyAsync(tok.p, tokens, (size_t)M * 4, hipMemcpyHostToDevice, c->stream));
+    ARP_HIP_OK(hipMemcpyAsync(eot.p, eot_rows.data(), (size_t)np * 4, hipMemcpyHostToDevice, c->stream));
+    hipLaunchKernelGGL(text_embed_kernel, dim3((M + 3) / 4), dim3(256), 0, c->stream, tok.as<int>(), c->tok_emb, c->tpos,
+                       x.as<float>(), M, ctx, Tw);
+    ARP_HIP_OK(hipGetLastError());
+    if (ms_host) { c->ms_out = ms.as<float>(); c->ms_ld = c->txt.layers * Tw; c->ms_rows = eot.as<int>(); }
+    const int rb = run_blocks<T>(c, txt, "text", x.as<float>(), h.as<T>(), qkv.as<T>(), ao.as<T>(), fc.as<T>(), np, ctx, 1);
+    c->ms_out = nullptr; c->ms_rows = nullptr;
+    ARP_TRY(rb);
+    // ln_final, EOT row, text_projection (arp_dt/models/openai/layers.py:367-369)
 #define ARP_LNG_CALL(NV)                                                                                                     \
-    hipLaunchKernelGGL((layernorm_gather_kernel<T, NV>), dim3((np + 3) / 4), dim3(256), 0, c->stream, x.as<float>(), (size_t)Tw, \
-                       eot.as<int>(), hs.as<T>(), Tw, c->lnf_w, c->lnf_b, np, Tw, 1e-5f)
-        ARP_NV_DISPATCH(Tw, ARP_LNG_CALL);
+hipLaunchKernelGGL((layernorm_gather_kernel<T, NV>), dim3((np + 3) / 4), dim3(256), 0, c->stream, x.as<float>(), (size_t)Tw, \
+                   eot.as<int>(), hs.as<T>(), Tw, c->lnf_w, c->lnf_b, np, Tw, 1e-5f)
+    ARP_NV_DISPATCH(Tw, ARP_LNG_CALL);
 #undef ARP_LNG_CALL
+    ARP_HIP_OK(hipGetLastError());
+    ARP_TRY((gemm<T, float, ACT_NONE, false, SITE_PROJ>(c, "text.proj", hs.p, tproj, nullptr, nullptr, feat.p, np,
+                                                        k.embed, Tw)));
+    if (normalize) {
+        hipLaunchKernelGGL(l2_normalize_kernel, dim3((np + 3) / 4), dim3(256), 0, c->stream, feat.as<float>(), np, k.embed);
         ARP_HIP_OK(hipGetLastError());
-        ARP_TRY((gemm<T, float, ACT_NONE, false, SITE_PROJ>(c, "text.proj", hs.p, tproj, nullptr, nullptr, feat.p, np,
-                                                            k.embed, Tw)));
-        if (normalize) {
-            hipLaunchKernelGGL(l2_normalize_kernel, dim3((np + 3) / 4), dim3(256), 0, c->stream, feat.as<float>(), np, k.embed);
-            ARP_HIP_OK(hipGetLastError());
-        }
-        const hipMemcpyKind okind = dev_out ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
-        if (out_host) ARP_HIP_OK(hipMemcpyAsync(out_host, feat.p, (size_t)np * k.embed * 4, okind, c->stream));
-        if (ms_host) ARP_HIP_OK(hipMemcpyAsync(ms_host, ms.p, (size_t)np * c->txt.layers * Tw * 4, okind, c->stream));
-        ARP_HIP_OK(hipStreamSynchronize(c->stream));
-        return 0;
-    };
-    rc = body();
-    tok.release(); eot.release(); x.release(); h.release(); qkv.release(); ao.release(); fc.release(); hs.release(); ms.release(); feat_tmp.release();
-    if (rc == 0 && !out_host) c->n_prompts = np;
-    return rc;
+    }
+    const hipMemcpyKind okind = dev_out ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
+    if (out_host) ARP_HIP_OK(hipMemcpyAsync(out_host, feat.p, (size_t)np * k.embed * 4, okind, c->stream));
+    if (ms_host) ARP_HIP_OK(hipMemcpyAsync(ms_host, ms.p, (size_t)np * c->txt.layers * Tw * 4, okind, c->stream));
+    ARP_HIP_OK(hipStreamSynchronize(c->stream));
+    if (!out_host) c->n_prompts = np;
+    return 0;
 }
 
 static int check_ready(arp_clip* c, bool need_text) {
@@ -559,22 +536,23 @@ static int check_ready(arp_clip* c, bool need_text) {
 }
 
 static int label_dev_single(arp_clip* c, const uint8_t* frames_dev, int n, int H, int W, int use_crop, float* rewards_dev) {
-    ARP_TRY(check_ready(c, true));
+    arp_clip* o = c->shared();  // the prompt set, its reduction, the plans and the logit scale are the primary's
+    ARP_TRY(check_ready(o, true));
     if (n < 0) return fail("negative frame count");
     if (n == 0) return 0;
     ARP_HIP_OK(hipSetDevice(c->cfg.device));
     ResizePlan* plan;
     const int mb = c->cfg.max_batch;
-    const bool small = !c->is_sibling && n <= mb && (long)n * c->ntok() <= c->lat_rows;  // the rollout loop's call (one frame, or a few)
-    ARP_TRY(get_plan(c, H, W, use_crop, &plan, small));
+    const bool small = !c->primary && n <= mb && (long)n * c->ntok() <= c->lat_rows;  // the rollout loop's call (one frame, or a few)
+    ARP_TRY(get_plan(o, H, W, use_crop, &plan, small));
     ARP_TRY(ensure_workspace(c, std::min(n, mb)));
-    const float scale = expf(c->logit_scale);
+    const float scale = expf(o->logit_scale);
     auto pass = [&](const uint8_t* fr, int nb, float* rw) -> int {
         ARP_TRY(forward_chunk_dispatch(c, fr, nb, plan));
         ProfScope ps(c->prof, c->stream, "reward");
         // mean over prompts of scale <img_n, txt_p> = scale <img_n, mean_p txt_p>: the same kernel on the mean prompt vector
         hipLaunchKernelGGL(reward_kernel, dim3((nb + 3) / 4), dim3(256), 0, c->stream, c->feat.as<float>(),
-                           c->prompt_reduce ? c->txt_mean.as<float>() : c->txt_feat.as<float>(), scale, rw, nb, c->cfg.embed);
+                           o->prompt_reduce ? o->txt_mean.as<float>() : o->txt_feat.as<float>(), scale, rw, nb, c->cfg.embed);
         ARP_HIP_OK(hipGetLastError());
         return 0;
     };
@@ -614,36 +592,15 @@ static int label_dev_single(arp_clip* c, const uint8_t* frames_dev, int n, int H
 }
 
 static int make_sibling(arp_clip* c) {
-    arp_clip* s = new arp_clip(*c);  // shares every weight pointer; owns nothing of them
-    s->is_sibling = true;
-    s->siblings.clear();
-    s->ev_join.clear();
-    s->owned.clear();
-    s->staged.clear();
-    s->prof = Profiler();
+    auto s = std::make_unique<arp_clip>(static_cast<const ClipModel&>(*c));  // shares every weight pointer; owns nothing of them
+    s->primary = c;
     s->prof.on = c->prof.on;
-    s->ws_frames = 0;
-    DevBuf* bufs[] = {&s->patches, &s->pe, &s->x, &s->h, &s->qkv, &s->ao, &s->fc, &s->cls_h, &s->feat, &s->frames_in, &s->rewards, &s->stats};
-    for (auto* b : bufs) *b = DevBuf();
-    s->clock_buf = DevBuf();  // (the primary's; clock_acc is copied per call)
-    s->part = DevBuf();  // the latency path never runs on a sibling (parts of >= 128 frames)
-    s->lat_stats = DevBuf();
-    s->lat_graphs.clear();
-    s->pin_frames = nullptr; s->pin_frames_bytes = 0; s->pin_rewards = nullptr; s->pin_rewards_n = 0;
-    s->stream = nullptr;
-    s->ev_fork = nullptr;
-    s->copy_stream = nullptr;
-    s->ev_copy.clear();
-    for (auto& ls : s->lslot) ls = arp_clip::LabelSlot();
-    if (hipStreamCreateWithFlags(&s->stream, hipStreamNonBlocking) != hipSuccess) {
-        delete s;
-        return fail("hipStreamCreate failed");
-    }
-    if (!c->ev_fork) ARP_HIP_OK(hipEventCreateWithFlags(&c->ev_fork, hipEventDisableTiming));
-    hipEvent_t ej = nullptr;
-    ARP_HIP_OK(hipEventCreateWithFlags(&ej, hipEventDisableTiming));
-    c->ev_join.push_back(ej);
-    c->siblings.push_back(s);
+    ARP_TRY(s->stream.create());
+    if (!c->ev_fork) ARP_TRY(c->ev_fork.create());
+    Event ej;
+    ARP_TRY(ej.create());
+    c->ev_join.push_back(std::move(ej));
+    c->siblings.push_back(std::move(s));
     return 0;
 }
 
@@ -670,29 +627,18 @@ static int label_dev(arp_clip* c, const uint8_t* frames_dev, int n, int H, int W
         parts = env_parts > 0 ? env_parts : ns;
         while (parts > ns && n / parts < 128) --parts;
         if (parts < ns) parts = ns;
-        if (!c->copy_stream) ARP_HIP_OK(hipStreamCreateWithFlags(&c->copy_stream, hipStreamNonBlocking));
+        if (!c->copy_stream) ARP_TRY(c->copy_stream.create());
         while ((int)c->ev_copy.size() < parts + 1) {
-            hipEvent_t e = nullptr;
-            ARP_HIP_OK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-            c->ev_copy.push_back(e);
+            Event e;
+            ARP_TRY(e.create());
+            c->ev_copy.push_back(std::move(e));
         }
     }
     while ((int)c->siblings.size() < ns - 1) ARP_TRY(make_sibling(c));
     ResizePlan* plan;
     ARP_TRY(get_plan(c, H, W, use_crop, &plan));
     ARP_HIP_OK(hipEventRecord(c->ev_fork, c->stream));
-    for (int i = 1; i < ns; ++i) {
-        arp_clip* s = c->siblings[i - 1];
-        s->plans = c->plans;  // shared, owned by the primary
-        s->txt_feat = c->txt_feat;
-        s->txt_mean = c->txt_mean;
-        s->prompt_reduce = c->prompt_reduce;
-        s->n_prompts = c->n_prompts;
-        s->logit_scale = c->logit_scale;
-        s->prof.on = c->prof.on;
-        s->clock_acc = c->clock_acc;
-        ARP_HIP_OK(hipStreamWaitEvent(s->stream, c->ev_fork, 0));
-    }
+    for (int i = 1; i < ns; ++i) ARP_HIP_OK(hipStreamWaitEvent(c->siblings[i - 1]->stream, c->ev_fork, 0));
     // contiguous parts; part i runs on stream i % ns (0 = the primary, k = sibling k-1).
     // lead > 0 (a SYNCHRONOUS host-fed call): a short first part on the primary stream, so that kernels start after lead / n of the upload
     // instead of 1 / parts of it; the remaining frames are cut into `parts` equal parts, the first of them on the first sibling.
@@ -702,7 +648,7 @@ static int label_dev(arp_clip* c, const uint8_t* frames_dev, int n, int H, int W
         const int b0 = i < 0 ? 0 : lead + i * per, nb = i < 0 ? lead : std::min(per, n - b0);
         if (nb <= 0) break;
         const int si = i < 0 ? 0 : (lead ? (i + 1) % ns : i % ns);
-        arp_clip* s = si == 0 ? c : c->siblings[si - 1];
+        arp_clip* s = si == 0 ? c : c->siblings[si - 1].get();
         if (host_src) {
             // (the staging buffer's previous readers -- the last call's kernels -- were synchronised before that call returned)
             ARP_HIP_OK(hipMemcpyAsync(const_cast<uint8_t*>(frames_dev) + (size_t)b0 * fbytes, host_src + (size_t)b0 * fbytes, (size_t)nb * fbytes,
@@ -729,6 +675,12 @@ extern "C" {
 
 const char* arp_last_error(void) { return g_err.c_str(); }
 int arp_version(void) { return 100; }
+
+int arp_debug_live(int64_t out5[5]) {
+    if (!out5) return fail("null out");
+    out5[0] = live.dev_bytes; out5[1] = live.dev_bufs; out5[2] = live.streams; out5[3] = live.events; out5[4] = live.pin_bytes;
+    return 0;
+}
 
 int arp_device_count(void) {
     int n = 0;
@@ -802,7 +754,7 @@ int arp_clip_create(const arp_clip_cfg* cfg, arp_clip** out) {
     if (const char* e = getenv("ARP_CLIP_GRAPH")) c->lat_graph = atoi(e) != 0;
     if (const char* e = getenv("ARP_SKINNY_ROWS")) c->lat_rows = std::min(std::max(atoi(e), 1), SKINNY_MAX_M);
     if (const char* e = getenv("ARP_CLIP_PINNED")) c->lat_pinned = atoi(e) != 0;
-    if (hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking) != hipSuccess) {
+    if (c->stream.create() != 0) {
         delete c;
         return fail("hipStreamCreate failed");
     }
@@ -814,41 +766,8 @@ int arp_clip_destroy(arp_clip* c) {
     if (!c) return 0;
     (void)hipSetDevice(c->cfg.device);
     (void)hipStreamSynchronize(c->stream);
-    for (arp_clip* s : c->siblings) {
-        (void)hipStreamSynchronize(s->stream);
-        s->prof.destroy();
-        DevBuf* sb[] = {&s->patches, &s->pe, &s->x, &s->h, &s->qkv, &s->ao, &s->fc, &s->cls_h, &s->feat, &s->frames_in, &s->rewards, &s->stats};
-        for (auto* b : sb) b->release();
-        (void)hipStreamDestroy(s->stream);
-        s->plans.clear();
-        delete s;
-    }
-    if (c->ev_fork) (void)hipEventDestroy(c->ev_fork);
-    for (hipEvent_t e : c->ev_join) (void)hipEventDestroy(e);
-    for (hipEvent_t e : c->ev_copy) (void)hipEventDestroy(e);
-    if (c->copy_stream) (void)hipStreamDestroy(c->copy_stream);
-    for (auto& ls : c->lslot) {
-        ls.frames.release();
-        ls.rewards.release();
-        if (ls.host) (void)hipHostFree(ls.host);
-        if (ls.done) (void)hipEventDestroy(ls.done);
-    }
-    c->prof.destroy();
+    for (auto& s : c->siblings) (void)hipStreamSynchronize(s->stream);
     drop_lat_graphs(c);
-    c->part.release();
-    c->lat_stats.release();
-    c->clock_buf.release();
-    if (c->pin_frames) (void)hipHostFree(c->pin_frames);
-    if (c->pin_rewards) (void)hipHostFree(c->pin_rewards);
-    for (void* p : c->owned) (void)hipFree(p);
-    for (auto& kv : c->plans) {
-        kv.second->h_tab.release();
-        kv.second->v_tab.release();
-        delete kv.second;
-    }
-    DevBuf* bufs[] = {&c->txt_feat, &c->txt_mean, &c->ms_keep, &c->patches, &c->pe, &c->x, &c->h, &c->qkv, &c->ao, &c->fc, &c->cls_h, &c->feat, &c->frames_in, &c->rewards, &c->stats};
-    for (auto* b : bufs) b->release();
-    (void)hipStreamDestroy(c->stream);
     delete c;
     return 0;
 }
@@ -971,24 +890,18 @@ int arp_clip_label(arp_clip* c, const uint8_t* frames, int n, int H, int W, int 
     const size_t fb = (size_t)H * W * 3;
     const int mb = c->cfg.max_batch;
     if (c->lat_pinned && n <= mb && (long)n * c->ntok() <= c->lat_rows) {
-        if (c->pin_frames_bytes < (size_t)n * fb) {
+        if (c->pin_frames.bytes < (size_t)n * fb) {
             ARP_HIP_OK(hipStreamSynchronize(c->stream));
-            if (c->pin_frames) ARP_HIP_OK(hipHostFree(c->pin_frames));
-            c->pin_frames = nullptr; c->pin_frames_bytes = 0;
-            ARP_HIP_OK(hipHostMalloc(reinterpret_cast<void**>(&c->pin_frames), (size_t)n * fb, hipHostMallocDefault));
-            c->pin_frames_bytes = (size_t)n * fb;
+            ARP_TRY(c->pin_frames.ensure((size_t)n * fb));
         }
-        if (c->pin_rewards_n < (size_t)n) {
+        if (c->pin_rewards.bytes < (size_t)n * 4) {
             ARP_HIP_OK(hipStreamSynchronize(c->stream));
-            if (c->pin_rewards) ARP_HIP_OK(hipHostFree(c->pin_rewards));
-            c->pin_rewards = nullptr; c->pin_rewards_n = 0;
-            ARP_HIP_OK(hipHostMalloc(reinterpret_cast<void**>(&c->pin_rewards), (size_t)std::max(n, 16) * 4, hipHostMallocDefault));
-            c->pin_rewards_n = (size_t)std::max(n, 16);
+            ARP_TRY(c->pin_rewards.ensure((size_t)std::max(n, 16) * 4));
         }
-        memcpy(c->pin_frames, frames, (size_t)n * fb);
-        ARP_TRY(label_dev_single(c, c->pin_frames, n, H, W, use_crop, c->pin_rewards));
+        memcpy(c->pin_frames.p, frames, (size_t)n * fb);
+        ARP_TRY(label_dev_single(c, c->pin_frames.as<uint8_t>(), n, H, W, use_crop, c->pin_rewards.as<float>()));
         ARP_HIP_OK(hipStreamSynchronize(c->stream));
-        memcpy(rewards, c->pin_rewards, (size_t)n * 4);
+        memcpy(rewards, c->pin_rewards.p, (size_t)n * 4);
         return 0;
     }
     ARP_TRY(c->frames_in.ensure((size_t)std::min(n, mb) * fb));
@@ -1018,15 +931,10 @@ int arp_clip_label_submit(arp_clip* c, int slot, const uint8_t* frames, int n, i
     const size_t fb = (size_t)H * W * 3;
     ARP_TRY(ls.frames.ensure((size_t)c->cfg.max_batch * fb));
     ARP_TRY(ls.rewards.ensure((size_t)c->cfg.max_batch * 4));
-    if (ls.host_n < (size_t)c->cfg.max_batch) {
-        if (ls.host) ARP_HIP_OK(hipHostFree(ls.host));
-        ls.host = nullptr;
-        ARP_HIP_OK(hipHostMalloc(reinterpret_cast<void**>(&ls.host), (size_t)c->cfg.max_batch * 4, hipHostMallocDefault));
-        ls.host_n = (size_t)c->cfg.max_batch;
-    }
-    if (!ls.done) ARP_HIP_OK(hipEventCreateWithFlags(&ls.done, hipEventDisableTiming));
+    ARP_TRY(ls.host.ensure((size_t)c->cfg.max_batch * 4));
+    if (!ls.done) ARP_TRY(ls.done.create());
     ARP_TRY(label_dev(c, ls.frames.as<uint8_t>(), n, H, W, use_crop, ls.rewards.as<float>(), frames));
-    ARP_HIP_OK(hipMemcpyAsync(ls.host, ls.rewards.p, (size_t)n * 4, hipMemcpyDeviceToHost, c->stream));
+    ARP_HIP_OK(hipMemcpyAsync(ls.host.p, ls.rewards.p, (size_t)n * 4, hipMemcpyDeviceToHost, c->stream));
     ARP_HIP_OK(hipEventRecord(ls.done, c->stream));
     ls.n = n;
     ls.busy = true;
@@ -1037,7 +945,7 @@ int arp_clip_label_collect(arp_clip* c, int slot, float* rewards) {
     arp_clip::LabelSlot& ls = c->lslot[slot];
     if (!ls.busy) return fail("arp_clip_label_collect: nothing was submitted on this slot");
     ARP_HIP_OK(hipEventSynchronize(ls.done));
-    memcpy(rewards, ls.host, (size_t)ls.n * 4);
+    memcpy(rewards, ls.host.p, (size_t)ls.n * 4);
     ls.busy = false;
     return 0;
 }
@@ -1092,27 +1000,20 @@ static int encode_image_multiscale(arp_clip* c, const uint8_t* frames, int n, in
     const bool keep = (size_t)std::min(n, mb) * LD * 4 <= (1u << 20);  // a few frames: the export buffer stays with the handle
     DevBuf ms_tmp;
     DevBuf& ms = keep ? c->ms_keep : ms_tmp;
-    int rc = 0;
-    auto body = [&]() -> int {
-        ARP_TRY(ms.ensure((size_t)std::min(n, mb) * LD * 4));
-        for (int off = 0; off < n; off += mb) {
-            const int nb = std::min(mb, n - off);
-            ARP_HIP_OK(hipMemcpyAsync(c->frames_in.p, frames + (size_t)off * fb, (size_t)nb * fb, hipMemcpyHostToDevice, c->stream));
-            c->ms_out = ms.as<float>(); c->ms_ld = LD; c->ms_rows = nullptr; c->pre_bilinear = pil_crop < 0 ? ((H << 16) | W) : 0;
-            const int r = forward_chunk_dispatch(c, c->frames_in.as<uint8_t>(), nb, plan);
-            c->ms_out = nullptr; c->pre_bilinear = 0;
-            ARP_TRY(r);
-            const hipMemcpyKind kind = dev_out ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
-            ARP_HIP_OK(hipMemcpyAsync(final_feat + (size_t)off * E, c->feat.p, (size_t)nb * E * 4, kind, c->stream));
-            ARP_HIP_OK(hipMemcpyAsync(inter + (size_t)off * LD, ms.p, (size_t)nb * LD * 4, kind, c->stream));
-            ARP_HIP_OK(hipStreamSynchronize(c->stream));
-        }
-        return 0;
-    };
-    rc = body();
-    c->ms_out = nullptr; c->pre_bilinear = 0;
-    ms_tmp.release();
-    return rc;
+    ARP_TRY(ms.ensure((size_t)std::min(n, mb) * LD * 4));
+    for (int off = 0; off < n; off += mb) {
+        const int nb = std::min(mb, n - off);
+        ARP_HIP_OK(hipMemcpyAsync(c->frames_in.p, frames + (size_t)off * fb, (size_t)nb * fb, hipMemcpyHostToDevice, c->stream));
+        c->ms_out = ms.as<float>(); c->ms_ld = LD; c->ms_rows = nullptr; c->pre_bilinear = pil_crop < 0 ? ((H << 16) | W) : 0;
+        const int r = forward_chunk_dispatch(c, c->frames_in.as<uint8_t>(), nb, plan);
+        c->ms_out = nullptr; c->pre_bilinear = 0;  // (the export target is cleared before anything below can return)
+        ARP_TRY(r);
+        const hipMemcpyKind kind = dev_out ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
+        ARP_HIP_OK(hipMemcpyAsync(final_feat + (size_t)off * E, c->feat.p, (size_t)nb * E * 4, kind, c->stream));
+        ARP_HIP_OK(hipMemcpyAsync(inter + (size_t)off * LD, ms.p, (size_t)nb * LD * 4, kind, c->stream));
+        ARP_HIP_OK(hipStreamSynchronize(c->stream));
+    }
+    return 0;
 }
 
 int arp_clip_encode_image_multiscale(arp_clip* c, const uint8_t* frames, int n, int H, int W, float* inter, float* final_feat) {
@@ -1166,23 +1067,17 @@ int arp_preprocess(const uint8_t* frames, int n, int H, int W, int use_crop, int
     if (!frames || !out) return fail("null buffer");
     ResizePlan plan;
     DevBuf in, o, lut;
-    int rc = 0;
-    auto body = [&]() -> int {
-        ARP_TRY(build_plan(H, W, use_crop, res, plan));
-        const size_t fb = (size_t)H * W * 3, ob = (size_t)3 * res * res * 4;
-        ARP_TRY(in.ensure((size_t)n * fb)); ARP_TRY(o.ensure((size_t)n * ob)); ARP_TRY(lut.ensure(768 * 4));
-        std::vector<float> l(768);
-        build_lut(l.data());
-        ARP_HIP_OK(hipMemcpy(lut.p, l.data(), 768 * 4, hipMemcpyHostToDevice));
-        ARP_HIP_OK(hipMemcpy(in.p, frames, (size_t)n * fb, hipMemcpyHostToDevice));
-        ARP_TRY((launch_preprocess<float, PRE_NCHW>(plan, in.as<uint8_t>(), n, 4, lut.as<float>(), o.p, nullptr)));
-        ARP_HIP_OK(hipDeviceSynchronize());
-        ARP_HIP_OK(hipMemcpy(out, o.p, (size_t)n * ob, hipMemcpyDeviceToHost));
-        return 0;
-    };
-    rc = body();
-    in.release(); o.release(); lut.release(); plan.h_tab.release(); plan.v_tab.release();
-    return rc;
+    ARP_TRY(build_plan(H, W, use_crop, res, plan));
+    const size_t fb = (size_t)H * W * 3, ob = (size_t)3 * res * res * 4;
+    ARP_TRY(in.ensure((size_t)n * fb)); ARP_TRY(o.ensure((size_t)n * ob)); ARP_TRY(lut.ensure(768 * 4));
+    std::vector<float> l(768);
+    build_lut(l.data());
+    ARP_HIP_OK(hipMemcpy(lut.p, l.data(), 768 * 4, hipMemcpyHostToDevice));
+    ARP_HIP_OK(hipMemcpy(in.p, frames, (size_t)n * fb, hipMemcpyHostToDevice));
+    ARP_TRY((launch_preprocess<float, PRE_NCHW>(plan, in.as<uint8_t>(), n, 4, lut.as<float>(), o.p, nullptr)));
+    ARP_HIP_OK(hipDeviceSynchronize());
+    ARP_HIP_OK(hipMemcpy(out, o.p, (size_t)n * ob, hipMemcpyDeviceToHost));
+    return 0;
 }
 
 int arp_clip_set_fp8_mlp(arp_clip* c, int on) {
@@ -1198,7 +1093,7 @@ int arp_clip_set_fp8_mlp(arp_clip* c, int on) {
 int arp_clip_set_streams(arp_clip* c, int n_streams) {
     if (!c || n_streams < 0 || n_streams > 4) return fail("n_streams must be 0..4");
     ARP_HIP_OK(hipStreamSynchronize(c->stream));
-    for (arp_clip* s : c->siblings) ARP_HIP_OK(hipStreamSynchronize(s->stream));
+    for (auto& s : c->siblings) ARP_HIP_OK(hipStreamSynchronize(s->stream));
     c->cfg.n_streams = n_streams;
     return 0;
 }
@@ -1210,7 +1105,7 @@ int arp_clip_clock_probe(arp_clip* c, int on) {
     if (!c) return fail("null handle");
     ARP_HIP_OK(hipSetDevice(c->cfg.device));
     ARP_HIP_OK(hipStreamSynchronize(c->stream));
-    for (arp_clip* s : c->siblings) ARP_HIP_OK(hipStreamSynchronize(s->stream));
+    for (auto& s : c->siblings) ARP_HIP_OK(hipStreamSynchronize(s->stream));
     if (on) {
         ARP_TRY(c->clock_buf.ensure(64));
         ARP_HIP_OK(hipMemset(c->clock_buf.p, 0, 64));
@@ -1218,7 +1113,6 @@ int arp_clip_clock_probe(arp_clip* c, int on) {
     } else {
         c->clock_acc = nullptr;
     }
-    for (arp_clip* s : c->siblings) s->clock_acc = c->clock_acc;
     // (a captured single-frame pass holds the instance it was captured with)
     return 0;
 }
@@ -1229,7 +1123,7 @@ int arp_clip_clock_read(arp_clip* c, double* out) {
     if (!c->clock_buf.p) return fail("arp_clip_clock_probe was never switched on");
     ARP_HIP_OK(hipSetDevice(c->cfg.device));
     ARP_HIP_OK(hipStreamSynchronize(c->stream));
-    for (arp_clip* s : c->siblings) ARP_HIP_OK(hipStreamSynchronize(s->stream));
+    for (auto& s : c->siblings) ARP_HIP_OK(hipStreamSynchronize(s->stream));
     unsigned long long v[3] = {0, 0, 0};
     ARP_HIP_OK(hipMemcpy(v, c->clock_buf.p, sizeof(v), hipMemcpyDeviceToHost));
     out[0] = v[1] ? (double)v[0] / (double)v[1] * 0.1 : 0.0;
@@ -1241,18 +1135,18 @@ int arp_clip_clock_read(arp_clip* c, double* out) {
 int arp_clip_profile_enable(arp_clip* c, int on) {
     if (!c) return fail("null handle");
     c->prof.on = on != 0;
-    for (arp_clip* s : c->siblings) s->prof.on = c->prof.on;
+    for (auto& s : c->siblings) s->prof.on = c->prof.on;
     return 0;
 }
 int arp_clip_profile_reset(arp_clip* c) {
     if (!c) return fail("null handle");
     c->prof.reset();
-    for (arp_clip* s : c->siblings) s->prof.reset();
+    for (auto& s : c->siblings) s->prof.reset();
     return 0;
 }
 int arp_clip_profile_json(arp_clip* c, char* buf, int buf_len) {
     if (!c || !buf) return fail("null argument");
-    for (arp_clip* sb : c->siblings) {  // fold the other streams' launches into the primary's sites
+    for (auto& sb : c->siblings) {  // fold the other streams' launches into the primary's sites
         Profiler& q = sb->prof;
         q.collect();
         c->prof.collect();
@@ -1338,31 +1232,26 @@ template <typename T> static int from_dev(float* dst, size_t n, const DevBuf& d)
 template <typename T> static int op_gemm(int act, const float* A, const float* W, const float* bias, const float* resid, float* out,
                                          int M, int N, int K) {
     DevBuf dA, dW, dB, dR, dO;
-    auto body = [&]() -> int {
-        ARP_TRY(to_dev<T>(A, (size_t)M * K, dA)); ARP_TRY(to_dev<T>(W, (size_t)N * K, dW));
-        if (bias) ARP_TRY(to_dev<float>(bias, N, dB));
-        ARP_TRY(dO.ensure((size_t)M * N * 4));
-        if (resid) ARP_TRY(to_dev<float>(resid, (size_t)M * N, dR));
-        GemmArgs g;
-        g.A = dA.p; g.W = dW.p; g.bias = bias ? dB.as<float>() : nullptr; g.resid = resid ? dR.as<float>() : nullptr; g.out = dO.p;
-        g.M = M; g.N = N; g.K = K; g.lda = K; g.ldw = K; g.ldr = N; g.ldo = N;
-        int rc = -1;
-        const char* fe = getenv("ARP_GEMM");
-        const int force = fe ? atoi(fe) : 0;
+    ARP_TRY(to_dev<T>(A, (size_t)M * K, dA)); ARP_TRY(to_dev<T>(W, (size_t)N * K, dW));
+    if (bias) ARP_TRY(to_dev<float>(bias, N, dB));
+    ARP_TRY(dO.ensure((size_t)M * N * 4));
+    if (resid) ARP_TRY(to_dev<float>(resid, (size_t)M * N, dR));
+    GemmArgs g;
+    g.A = dA.p; g.W = dW.p; g.bias = bias ? dB.as<float>() : nullptr; g.resid = resid ? dR.as<float>() : nullptr; g.out = dO.p;
+    g.M = M; g.N = N; g.K = K; g.lda = K; g.ldw = K; g.ldr = N; g.ldo = N;
+    int rc = -1;
+    const char* fe = getenv("ARP_GEMM");
+    const int force = fe ? atoi(fe) : 0;
 #define ARP_OP_CASE(a)                                                                                            \
-    case a: rc = resid ? launch_gemm_auto<T, float, a, true, SITE_OP>(g, nullptr, force) : launch_gemm_auto<T, float, a, false, SITE_OP>(g, nullptr, force); break;
-        switch (act) {
-            ARP_OP_CASE(ACT_NONE) ARP_OP_CASE(ACT_QGELU) ARP_OP_CASE(ACT_RELU) ARP_OP_CASE(ACT_TANH) ARP_OP_CASE(ACT_GELU_TANH)
-            default: return fail("bad activation");
-        }
+case a: rc = resid ? launch_gemm_auto<T, float, a, true, SITE_OP>(g, nullptr, force) : launch_gemm_auto<T, float, a, false, SITE_OP>(g, nullptr, force); break;
+    switch (act) {
+        ARP_OP_CASE(ACT_NONE) ARP_OP_CASE(ACT_QGELU) ARP_OP_CASE(ACT_RELU) ARP_OP_CASE(ACT_TANH) ARP_OP_CASE(ACT_GELU_TANH)
+        default: return fail("bad activation");
+    }
 #undef ARP_OP_CASE
-        ARP_TRY(rc);
-        ARP_HIP_OK(hipDeviceSynchronize());
-        return from_dev<float>(out, (size_t)M * N, dO);
-    };
-    const int rc = body();
-    dA.release(); dW.release(); dB.release(); dR.release(); dO.release();
-    return rc;
+    ARP_TRY(rc);
+    ARP_HIP_OK(hipDeviceSynchronize());
+    return from_dev<float>(out, (size_t)M * N, dO);
 }
 
 // The latency path's GEMM (skinny.h) on host arrays.  ksplit = 0: one launch with the bias / activation / residual epilogue;
@@ -1371,38 +1260,33 @@ template <typename T> static int op_skinny(int act, const float* A, const float*
                                            int ksplit, const float* ln_w, const float* ln_b, float eps, float* h_out) {
     DevBuf dA, dW, dB, dR, dO, dP, dH, dLw, dLb;
     const int tcode = __is_same(T, bf16_t) ? 1 : 2;
-    auto body = [&]() -> int {
-        ARP_TRY(to_dev<T>(A, (size_t)M * K, dA)); ARP_TRY(to_dev<T>(W, (size_t)N * K, dW));
-        if (bias) ARP_TRY(to_dev<float>(bias, N, dB));
-        SkinnyArgs k;
-        k.A = dA.p; k.W = dW.p; k.M = M; k.N = N; k.K = K; k.lda = K; k.ldw = K; k.ldr = N; k.ldo = N; k.out_f32 = 1;
-        if (ksplit == 0) {
-            ARP_TRY(dO.ensure((size_t)M * N * 4));
-            if (resid) ARP_TRY(to_dev<float>(resid, (size_t)M * N, dR));
-            k.bias = bias ? dB.as<float>() : nullptr; k.resid = resid ? dR.as<float>() : nullptr; k.out = dO.p; k.act = act;
-            ARP_TRY(launch_skinny_gemm(tcode, k, nullptr));
-            ARP_HIP_OK(hipDeviceSynchronize());
-            return from_dev<float>(out, (size_t)M * N, dO);
-        }
-        if (!resid || act != ACT_NONE) return fail("skinny split: needs the residual, takes no activation");
-        ARP_TRY(to_dev<float>(resid, (size_t)M * N, dR));
-        ARP_TRY(dP.ensure((size_t)ksplit * M * N * 4));
-        if (ln_w) {
-            if (!ln_b || !h_out) return fail("skinny split: ln_w needs ln_b and h_out");
-            ARP_TRY(to_dev<float>(ln_w, N, dLw)); ARP_TRY(to_dev<float>(ln_b, N, dLb)); ARP_TRY(dH.ensure((size_t)M * N * sizeof(T)));
-        }
-        k.out = dP.p; k.ksplit = ksplit; k.slice_stride = (size_t)M * N;
+    ARP_TRY(to_dev<T>(A, (size_t)M * K, dA)); ARP_TRY(to_dev<T>(W, (size_t)N * K, dW));
+    if (bias) ARP_TRY(to_dev<float>(bias, N, dB));
+    SkinnyArgs k;
+    k.A = dA.p; k.W = dW.p; k.M = M; k.N = N; k.K = K; k.lda = K; k.ldw = K; k.ldr = N; k.ldo = N; k.out_f32 = 1;
+    if (ksplit == 0) {
+        ARP_TRY(dO.ensure((size_t)M * N * 4));
+        if (resid) ARP_TRY(to_dev<float>(resid, (size_t)M * N, dR));
+        k.bias = bias ? dB.as<float>() : nullptr; k.resid = resid ? dR.as<float>() : nullptr; k.out = dO.p; k.act = act;
         ARP_TRY(launch_skinny_gemm(tcode, k, nullptr));
-        ARP_TRY(launch_skinny_reduce_ln(tcode, dP.as<float>(), ksplit, (size_t)M * N, bias ? dB.as<float>() : nullptr, dR.as<float>(), N, dH.p, N,
-                                        ln_w ? dLw.as<float>() : nullptr, ln_w ? dLb.as<float>() : nullptr, M, N, eps, nullptr));
         ARP_HIP_OK(hipDeviceSynchronize());
-        ARP_TRY(from_dev<float>(out, (size_t)M * N, dR));
-        if (ln_w) ARP_TRY(from_dev<T>(h_out, (size_t)M * N, dH));
-        return 0;
-    };
-    const int rc = body();
-    dA.release(); dW.release(); dB.release(); dR.release(); dO.release(); dP.release(); dH.release(); dLw.release(); dLb.release();
-    return rc;
+        return from_dev<float>(out, (size_t)M * N, dO);
+    }
+    if (!resid || act != ACT_NONE) return fail("skinny split: needs the residual, takes no activation");
+    ARP_TRY(to_dev<float>(resid, (size_t)M * N, dR));
+    ARP_TRY(dP.ensure((size_t)ksplit * M * N * 4));
+    if (ln_w) {
+        if (!ln_b || !h_out) return fail("skinny split: ln_w needs ln_b and h_out");
+        ARP_TRY(to_dev<float>(ln_w, N, dLw)); ARP_TRY(to_dev<float>(ln_b, N, dLb)); ARP_TRY(dH.ensure((size_t)M * N * sizeof(T)));
+    }
+    k.out = dP.p; k.ksplit = ksplit; k.slice_stride = (size_t)M * N;
+    ARP_TRY(launch_skinny_gemm(tcode, k, nullptr));
+    ARP_TRY(launch_skinny_reduce_ln(tcode, dP.as<float>(), ksplit, (size_t)M * N, bias ? dB.as<float>() : nullptr, dR.as<float>(), N, dH.p, N,
+                                    ln_w ? dLw.as<float>() : nullptr, ln_w ? dLb.as<float>() : nullptr, M, N, eps, nullptr));
+    ARP_HIP_OK(hipDeviceSynchronize());
+    ARP_TRY(from_dev<float>(out, (size_t)M * N, dR));
+    if (ln_w) ARP_TRY(from_dev<T>(h_out, (size_t)M * N, dH));
+    return 0;
 }
 
 extern "C" {
@@ -1470,86 +1354,74 @@ int arp_op_gemm_fp8(int act, const float* A, const float* W, const float* bias, 
     if (!A || !W || !out || M <= 0 || N <= 0 || K <= 0 || K % 128 || N % 16) return fail("bad argument (K % 128, N % 16)");
     if (out_fp8 && resid) return fail("fp8 output has no residual epilogue");
     DevBuf dA, dW, dB, dR, dO;
-    auto body = [&]() -> int {
-        std::vector<fp8_t> qa((size_t)M * K), qw((size_t)N * K);
-        for (size_t i = 0; i < qa.size(); ++i) qa[i] = host_f2fp8(A[i]);
-        for (size_t i = 0; i < qw.size(); ++i) qw[i] = host_f2fp8(W[i]);
-        ARP_TRY(dA.ensure(qa.size())); ARP_TRY(dW.ensure(qw.size()));
-        ARP_HIP_OK(hipMemcpy(dA.p, qa.data(), qa.size(), hipMemcpyHostToDevice));
-        ARP_HIP_OK(hipMemcpy(dW.p, qw.data(), qw.size(), hipMemcpyHostToDevice));
-        if (bias) ARP_TRY(to_dev<float>(bias, N, dB));
-        if (resid) ARP_TRY(to_dev<float>(resid, (size_t)M * N, dR));
-        ARP_TRY(dO.ensure((size_t)M * N * 4));
-        GemmArgs g;
-        g.A = dA.p; g.W = dW.p; g.bias = bias ? dB.as<float>() : nullptr; g.resid = resid ? dR.as<float>() : nullptr; g.out = dO.p;
-        g.M = M; g.N = N; g.K = K; g.lda = K; g.ldw = K; g.ldr = N; g.ldo = N; g.alpha = alpha; g.out_scale = out_scale;
-        int rc;
-        if (out_fp8 == 2) {  // f16 output (the in_proj of the fp8 attention projections)
-            if (act != ACT_NONE || resid) return fail("f16 output: no activation, no residual");
-            rc = launch_gemm256_nt<fp8_t, f16_t, ACT_NONE, false, SITE_OP>(g, nullptr);
-            ARP_TRY(rc);
-            ARP_HIP_OK(hipDeviceSynchronize());
-            return from_dev<f16_t>(out, (size_t)M * N, dO);
-        }
-        if (out_fp8) rc = act == ACT_QGELU ? launch_gemm256_nt<fp8_t, fp8_t, ACT_QGELU, false, SITE_OP>(g, nullptr) : launch_gemm256_nt<fp8_t, fp8_t, ACT_NONE, false, SITE_OP>(g, nullptr);
-        else if (act != ACT_NONE) return fail("f32 output: act must be ACT_NONE");
-        else rc = resid ? launch_gemm256_nt<fp8_t, float, ACT_NONE, true, SITE_OP>(g, nullptr) : launch_gemm256_nt<fp8_t, float, ACT_NONE, false, SITE_OP>(g, nullptr);
+    std::vector<fp8_t> qa((size_t)M * K), qw((size_t)N * K);
+    for (size_t i = 0; i < qa.size(); ++i) qa[i] = host_f2fp8(A[i]);
+    for (size_t i = 0; i < qw.size(); ++i) qw[i] = host_f2fp8(W[i]);
+    ARP_TRY(dA.ensure(qa.size())); ARP_TRY(dW.ensure(qw.size()));
+    ARP_HIP_OK(hipMemcpy(dA.p, qa.data(), qa.size(), hipMemcpyHostToDevice));
+    ARP_HIP_OK(hipMemcpy(dW.p, qw.data(), qw.size(), hipMemcpyHostToDevice));
+    if (bias) ARP_TRY(to_dev<float>(bias, N, dB));
+    if (resid) ARP_TRY(to_dev<float>(resid, (size_t)M * N, dR));
+    ARP_TRY(dO.ensure((size_t)M * N * 4));
+    GemmArgs g;
+    g.A = dA.p; g.W = dW.p; g.bias = bias ? dB.as<float>() : nullptr; g.resid = resid ? dR.as<float>() : nullptr; g.out = dO.p;
+    g.M = M; g.N = N; g.K = K; g.lda = K; g.ldw = K; g.ldr = N; g.ldo = N; g.alpha = alpha; g.out_scale = out_scale;
+    int rc;
+    if (out_fp8 == 2) {  // f16 output (the in_proj of the fp8 attention projections)
+        if (act != ACT_NONE || resid) return fail("f16 output: no activation, no residual");
+        rc = launch_gemm256_nt<fp8_t, f16_t, ACT_NONE, false, SITE_OP>(g, nullptr);
         ARP_TRY(rc);
         ARP_HIP_OK(hipDeviceSynchronize());
-        if (out_fp8) {
-            std::vector<uint8_t> hb((size_t)M * N);
-            ARP_HIP_OK(hipMemcpy(hb.data(), dO.p, hb.size(), hipMemcpyDeviceToHost));
-            for (size_t i = 0; i < hb.size(); ++i) out[i] = host_fp82f(hb[i]);
-            return 0;
-        }
-        return from_dev<float>(out, (size_t)M * N, dO);
-    };
-    const int rc = body();
-    dA.release(); dW.release(); dB.release(); dR.release(); dO.release();
-    return rc;
+        return from_dev<f16_t>(out, (size_t)M * N, dO);
+    }
+    if (out_fp8) rc = act == ACT_QGELU ? launch_gemm256_nt<fp8_t, fp8_t, ACT_QGELU, false, SITE_OP>(g, nullptr) : launch_gemm256_nt<fp8_t, fp8_t, ACT_NONE, false, SITE_OP>(g, nullptr);
+    else if (act != ACT_NONE) return fail("f32 output: act must be ACT_NONE");
+    else rc = resid ? launch_gemm256_nt<fp8_t, float, ACT_NONE, true, SITE_OP>(g, nullptr) : launch_gemm256_nt<fp8_t, float, ACT_NONE, false, SITE_OP>(g, nullptr);
+    ARP_TRY(rc);
+    ARP_HIP_OK(hipDeviceSynchronize());
+    if (out_fp8) {
+        std::vector<uint8_t> hb((size_t)M * N);
+        ARP_HIP_OK(hipMemcpy(hb.data(), dO.p, hb.size(), hipMemcpyDeviceToHost));
+        for (size_t i = 0; i < hb.size(); ++i) out[i] = host_fp82f(hb[i]);
+        return 0;
+    }
+    return from_dev<float>(out, (size_t)M * N, dO);
 }
 
 }  // extern "C"
 
 template <typename T> static int op_gemm_bench(int kernel, int act, int resid, int out_f32, int M, int N, int K, int iters, float* avg_ms) {
     DevBuf dA, dW, dB, dR, dO;
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    auto body = [&]() -> int {
-        std::vector<float> hA((size_t)M * K), hW((size_t)N * K), hb(N);
-        uint32_t s = 12345u;
-        auto rnd = [&]() { s = s * 1664525u + 1013904223u; return ((s >> 8) & 0xffff) / 32768.0f - 1.0f; };
-        for (auto& v : hA) v = rnd();
-        for (auto& v : hW) v = rnd() * 0.05f;
-        for (auto& v : hb) v = rnd();
-        ARP_TRY(to_dev<T>(hA.data(), hA.size(), dA)); ARP_TRY(to_dev<T>(hW.data(), hW.size(), dW)); ARP_TRY(to_dev<float>(hb.data(), N, dB));
-        ARP_TRY(dO.ensure((size_t)M * N * 4)); ARP_TRY(dR.ensure((size_t)M * N * 4));
-        ARP_HIP_OK(hipMemset(dR.p, 0, (size_t)M * N * 4));
-        GemmArgs g;
-        g.A = dA.p; g.W = dW.p; g.bias = dB.as<float>(); g.resid = resid ? dR.as<float>() : nullptr; g.out = resid ? dR.p : dO.p;
-        g.M = M; g.N = N; g.K = K; g.lda = K; g.ldw = K; g.ldr = N; g.ldo = N;
-        if (const char* fe = getenv("ARP_GEMM_GROUP_M")) g.group_m = atoi(fe);
-        auto run = [&]() -> int {
-            if (resid) return launch_gemm_auto<T, float, ACT_NONE, true, SITE_OP>(g, nullptr, kernel);
-            if (out_f32) return launch_gemm_auto<T, float, ACT_NONE, false, SITE_OP>(g, nullptr, kernel);
-            if (act == ACT_QGELU) return launch_gemm_auto<T, T, ACT_QGELU, false, SITE_OP>(g, nullptr, kernel);
-            return launch_gemm_auto<T, T, ACT_NONE, false, SITE_OP>(g, nullptr, kernel);
-        };
-        ARP_HIP_OK(hipEventCreate(&e0)); ARP_HIP_OK(hipEventCreate(&e1));
-        for (int i = 0; i < 3; ++i) ARP_TRY(run());
-        ARP_HIP_OK(hipEventRecord(e0, nullptr));
-        for (int i = 0; i < iters; ++i) ARP_TRY(run());
-        ARP_HIP_OK(hipEventRecord(e1, nullptr));
-        ARP_HIP_OK(hipEventSynchronize(e1));
-        float ms = 0.f;
-        ARP_HIP_OK(hipEventElapsedTime(&ms, e0, e1));
-        *avg_ms = ms / iters;
-        return 0;
+    Event e0, e1;
+    std::vector<float> hA((size_t)M * K), hW((size_t)N * K), hb(N);
+    uint32_t s = 12345u;
+    auto rnd = [&]() { s = s * 1664525u + 1013904223u; return ((s >> 8) & 0xffff) / 32768.0f - 1.0f; };
+    for (auto& v : hA) v = rnd();
+    for (auto& v : hW) v = rnd() * 0.05f;
+    for (auto& v : hb) v = rnd();
+    ARP_TRY(to_dev<T>(hA.data(), hA.size(), dA)); ARP_TRY(to_dev<T>(hW.data(), hW.size(), dW)); ARP_TRY(to_dev<float>(hb.data(), N, dB));
+    ARP_TRY(dO.ensure((size_t)M * N * 4)); ARP_TRY(dR.ensure((size_t)M * N * 4));
+    ARP_HIP_OK(hipMemset(dR.p, 0, (size_t)M * N * 4));
+    GemmArgs g;
+    g.A = dA.p; g.W = dW.p; g.bias = dB.as<float>(); g.resid = resid ? dR.as<float>() : nullptr; g.out = resid ? dR.p : dO.p;
+    g.M = M; g.N = N; g.K = K; g.lda = K; g.ldw = K; g.ldr = N; g.ldo = N;
+    if (const char* fe = getenv("ARP_GEMM_GROUP_M")) g.group_m = atoi(fe);
+    auto run = [&]() -> int {
+        if (resid) return launch_gemm_auto<T, float, ACT_NONE, true, SITE_OP>(g, nullptr, kernel);
+        if (out_f32) return launch_gemm_auto<T, float, ACT_NONE, false, SITE_OP>(g, nullptr, kernel);
+        if (act == ACT_QGELU) return launch_gemm_auto<T, T, ACT_QGELU, false, SITE_OP>(g, nullptr, kernel);
+        return launch_gemm_auto<T, T, ACT_NONE, false, SITE_OP>(g, nullptr, kernel);
     };
-    const int rc = body();
-    if (e0) (void)hipEventDestroy(e0);
-    if (e1) (void)hipEventDestroy(e1);
-    dA.release(); dW.release(); dB.release(); dR.release(); dO.release();
-    return rc;
+    ARP_TRY(e0.create(hipEventDefault)); ARP_TRY(e1.create(hipEventDefault));
+    for (int i = 0; i < 3; ++i) ARP_TRY(run());
+    ARP_HIP_OK(hipEventRecord(e0, nullptr));
+    for (int i = 0; i < iters; ++i) ARP_TRY(run());
+    ARP_HIP_OK(hipEventRecord(e1, nullptr));
+    ARP_HIP_OK(hipEventSynchronize(e1));
+    float ms = 0.f;
+    ARP_HIP_OK(hipEventElapsedTime(&ms, e0, e1));
+    *avg_ms = ms / iters;
+    return 0;
 }
 
 extern "C" {
@@ -1565,37 +1437,27 @@ int arp_op_layernorm(const float* x, const float* w, const float* b, float* out,
     if (!x || !w || !b || !out || rows <= 0 || D <= 0) return fail("bad argument");
     if (D % 4 || D > ROW_MAX_V4 * 256) return fail("layernorm: unsupported width");
     DevBuf dx, dw, db, dout;
-    auto body = [&]() -> int {
-        ARP_TRY(to_dev<float>(x, (size_t)rows * D, dx)); ARP_TRY(to_dev<float>(w, D, dw)); ARP_TRY(to_dev<float>(b, D, db));
-        ARP_TRY(dout.ensure((size_t)rows * D * 4));
+    ARP_TRY(to_dev<float>(x, (size_t)rows * D, dx)); ARP_TRY(to_dev<float>(w, D, dw)); ARP_TRY(to_dev<float>(b, D, db));
+    ARP_TRY(dout.ensure((size_t)rows * D * 4));
 #define ARP_LN_CALL(NV)                                                                                                  \
-    hipLaunchKernelGGL((layernorm_kernel<float, NV>), dim3((rows + 3) / 4), dim3(256), 0, nullptr, dx.as<float>(), (size_t)D, \
-                       dout.as<float>(), D, dw.as<float>(), db.as<float>(), rows, D, eps)
-        ARP_NV_DISPATCH(D, ARP_LN_CALL);
+hipLaunchKernelGGL((layernorm_kernel<float, NV>), dim3((rows + 3) / 4), dim3(256), 0, nullptr, dx.as<float>(), (size_t)D, \
+                   dout.as<float>(), D, dw.as<float>(), db.as<float>(), rows, D, eps)
+    ARP_NV_DISPATCH(D, ARP_LN_CALL);
 #undef ARP_LN_CALL
-        ARP_HIP_OK(hipGetLastError());
-        ARP_HIP_OK(hipDeviceSynchronize());
-        return from_dev<float>(out, (size_t)rows * D, dout);
-    };
-    const int rc = body();
-    dx.release(); dw.release(); db.release(); dout.release();
-    return rc;
+    ARP_HIP_OK(hipGetLastError());
+    ARP_HIP_OK(hipDeviceSynchronize());
+    return from_dev<float>(out, (size_t)rows * D, dout);
 }
 
 }  // extern "C"
 
 template <typename T> static int op_attn(int impl, const float* qkv, float* out, int B, int N, int D, int heads, int causal) {
     DevBuf dq, dout;
-    auto body = [&]() -> int {
-        ARP_TRY(to_dev<T>(qkv, (size_t)B * N * 3 * D, dq));
-        ARP_TRY(dout.ensure((size_t)B * N * D * sizeof(T)));
-        ARP_TRY(launch_attention<T>(nullptr, impl, dq.as<T>(), dout.as<T>(), B, N, D, heads, causal));
-        ARP_HIP_OK(hipDeviceSynchronize());
-        return from_dev<T>(out, (size_t)B * N * D, dout);
-    };
-    const int rc = body();
-    dq.release(); dout.release();
-    return rc;
+    ARP_TRY(to_dev<T>(qkv, (size_t)B * N * 3 * D, dq));
+    ARP_TRY(dout.ensure((size_t)B * N * D * sizeof(T)));
+    ARP_TRY(launch_attention<T>(nullptr, impl, dq.as<T>(), dout.as<T>(), B, N, D, heads, causal));
+    ARP_HIP_OK(hipDeviceSynchronize());
+    return from_dev<T>(out, (size_t)B * N * D, dout);
 }
 
 extern "C" {
@@ -1623,30 +1485,25 @@ static int op_attn_forms(int impl, const float* qkv, uint8_t* out, size_t out_by
     else return fail("attention_forms: this output form does not exist in this mode (e4m3: 16-bit modes and a scale; [hi | x4 | dx4]: f16 and outc 1, 2, 5 or 6; (hi, lo, hi): f32)");
     if (out_bytes < rows * row_bytes) return fail("attention_forms: output buffer shorter than B * N rows");
     DevBuf dq, dout;
-    auto body = [&]() -> int {
-        const float* src = qkv;
-        std::vector<float> permuted;
-        if (form == ARP_ATTN_OUT_F16C && (outc & 3) == 2) {
-            if (attn_vperm_applies(N, D / heads)) {  // what the encoder's weight loader does to in_proj's V columns (arp_enc.hip)
-                permuted.resize(rows * ld);
-                for (size_t r = 0; r < rows; ++r)
-                    for (int o = 0; o < 3 * D; ++o) permuted[r * ld + o] = qkv[r * ld + attn_vperm_col(o, D)];
-                src = permuted.data();
-            } else {
-                outc = (outc & 4) | 1;
-            }
+    const float* src = qkv;
+    std::vector<float> permuted;
+    if (form == ARP_ATTN_OUT_F16C && (outc & 3) == 2) {
+        if (attn_vperm_applies(N, D / heads)) {  // what the encoder's weight loader does to in_proj's V columns (arp_enc.hip)
+            permuted.resize(rows * ld);
+            for (size_t r = 0; r < rows; ++r)
+                for (int o = 0; o < 3 * D; ++o) permuted[r * ld + o] = qkv[r * ld + attn_vperm_col(o, D)];
+            src = permuted.data();
+        } else {
+            outc = (outc & 4) | 1;
         }
-        ARP_TRY(to_dev<T>(src, rows * ld, dq));
-        ARP_TRY(dout.ensure(std::max<size_t>(out_bytes, 16)));
-        ARP_HIP_OK(hipMemcpy(dout.p, out, out_bytes, hipMemcpyHostToDevice));
-        const int rc = launch_attention<T>(nullptr, impl, dq.as<T>(), dout.as<T>(), B, N, D, heads, causal, nq, form == ARP_ATTN_OUT_E4M3 ? out_scale : 0.f,
-                                           form == ARP_ATTN_OUT_SPLIT3 ? dout.as<f16_t>() : nullptr, form == ARP_ATTN_OUT_F16C ? outc : 0);
-        ARP_HIP_OK(hipDeviceSynchronize());
-        ARP_HIP_OK(hipMemcpy(out, dout.p, out_bytes, hipMemcpyDeviceToHost));
-        return rc;
-    };
-    const int rc = body();
-    dq.release(); dout.release();
+    }
+    ARP_TRY(to_dev<T>(src, rows * ld, dq));
+    ARP_TRY(dout.ensure(std::max<size_t>(out_bytes, 16)));
+    ARP_HIP_OK(hipMemcpy(dout.p, out, out_bytes, hipMemcpyHostToDevice));
+    const int rc = launch_attention<T>(nullptr, impl, dq.as<T>(), dout.as<T>(), B, N, D, heads, causal, nq, form == ARP_ATTN_OUT_E4M3 ? out_scale : 0.f,
+                                       form == ARP_ATTN_OUT_SPLIT3 ? dout.as<f16_t>() : nullptr, form == ARP_ATTN_OUT_F16C ? outc : 0);
+    ARP_HIP_OK(hipDeviceSynchronize());
+    ARP_HIP_OK(hipMemcpy(out, dout.p, out_bytes, hipMemcpyDeviceToHost));
     return rc;
 }
 
@@ -1656,22 +1513,17 @@ static int op_qkv_attn(const float* A, const float* W, const float* bias, uint8_
     const size_t rows = (size_t)B * N;
     if (out_bytes < rows * D * sizeof(T)) return fail("qkv_attention: output buffer shorter than B * N rows");
     DevBuf dA, dW, dB, dout;
-    auto body = [&]() -> int {
-        std::vector<float> wp((size_t)3 * D * K), bp((size_t)3 * D);
-        qkv_head_major(W, bias, K, heads, wp.data(), bp.data());
-        ARP_TRY(to_dev<T>(A, rows * K, dA)); ARP_TRY(to_dev<T>(wp.data(), wp.size(), dW)); ARP_TRY(to_dev<float>(bp.data(), bp.size(), dB));
-        ARP_TRY(dout.ensure(std::max<size_t>(out_bytes, 16)));
-        ARP_HIP_OK(hipMemcpy(dout.p, out, out_bytes, hipMemcpyHostToDevice));
-        QkvAttnArgs q;
-        q.A = dA.p; q.W = dW.p; q.bias = dB.as<float>(); q.out = dout.p;
-        q.B = B; q.N = N; q.K = K; q.heads = heads; q.lda = K; q.ldw = K; q.ldo = D; q.fpt = 0; q.nq = nq; q.causal = causal; q.scale = 0.f;
-        const int rc = launch_qkv_attn<T>(q, nullptr);
-        ARP_HIP_OK(hipDeviceSynchronize());
-        ARP_HIP_OK(hipMemcpy(out, dout.p, out_bytes, hipMemcpyDeviceToHost));
-        return rc;
-    };
-    const int rc = body();
-    dA.release(); dW.release(); dB.release(); dout.release();
+    std::vector<float> wp((size_t)3 * D * K), bp((size_t)3 * D);
+    qkv_head_major(W, bias, K, heads, wp.data(), bp.data());
+    ARP_TRY(to_dev<T>(A, rows * K, dA)); ARP_TRY(to_dev<T>(wp.data(), wp.size(), dW)); ARP_TRY(to_dev<float>(bp.data(), bp.size(), dB));
+    ARP_TRY(dout.ensure(std::max<size_t>(out_bytes, 16)));
+    ARP_HIP_OK(hipMemcpy(dout.p, out, out_bytes, hipMemcpyHostToDevice));
+    QkvAttnArgs q;
+    q.A = dA.p; q.W = dW.p; q.bias = dB.as<float>(); q.out = dout.p;
+    q.B = B; q.N = N; q.K = K; q.heads = heads; q.lda = K; q.ldw = K; q.ldo = D; q.fpt = 0; q.nq = nq; q.causal = causal; q.scale = 0.f;
+    const int rc = launch_qkv_attn<T>(q, nullptr);
+    ARP_HIP_OK(hipDeviceSynchronize());
+    ARP_HIP_OK(hipMemcpy(out, dout.p, out_bytes, hipMemcpyDeviceToHost));
     return rc;
 }
 

@@ -27,6 +27,7 @@ struct arp_ds {
     int n_actions = 0, tokens = 0, dim = 0;
     size_t enc_row() const { return (size_t)tokens * dim; }
 };
+static_assert(!std::is_copy_constructible_v<arp_ds>);
 
 namespace {
 
@@ -188,7 +189,6 @@ int arp_ds_destroy(arp_ds* d) {
     if (!d) return 0;
     (void)hipSetDevice(d->device);
     (void)hipDeviceSynchronize();  // (a gather of a policy handle may still be reading)
-    for (DevBuf* b : {&d->frames, &d->action, &d->rtg, &d->start, &d->lut, &d->enc, &d->iota}) b->release();
     delete d;
     return 0;
 }
@@ -280,25 +280,18 @@ int arp_ds_encode(arp_ds* d, arp_enc* enc, int chunk) {
         ARP_HIP_OK(hipMemcpy(d->iota.p, h.data(), (size_t)d->n_rows * 4, hipMemcpyHostToDevice));
     }
     DevBuf scratch;
-    hipStream_t st = nullptr;  // a stream for the duration of this call (load time: no step runs beside it)
-    auto body = [&]() -> int {
-        ARP_TRY(scratch.ensure((size_t)chunk * d->fb * 4));
-        ARP_HIP_OK(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
-        int rc = 0;
-        for (int r0 = 0; r0 < d->n_rows && !rc; r0 += chunk) {
-            const int nb = std::min(chunk, d->n_rows - r0);
-            rc = gather_impl(d, st, d->iota.as<int32_t>() + r0, nullptr, nb, 1, scratch.as<float>(), nullptr, nullptr, nullptr);
-            if (!rc) rc = enc_forward_on(enc, st, scratch.as<float>(), nb, d->enc.as<float>() + (size_t)r0 * d->enc_row());
-        }
-        const hipError_t e = hipStreamSynchronize(st);  // (after a failure too: nothing may still read the scratch buffer when it is freed)
-        if (rc) return rc;
-        ARP_HIP_OK(e);
-        return 0;
-    };
-    const int rc = body();
-    if (st) (void)hipStreamDestroy(st);
-    scratch.release();
+    Stream st;  // a stream for the duration of this call (load time: no step runs beside it)
+    ARP_TRY(scratch.ensure((size_t)chunk * d->fb * 4));
+    ARP_TRY(st.create());
+    int rc = 0;
+    for (int r0 = 0; r0 < d->n_rows && !rc; r0 += chunk) {
+        const int nb = std::min(chunk, d->n_rows - r0);
+        rc = gather_impl(d, st, d->iota.as<int32_t>() + r0, nullptr, nb, 1, scratch.as<float>(), nullptr, nullptr, nullptr);
+        if (!rc) rc = enc_forward_on(enc, st, scratch.as<float>(), nb, d->enc.as<float>() + (size_t)r0 * d->enc_row());
+    }
+    const hipError_t e = hipStreamSynchronize(st);  // (after a failure too: nothing may still read the scratch buffer when it is freed)
     if (rc) return rc;
+    ARP_HIP_OK(e);
     d->enc_up.assign(d->n_rows, 1);
     d->n_enc_up = d->n_rows;
     return 0;
@@ -312,23 +305,17 @@ int arp_ds_gather_debug(arp_ds* d, const int64_t* idx, int B, int window, float*
     ARP_HIP_OK(hipSetDevice(d->device));
     const size_t n = (size_t)B * window;
     std::vector<int32_t> h(idx, idx + B);
-    DevBuf di, df, da, dr;
-    auto body = [&]() -> int {
-        ARP_TRY(di.ensure((size_t)B * 4));
-        if (frames_out) ARP_TRY(df.ensure(n * d->fb * 4));
-        if (action_out) ARP_TRY(da.ensure(n * 4));
-        if (rtg_out) ARP_TRY(dr.ensure(n * 4));
-        ARP_HIP_OK(hipMemcpy(di.p, h.data(), (size_t)B * 4, hipMemcpyHostToDevice));
-        ARP_TRY(ds_gather_on(d, nullptr, di.as<int32_t>(), B, window, df.as<float>(), nullptr, da.as<int32_t>(), dr.as<float>()));
-        if (frames_out) ARP_HIP_OK(hipMemcpy(frames_out, df.p, n * d->fb * 4, hipMemcpyDeviceToHost));
-        if (action_out) ARP_HIP_OK(hipMemcpy(action_out, da.p, n * 4, hipMemcpyDeviceToHost));
-        if (rtg_out) ARP_HIP_OK(hipMemcpy(rtg_out, dr.p, n * 4, hipMemcpyDeviceToHost));
-        return 0;
-    };
-    const int rc = body();
-    (void)hipDeviceSynchronize();
-    for (DevBuf* b : {&di, &df, &da, &dr}) b->release();
-    return rc;
+    DevBuf di, df, da, dr;  // (freed on every return; hipFree waits for the gather)
+    ARP_TRY(di.ensure((size_t)B * 4));
+    if (frames_out) ARP_TRY(df.ensure(n * d->fb * 4));
+    if (action_out) ARP_TRY(da.ensure(n * 4));
+    if (rtg_out) ARP_TRY(dr.ensure(n * 4));
+    ARP_HIP_OK(hipMemcpy(di.p, h.data(), (size_t)B * 4, hipMemcpyHostToDevice));
+    ARP_TRY(ds_gather_on(d, nullptr, di.as<int32_t>(), B, window, df.as<float>(), nullptr, da.as<int32_t>(), dr.as<float>()));
+    if (frames_out) ARP_HIP_OK(hipMemcpy(frames_out, df.p, n * d->fb * 4, hipMemcpyDeviceToHost));
+    if (action_out) ARP_HIP_OK(hipMemcpy(action_out, da.p, n * 4, hipMemcpyDeviceToHost));
+    if (rtg_out) ARP_HIP_OK(hipMemcpy(rtg_out, dr.p, n * 4, hipMemcpyDeviceToHost));
+    return 0;
 }
 
 // HBM the dataset holds, in bytes

@@ -48,7 +48,7 @@ inline int cdiv(size_t a, size_t b) { return (int)((a + b - 1) / b); }
 
 struct arp_dt {
     arp_dt_cfg cfg;
-    hipStream_t stream = nullptr;
+    Stream stream;
     std::mutex capture_mu;  // graph capture on the compute thread vs the uploader thread's HIP calls (fwd_bwd_graphed / upload_async)
     std::vector<ParamInfo> infos;
     std::map<std::string, int> index;
@@ -80,23 +80,22 @@ struct arp_dt {
         DevBuf img32;             // raw frames [B*T, res, res, 3] f32 when the encoder is attached
         int B = 0;
         bool images = false;
-        hipEvent_t up = nullptr;   // recorded on the copy stream behind the slot's upload
-        hipEvent_t use = nullptr;  // recorded on the compute stream behind the last step that read the slot
+        Event up;   // recorded on the copy stream behind the slot's upload
+        Event use;  // recorded on the compute stream behind the last step that read the slot
         bool up_pending = false, used = false;
-        hipEvent_t enc_done = nullptr;  // recorded on the encoder stream behind the encoder pass that filled enc32 from img32
+        Event enc_done;  // recorded on the encoder stream behind the encoder pass that filled enc32 from img32
         bool up_recorded = false;       // `up` has been recorded at least once (a slot the prefetcher has used)
         bool enc_ahead = false;         // enc32 holds (or will hold, behind enc_done) the encodings of the frames now in img32: the step does not encode again
         // a batch named by row indices of a device-resident dataset (arp_dt_upload_batch_indices_async): the indices go through idx_pin, a small pinned
         // staging buffer of the handle's, into idx, and gather kernels on the upload's stream fill the buffers above
         DevBuf idx;
-        int32_t* idx_pin = nullptr;
-        int idx_cap = 0;
+        PinBuf idx_pin;
     } bt[3];  // 0 / 1: the prefetcher's slots (arp_dt_upload_batch*_async); 2: the synchronous arp_dt_set_batch* calls -- a validation
               // step or a greedy action in between prefetched train steps must not write into a slot the uploader thread may be filling
     int cur = 2;
-    // one copy stream per slot; an upload waits on the HOST for the slot's last reader (upload_async) and then runs on a stream with
+    // the prefetcher's copy stream; an upload waits on the HOST for the slot's last reader (upload_async) and then runs on a stream with
     // nothing else queued, beside the step on the other slot
-    hipStream_t copy_stream[2] = {nullptr, nullptr};
+    Stream copy_stream;
     arp_enc* enc = nullptr;   // optional frozen encoder in front (row N1)
     bool use_images = false;
     // The encoder's part streams fork and join around ~150 long kernels: replayed as parallel branches of the step's hipGraph that costs more than it overlaps
@@ -109,8 +108,8 @@ struct arp_dt {
     // slot's enc_done event: arp_dt_encode_ahead(slot) lets batch i + 1 be encoded WHILE step i's policy part (19 short, partly HBM-bound launches, one of them
     // on 32 of 256 CUs) runs -- what prefetch_to_device's uploader thread calls once a batch of frames has landed.  All passes share the encoder's
     // workspace and are serialised on that one stream.
-    hipStream_t enc_stream = nullptr;
-    hipEvent_t ev_enc_go = nullptr;
+    Stream enc_stream;
+    Event ev_enc_go;
     // activations (T = operand type)
     DevBuf Xb, XbT, H1, H1T, A, Y, YT, dY, dApre, dApreT, G, dH1T, dzb, dzT, part, scal;
     // f32 small tensors
@@ -156,8 +155,8 @@ struct arp_dt {
     bool has_comm = false;
     // data-parallel step: gradient all-reduce in two buckets on a communication stream, bucket 1 (image_text_input's kernel, 94 % of
     // the bytes, + everything the transformer produced) launched while the adapter's backward GEMMs still run (step_impl)
-    hipStream_t comm_stream = nullptr;
-    hipEvent_t ev_b1 = nullptr, ev_b2 = nullptr, ev_comm = nullptr;
+    Stream comm_stream;
+    Event ev_b1, ev_b2, ev_comm;
     bool dzb_from_pf = false;
     bool defer_w2t = false, w2t_pending = false;  // forward<T>'s merged prologue launch (dt_prologue_kernel)
     bool overlap_comm = true;   // ARP_DT_OVERLAP=0: the serial form (one all-reduce after the whole backward), for A/B and the bit-identity test
@@ -211,6 +210,7 @@ struct arp_dt {
     float* p(const std::string& n) { return params.as<float>() + infos[index.at(n)].off; }
     float* g(const std::string& n) { return grads.as<float>() + infos[index.at(n)].off; }
 };
+static_assert(!std::is_copy_constructible_v<arp_dt>);
 
 namespace {
 
@@ -681,9 +681,9 @@ int policy_fused(arp_dt* c, bool do_bwd) {
 int enqueue_encode(arp_dt* c, int slot, bool after_compute) {
     arp_dt::BatchSlot& b = c->bt[slot];
     if (!c->enc || !b.images || b.B <= 0) return fail("encode: the slot holds no frames (or no encoder is attached)");
-    if (!c->enc_stream) ARP_HIP_OK(hipStreamCreateWithFlags(&c->enc_stream, hipStreamNonBlocking));
-    if (!c->ev_enc_go) ARP_HIP_OK(hipEventCreateWithFlags(&c->ev_enc_go, hipEventDisableTiming));
-    if (!b.enc_done) ARP_HIP_OK(hipEventCreateWithFlags(&b.enc_done, hipEventDisableTiming));
+    if (!c->enc_stream) ARP_TRY(c->enc_stream.create());
+    if (!c->ev_enc_go) ARP_TRY(c->ev_enc_go.create());
+    if (!b.enc_done) ARP_TRY(b.enc_done.create());
     if (after_compute) {
         ARP_HIP_OK(hipEventRecord(c->ev_enc_go, c->stream));
         ARP_HIP_OK(hipStreamWaitEvent(c->enc_stream, c->ev_enc_go, 0));
@@ -1367,7 +1367,7 @@ template <typename T> int step_impl(arp_dt* c, float lr, float* aux) {
         // 2 (the adapter's backward: the fused dY pass and three 768 x 768 x 32 896 GEMMs, ~0.25 ms) still runs -> bucket 2 + the
         // loss scalars -> the update waits for both.
         const BucketPlan b = bucket_plan(c);
-        if (!c->comm_stream) ARP_HIP_OK(hipStreamCreateWithFlags(&c->comm_stream, hipStreamNonBlocking));
+        if (!c->comm_stream) ARP_TRY(c->comm_stream.create());
         ARP_TRY(fwd_bwd_graphed<T>(c, 1));
         ARP_HIP_OK(hipEventRecord(c->ev_b1, c->stream));
         ARP_HIP_OK(hipStreamWaitEvent(c->comm_stream, c->ev_b1, 0));
@@ -1466,9 +1466,9 @@ int arp_dt_create(const arp_dt_cfg* cfg, arp_dt** out) {
         // one after the other.  Round 6 measured what that costs: with the encoder's stream added this handle + its encoder held nine streams, the encoder's two
         // part streams shared a queue, and the step went 10.6 -> 12.4 ms (profiles/r6_n1_ab_queues.txt).  Only the compute stream exists from the start; the
         // communication and copy streams are created by the first call that needs them (stream_or_create).
-        ARP_HIP_OK(hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking));
-        for (hipEvent_t* e : {&c->ev_b1, &c->ev_b2, &c->ev_comm, &c->bt[0].up, &c->bt[0].use, &c->bt[1].up, &c->bt[1].use, &c->bt[2].up, &c->bt[2].use})
-            ARP_HIP_OK(hipEventCreateWithFlags(e, hipEventDisableTiming));
+        ARP_TRY(c->stream.create());
+        for (Event* e : {&c->ev_b1, &c->ev_b2, &c->ev_comm, &c->bt[0].up, &c->bt[0].use, &c->bt[1].up, &c->bt[1].use, &c->bt[2].up, &c->bt[2].use})
+            ARP_TRY(e->create());
         DevBuf* fb[] = {&c->params, &c->grads, &c->mu, &c->nu};
         for (auto* b : fb) {
             ARP_TRY(b->ensure(c->P * 4));
@@ -1495,33 +1495,12 @@ int arp_dt_create(const arp_dt_cfg* cfg, arp_dt** out) {
 int arp_dt_destroy(arp_dt* c) {
     if (!c) return 0;
     (void)hipSetDevice(c->cfg.device);
-    for (hipStream_t st : {c->stream, c->comm_stream, c->copy_stream[0], c->copy_stream[1], c->enc_stream})  // (an encode-ahead pass may still be in flight)
+    for (hipStream_t st : {c->stream.s, c->comm_stream.s, c->copy_stream.s, c->enc_stream.s})  // (an encode-ahead pass may still be in flight)
         if (st) (void)hipStreamSynchronize(st);
     for (auto& slot : c->graphs)
         for (auto& gr : slot)
             if (gr.exec) (void)hipGraphExecDestroy(gr.exec);
     if (c->has_comm && rccl_api()) (void)rccl_api()->CommDestroy(c->comm);
-    for (hipEvent_t e : {c->ev_enc_go, c->bt[0].enc_done, c->bt[1].enc_done, c->bt[2].enc_done})
-        if (e) (void)hipEventDestroy(e);
-    if (c->enc_stream) (void)hipStreamDestroy(c->enc_stream);
-    for (hipEvent_t e : {c->ev_b1, c->ev_b2, c->ev_comm, c->bt[0].up, c->bt[0].use, c->bt[1].up, c->bt[1].use, c->bt[2].up, c->bt[2].use})
-        if (e) (void)hipEventDestroy(e);
-    c->prof.destroy();
-    for (auto& b : c->bt) {
-        b.idx.release();
-        if (b.idx_pin) (void)hipHostFree(b.idx_pin);
-    }
-    DevBuf* all[] = {&c->params, &c->grads, &c->mu, &c->nu, &c->mirror, &c->W2t, &c->Wit, &c->colpart, &c->bt[0].enc32, &c->bt[0].img32, &c->bt[0].action, &c->bt[0].rtg, &c->bt[1].enc32, &c->bt[1].img32, &c->bt[1].action, &c->bt[1].rtg, &c->bt[2].enc32, &c->bt[2].img32, &c->bt[2].action, &c->bt[2].rtg, &c->Xb, &c->XbT,
-                     &c->H1, &c->H1T, &c->A, &c->Y, &c->YT, &c->Xc, &c->H1c, &c->A32, &c->Adx, &c->W1c, &c->W2c, &c->wc_scal, &c->dY, &c->dApre, &c->dApreT, &c->G, &c->dH1T, &c->dzb, &c->dzT, &c->part, &c->scal, &c->img,
-                     &c->hf, &c->a_in, &c->r_in, &c->ha, &c->hr, &c->logits, &c->ret, &c->metrics, &c->dlogits, &c->dret, &c->dha, &c->dhr, &c->da_in,
-                     &c->dr_in, &c->dhf, &c->dh, &c->t1, &c->t2, &c->t3, &c->dws, &c->dbs, &c->dimg, &c->dz, &c->dqkv,
-                     &c->dwsf, &c->dbsf, &c->dtok, &c->loss_part, &c->gtab, &c->gprefix, &c->ctab, &c->cprefix, &c->pf_pack, &c->pf_jobs};
-    for (auto* b : all) b->release();
-    for (auto* v : {&c->xs, &c->ln0, &c->qkv, &c->att, &c->hmid, &c->ln1, &c->u, &c->gl, &c->d_x1, &c->d_u, &c->d_mid, &c->d_qkv, &c->dws0, &c->dbs0,
-                    &c->dws1, &c->dbs1})
-        for (auto& b : *v) b.release();
-    for (hipStream_t st : {c->stream, c->comm_stream, c->copy_stream[0], c->copy_stream[1]})
-        if (st) (void)hipStreamDestroy(st);
     delete c;
     return 0;
 }
@@ -1658,9 +1637,9 @@ static int upload_async(arp_dt* c, int slot, const float* enc, const float* fram
     // ONE copy stream for both slots (round 6; two until then): the uploads share the PCIe link anyway, and every stream of a process is a hardware queue -- with
     // the two copy streams the encoder-inside step held five (compute, 2 x copy, encoder, encoder part) and ran 10.3 -> 11.9 ms per step when the fifth queue came
     // to share a dispatch pipe with a busy one (profiles/r6_n1_flow.txt: same box, GPU_MAX_HW_QUEUES 4 / 8 / 16 and creation orders); four is what the chip runs side by side
-    if (!c->copy_stream[0]) ARP_HIP_OK(hipStreamCreateWithFlags(&c->copy_stream[0], hipStreamNonBlocking));
-    ARP_TRY(stage_slot(c, slot, c->copy_stream[0], enc, frames, action, rtg, B));
-    ARP_HIP_OK(hipEventRecord(b.up, c->copy_stream[0]));
+    if (!c->copy_stream) ARP_TRY(c->copy_stream.create());
+    ARP_TRY(stage_slot(c, slot, c->copy_stream, enc, frames, action, rtg, B));
+    ARP_HIP_OK(hipEventRecord(b.up, c->copy_stream));
     b.up_pending = true;
     b.up_recorded = true;
     b.enc_ahead = false;  // (new frames: whatever enc32 holds belongs to the batch before)
@@ -1708,15 +1687,9 @@ static int stage_slot_indices(arp_dt* c, int si, hipStream_t st, arp_ds* ds, con
     ARP_TRY(b.enc32.ensure(R * k.enc_tokens * k.enc_dim * 4));  // with frames in: the encoder's output buffer
     if (!use_encodings) ARP_TRY(b.img32.ensure(R * res * res * 3 * 4));
     ARP_TRY(b.idx.ensure((size_t)B * 4));
-    if (b.idx_cap < B) {
-        if (b.idx_pin) ARP_HIP_OK(hipHostFree(b.idx_pin));
-        b.idx_pin = nullptr;
-        b.idx_cap = 0;
-        ARP_HIP_OK(hipHostMalloc((void**)&b.idx_pin, (size_t)B * 4, hipHostMallocDefault));
-        b.idx_cap = B;
-    }
-    for (int i = 0; i < B; ++i) b.idx_pin[i] = (int32_t)idx[i];
-    ARP_HIP_OK(hipMemcpyAsync(b.idx.p, b.idx_pin, (size_t)B * 4, hipMemcpyHostToDevice, st));
+    ARP_TRY(b.idx_pin.ensure((size_t)B * 4));
+    for (int i = 0; i < B; ++i) b.idx_pin.as<int32_t>()[i] = (int32_t)idx[i];
+    ARP_HIP_OK(hipMemcpyAsync(b.idx.p, b.idx_pin.p, (size_t)B * 4, hipMemcpyHostToDevice, st));
     // (profiled on the synchronous slot only: the profiler belongs to the compute thread, the uploader thread must not touch it)
     hipEvent_t t0 = si == 2 && c->prof.on ? c->prof.begin(st) : nullptr;
     ARP_TRY(ds_gather_on(ds, st, b.idx.as<int32_t>(), B, k.window, use_encodings ? nullptr : b.img32.as<float>(), use_encodings ? b.enc32.as<float>() : nullptr,
@@ -1737,9 +1710,9 @@ int arp_dt_upload_batch_indices_async(arp_dt* c, int slot, arp_ds* ds, const int
     if (b.used) ARP_HIP_OK(hipEventSynchronize(b.use));
     if (b.up_recorded) ARP_HIP_OK(hipEventSynchronize(b.up));  // (the copy that last read this slot's pinned staging buffer)
     if (b.enc_ahead && b.enc_done) ARP_HIP_OK(hipEventSynchronize(b.enc_done));  // (an encode-ahead pass nobody consumed still writes enc32 / reads img32)
-    if (!c->copy_stream[0]) ARP_HIP_OK(hipStreamCreateWithFlags(&c->copy_stream[0], hipStreamNonBlocking));
-    ARP_TRY(stage_slot_indices(c, slot, c->copy_stream[0], ds, idx, B, use_encodings));
-    ARP_HIP_OK(hipEventRecord(b.up, c->copy_stream[0]));
+    if (!c->copy_stream) ARP_TRY(c->copy_stream.create());
+    ARP_TRY(stage_slot_indices(c, slot, c->copy_stream, ds, idx, B, use_encodings));
+    ARP_HIP_OK(hipEventRecord(b.up, c->copy_stream));
     b.up_pending = true;
     b.up_recorded = true;
     b.enc_ahead = false;
@@ -1913,7 +1886,7 @@ int arp_dt_comm_init(arp_dt* c, const void* id128, int world, int rank) {
     if (!rccl_api()) return fail("librccl.so.1 could not be loaded");
     // the communication stream exists BEFORE RCCL sets up its own queues: created lazily at the first staged step instead (behind them) the staged step ran 1.54 ms
     // where it runs 0.80 (profiles/r6_n1_flow.txt, last block) -- which hardware queue a stream lands on follows the order of creation (runtime.h::prime_runtime)
-    if (!c->comm_stream) ARP_HIP_OK(hipStreamCreateWithFlags(&c->comm_stream, hipStreamNonBlocking));
+    if (!c->comm_stream) ARP_TRY(c->comm_stream.create());
     if (ncclResult_t r = rccl_api()->CommInitRank(&c->comm, world, id, rank); r != ncclSuccess) return rccl_fail("ncclCommInitRank", r);
     c->has_comm = true;
     c->cfg.world = world;
@@ -2006,51 +1979,41 @@ template <typename T> int download_from(DevBuf& stage, const DevBuf& src, float*
 
 template <typename T> int op_gemm_tn(int tile256, int ksplit, const float* A, const float* B, float* out, int M, int N, int K, float alpha) {
     DevBuf st, dA, dB, dP, dO;
-    auto body = [&]() -> int {
-        ARP_TRY(upload_as<T>(st, dA, A, (size_t)K * M));
-        ARP_TRY(upload_as<T>(st, dB, B, (size_t)K * N));
-        const size_t MN = (size_t)M * N;
-        ARP_TRY(dP.ensure((size_t)ksplit * MN * 4));
-        ARP_TRY(dO.ensure(MN * 4));
-        GemmTnArgs g;
-        g.A = dA.p; g.B = dB.p; g.M = M; g.N = N; g.K = K; g.lda = M; g.ldb = N; g.ldo = N; g.ksplit = ksplit; g.tile256 = tile256;
-        g.xcd_slices = tile256 && ksplit % 8 == 0;
-        const int tcode = __is_same(T, bf16_t) ? 1 : 2;
-        if (ksplit == 1) {
-            g.out = dO.as<float>(); g.slice_stride = 0; g.alpha = alpha;
-            ARP_TRY(launch_gemm_tn(tcode, g, nullptr));
-        } else {
-            g.out = dP.as<float>(); g.slice_stride = MN; g.alpha = 1.f;
-            ARP_TRY(launch_gemm_tn(tcode, g, nullptr));
-            launch_splitk_reduce<float>(nullptr, dP.as<float>(), ksplit, MN, N, nullptr, ACT_NONE, dO.as<float>(), nullptr, 0, alpha);
-            ARP_HIP_OK(hipGetLastError());
-        }
-        ARP_HIP_OK(hipMemcpy(out, dO.p, MN * 4, hipMemcpyDeviceToHost));
-        return 0;
-    };
-    const int rc = body();
-    st.release(); dA.release(); dB.release(); dP.release(); dO.release();
-    return rc;
+    ARP_TRY(upload_as<T>(st, dA, A, (size_t)K * M));
+    ARP_TRY(upload_as<T>(st, dB, B, (size_t)K * N));
+    const size_t MN = (size_t)M * N;
+    ARP_TRY(dP.ensure((size_t)ksplit * MN * 4));
+    ARP_TRY(dO.ensure(MN * 4));
+    GemmTnArgs g;
+    g.A = dA.p; g.B = dB.p; g.M = M; g.N = N; g.K = K; g.lda = M; g.ldb = N; g.ldo = N; g.ksplit = ksplit; g.tile256 = tile256;
+    g.xcd_slices = tile256 && ksplit % 8 == 0;
+    const int tcode = __is_same(T, bf16_t) ? 1 : 2;
+    if (ksplit == 1) {
+        g.out = dO.as<float>(); g.slice_stride = 0; g.alpha = alpha;
+        ARP_TRY(launch_gemm_tn(tcode, g, nullptr));
+    } else {
+        g.out = dP.as<float>(); g.slice_stride = MN; g.alpha = 1.f;
+        ARP_TRY(launch_gemm_tn(tcode, g, nullptr));
+        launch_splitk_reduce<float>(nullptr, dP.as<float>(), ksplit, MN, N, nullptr, ACT_NONE, dO.as<float>(), nullptr, 0, alpha);
+        ARP_HIP_OK(hipGetLastError());
+    }
+    ARP_HIP_OK(hipMemcpy(out, dO.p, MN * 4, hipMemcpyDeviceToHost));
+    return 0;
 }
 
 // launch_splitk_reduce<OutT> on host slabs: `out` (and `resid`) are [M, ldo ? ldo : N]; out goes up before the launch and comes back whole
 template <typename OutT>
 int op_splitk_reduce(const float* part, int S, int M, int N, const float* bias, int act, const float* resid, float* out, int ldo, float alpha) {
     DevBuf st, dP, dB, dR, dO;
-    auto body = [&]() -> int {
-        const size_t MN = (size_t)M * N, on = (size_t)M * (ldo ? ldo : N);
-        ARP_TRY(dP.ensure((size_t)S * MN * 4));
-        ARP_HIP_OK(hipMemcpy(dP.p, part, (size_t)S * MN * 4, hipMemcpyHostToDevice));
-        if (bias) ARP_TRY(upload_as<float>(st, dB, bias, (size_t)N));
-        if (resid) ARP_TRY(upload_as<float>(st, dR, resid, on));
-        ARP_TRY(upload_as<OutT>(st, dO, out, on));
-        launch_splitk_reduce<OutT>(nullptr, dP.as<float>(), S, MN, N, bias ? dB.as<float>() : nullptr, act, dO.as<OutT>(), resid ? dR.as<float>() : nullptr, ldo, alpha);
-        ARP_HIP_OK(hipGetLastError());
-        return download_from<OutT>(st, dO, out, on);
-    };
-    const int rc = body();
-    for (DevBuf* b : {&st, &dP, &dB, &dR, &dO}) b->release();
-    return rc;
+    const size_t MN = (size_t)M * N, on = (size_t)M * (ldo ? ldo : N);
+    ARP_TRY(dP.ensure((size_t)S * MN * 4));
+    ARP_HIP_OK(hipMemcpy(dP.p, part, (size_t)S * MN * 4, hipMemcpyHostToDevice));
+    if (bias) ARP_TRY(upload_as<float>(st, dB, bias, (size_t)N));
+    if (resid) ARP_TRY(upload_as<float>(st, dR, resid, on));
+    ARP_TRY(upload_as<OutT>(st, dO, out, on));
+    launch_splitk_reduce<OutT>(nullptr, dP.as<float>(), S, MN, N, bias ? dB.as<float>() : nullptr, act, dO.as<OutT>(), resid ? dR.as<float>() : nullptr, ldo, alpha);
+    ARP_HIP_OK(hipGetLastError());
+    return download_from<OutT>(st, dO, out, on);
 }
 
 constexpr int OP_BWD_GUARD_ROWS = 128;  // rows of N floats behind the last slab (a whole row tile: what a missing row guard would reach)
@@ -2068,46 +2031,41 @@ struct OpGemmBwd {
 };
 template <typename T, typename OutT> int op_gemm_bwd(const OpGemmBwd& a) {
     DevBuf st, dA, dB, dR, dP, dO;
-    auto body = [&]() -> int {
-        const auto [kind, tcode, ksplit, A, lda, B, ldb, resid, out, ldo, slabs, M, N, K, alpha] = a;
-        const bool nn = kind == 2;
-        const size_t MN = (size_t)M * N, on = (size_t)M * (ldo ? ldo : N);
-        const size_t an = nn ? (size_t)(M - 1) * lda + K : (size_t)(K - 1) * lda + M, bn = (size_t)(K - 1) * ldb + N;
-        const size_t pn = (size_t)ksplit * MN + (size_t)OP_BWD_GUARD_ROWS * N;
-        ARP_TRY(upload_as<T>(st, dA, A, an));
-        ARP_TRY(upload_as<T>(st, dB, B, bn));
-        if (resid) ARP_TRY(upload_as<float>(st, dR, resid, on));
-        ARP_TRY(upload_as<OutT>(st, dO, out, on));
-        const bool split = nn || ksplit > 1;
-        if (split) {
-            ARP_TRY(dP.ensure(pn * 4));
-            if (slabs) ARP_HIP_OK(hipMemcpy(dP.p, slabs, pn * 4, hipMemcpyHostToDevice));
-        }
-        GemmTnArgs g;
-        g.A = dA.p; g.B = dB.p; g.M = M; g.N = N; g.K = K; g.lda = lda; g.ldb = ldb; g.ksplit = ksplit;
-        int rc;
-        if (nn) {
-            g.out = dP.as<float>(); g.ldo = N; g.slice_stride = MN; g.alpha = 1.f;
-            rc = launch_gemm_nn(tcode, g, nullptr);
-        } else {
-            g.tile256 = kind; g.xcd_slices = kind && ksplit % 8 == 0;
-            if (split) { g.out = dP.as<float>(); g.ldo = N; g.slice_stride = MN; g.alpha = 1.f; }
-            else { g.out = dO.as<float>(); g.ldo = ldo ? ldo : N; g.slice_stride = 0; g.alpha = alpha; }
-            rc = launch_gemm_tn(tcode, g, nullptr);
-        }
-        if (rc == 0) ARP_HIP_OK(hipGetLastError());
-        if (split && slabs) ARP_HIP_OK(hipMemcpy(slabs, dP.p, pn * 4, hipMemcpyDeviceToHost));
-        if (rc == 0 && split) {
-            launch_splitk_reduce<OutT>(nullptr, dP.as<float>(), ksplit, MN, N, (const float*)nullptr, (int)ACT_NONE, dO.as<OutT>(),
-                                       resid ? dR.as<float>() : nullptr, ldo == N ? 0 : ldo, alpha);
-            ARP_HIP_OK(hipGetLastError());
-        }
-        // (a refused launch still returns the device's `out`: the caller sees that nothing ran)
-        ARP_TRY(download_from<OutT>(st, dO, out, on));
-        return rc;
-    };
-    const int rc = body();
-    for (DevBuf* b : {&st, &dA, &dB, &dR, &dP, &dO}) b->release();
+    const auto [kind, tcode, ksplit, A, lda, B, ldb, resid, out, ldo, slabs, M, N, K, alpha] = a;
+    const bool nn = kind == 2;
+    const size_t MN = (size_t)M * N, on = (size_t)M * (ldo ? ldo : N);
+    const size_t an = nn ? (size_t)(M - 1) * lda + K : (size_t)(K - 1) * lda + M, bn = (size_t)(K - 1) * ldb + N;
+    const size_t pn = (size_t)ksplit * MN + (size_t)OP_BWD_GUARD_ROWS * N;
+    ARP_TRY(upload_as<T>(st, dA, A, an));
+    ARP_TRY(upload_as<T>(st, dB, B, bn));
+    if (resid) ARP_TRY(upload_as<float>(st, dR, resid, on));
+    ARP_TRY(upload_as<OutT>(st, dO, out, on));
+    const bool split = nn || ksplit > 1;
+    if (split) {
+        ARP_TRY(dP.ensure(pn * 4));
+        if (slabs) ARP_HIP_OK(hipMemcpy(dP.p, slabs, pn * 4, hipMemcpyHostToDevice));
+    }
+    GemmTnArgs g;
+    g.A = dA.p; g.B = dB.p; g.M = M; g.N = N; g.K = K; g.lda = lda; g.ldb = ldb; g.ksplit = ksplit;
+    int rc;
+    if (nn) {
+        g.out = dP.as<float>(); g.ldo = N; g.slice_stride = MN; g.alpha = 1.f;
+        rc = launch_gemm_nn(tcode, g, nullptr);
+    } else {
+        g.tile256 = kind; g.xcd_slices = kind && ksplit % 8 == 0;
+        if (split) { g.out = dP.as<float>(); g.ldo = N; g.slice_stride = MN; g.alpha = 1.f; }
+        else { g.out = dO.as<float>(); g.ldo = ldo ? ldo : N; g.slice_stride = 0; g.alpha = alpha; }
+        rc = launch_gemm_tn(tcode, g, nullptr);
+    }
+    if (rc == 0) ARP_HIP_OK(hipGetLastError());
+    if (split && slabs) ARP_HIP_OK(hipMemcpy(slabs, dP.p, pn * 4, hipMemcpyDeviceToHost));
+    if (rc == 0 && split) {
+        launch_splitk_reduce<OutT>(nullptr, dP.as<float>(), ksplit, MN, N, (const float*)nullptr, (int)ACT_NONE, dO.as<OutT>(),
+                                   resid ? dR.as<float>() : nullptr, ldo == N ? 0 : ldo, alpha);
+        ARP_HIP_OK(hipGetLastError());
+    }
+    // (a refused launch still returns the device's `out`: the caller sees that nothing ran)
+    ARP_TRY(download_from<OutT>(st, dO, out, on));
     return rc;
 }
 
@@ -2121,27 +2079,22 @@ template <typename T> int op_gemm_bwd_out(int out_type, const OpGemmBwd& a) {
 template <typename T>
 int op_gemm_relu_bwd(const float* A, const float* W, const float* mask, float* out, float* colsum, int M, int N, int K) {
     DevBuf st, dA, dW, dM, dO, dC, dS;
-    auto body = [&]() -> int {
-        ARP_TRY(upload_as<T>(st, dA, A, (size_t)M * K));
-        ARP_TRY(upload_as<T>(st, dW, W, (size_t)N * K));
-        ARP_TRY(upload_as<T>(st, dM, mask, (size_t)M * N));
-        const int mt = cdiv(M, 256);
-        ARP_TRY(dO.ensure((size_t)M * N * sizeof(T)));
-        ARP_TRY(dC.ensure((size_t)mt * N * 4));
-        ARP_TRY(dS.ensure((size_t)N * 4));
-        GemmArgs g;
-        g.A = dA.p; g.W = dW.p; g.out = dO.p; g.M = M; g.N = N; g.K = K; g.lda = K; g.ldw = K; g.ldr = N; g.ldo = N;
-        g.mask = dM.p; g.ldm = N; g.colsum_part = dC.as<float>();
-        ARP_TRY((launch_gemm256_nt<T, T, ACT_NONE, false, SITE_DT>(g, nullptr)));
-        hipLaunchKernelGGL(colsum_kernel, dim3(cdiv(N, 64)), dim3(256), 0, nullptr, dC.as<float>(), mt, N, dS.as<float>(), 1.f);
-        ARP_HIP_OK(hipGetLastError());
-        ARP_TRY(download_from<T>(st, dO, out, (size_t)M * N));
-        ARP_HIP_OK(hipMemcpy(colsum, dS.p, (size_t)N * 4, hipMemcpyDeviceToHost));
-        return 0;
-    };
-    const int rc = body();
-    st.release(); dA.release(); dW.release(); dM.release(); dO.release(); dC.release(); dS.release();
-    return rc;
+    ARP_TRY(upload_as<T>(st, dA, A, (size_t)M * K));
+    ARP_TRY(upload_as<T>(st, dW, W, (size_t)N * K));
+    ARP_TRY(upload_as<T>(st, dM, mask, (size_t)M * N));
+    const int mt = cdiv(M, 256);
+    ARP_TRY(dO.ensure((size_t)M * N * sizeof(T)));
+    ARP_TRY(dC.ensure((size_t)mt * N * 4));
+    ARP_TRY(dS.ensure((size_t)N * 4));
+    GemmArgs g;
+    g.A = dA.p; g.W = dW.p; g.out = dO.p; g.M = M; g.N = N; g.K = K; g.lda = K; g.ldw = K; g.ldr = N; g.ldo = N;
+    g.mask = dM.p; g.ldm = N; g.colsum_part = dC.as<float>();
+    ARP_TRY((launch_gemm256_nt<T, T, ACT_NONE, false, SITE_DT>(g, nullptr)));
+    hipLaunchKernelGGL(colsum_kernel, dim3(cdiv(N, 64)), dim3(256), 0, nullptr, dC.as<float>(), mt, N, dS.as<float>(), 1.f);
+    ARP_HIP_OK(hipGetLastError());
+    ARP_TRY(download_from<T>(st, dO, out, (size_t)M * N));
+    ARP_HIP_OK(hipMemcpy(colsum, dS.p, (size_t)N * 4, hipMemcpyDeviceToHost));
+    return 0;
 }
 
 template <typename T>
@@ -2149,34 +2102,29 @@ int op_adapter_dy(const float* dz, const float* Wi, const float* A, const float*
                   int tokens, int D) {
     const size_t Kin = (size_t)tokens * D;
     DevBuf st, ddz, dWi, dA, dx, drw, dO, dC, dP, dS;
-    auto body = [&]() -> int {
-        ARP_TRY(upload_as<T>(st, ddz, dz, (size_t)R * E));
-        ARP_TRY(upload_as<T>(st, dWi, Wi, (size_t)E * Kin));
-        ARP_TRY(upload_as<T>(st, dA, A, (size_t)R * Kin));
-        ARP_TRY(dx.ensure((size_t)R * Kin * 4));
-        ARP_HIP_OK(hipMemcpy(dx.p, x, (size_t)R * Kin * 4, hipMemcpyHostToDevice));
-        ARP_TRY(drw.ensure(16));
-        ARP_HIP_OK(hipMemcpy(drw.p, &rw, 4, hipMemcpyHostToDevice));
-        const int nrb = adapter_dy_row_blocks(R), nct = (int)(Kin / 128);
-        ARP_TRY(dO.ensure((size_t)R * Kin * sizeof(T)));
-        ARP_TRY(dC.ensure((size_t)nrb * tokens * D * 4));
-        ARP_TRY(dP.ensure((size_t)nrb * nct * 4));
-        ARP_TRY(dS.ensure((size_t)(D + 4) * 4));
-        AdapterDyArgs a;
-        a.dz = ddz.p; a.Wi = dWi.p; a.A = dA.p; a.x32 = dx.as<float>(); a.rw = drw.as<float>(); a.dApre = dO.p; a.colpart = dC.as<float>();
-        a.dres_part = dP.as<float>(); a.R = R; a.E = E; a.Kin = (int)Kin; a.D = D;
-        ARP_TRY(launch_adapter_dy(__is_same(T, bf16_t) ? 1 : 2, a, nullptr));
-        hipLaunchKernelGGL(colsum_kernel, dim3(cdiv(D, 64)), dim3(256), 0, nullptr, dC.as<float>(), nrb * tokens, D, dS.as<float>(), 1.f);
-        hipLaunchKernelGGL(reduce_sum_kernel, dim3(1), dim3(256), 0, nullptr, dP.as<float>(), nrb * nct, 1.f, dS.as<float>() + D, 0);
-        ARP_HIP_OK(hipGetLastError());
-        ARP_TRY(download_from<T>(st, dO, dApre, (size_t)R * Kin));
-        ARP_HIP_OK(hipMemcpy(colsum, dS.p, (size_t)D * 4, hipMemcpyDeviceToHost));
-        ARP_HIP_OK(hipMemcpy(dres, dS.as<float>() + D, 4, hipMemcpyDeviceToHost));
-        return 0;
-    };
-    const int rc = body();
-    for (DevBuf* b : {&st, &ddz, &dWi, &dA, &dx, &drw, &dO, &dC, &dP, &dS}) b->release();
-    return rc;
+    ARP_TRY(upload_as<T>(st, ddz, dz, (size_t)R * E));
+    ARP_TRY(upload_as<T>(st, dWi, Wi, (size_t)E * Kin));
+    ARP_TRY(upload_as<T>(st, dA, A, (size_t)R * Kin));
+    ARP_TRY(dx.ensure((size_t)R * Kin * 4));
+    ARP_HIP_OK(hipMemcpy(dx.p, x, (size_t)R * Kin * 4, hipMemcpyHostToDevice));
+    ARP_TRY(drw.ensure(16));
+    ARP_HIP_OK(hipMemcpy(drw.p, &rw, 4, hipMemcpyHostToDevice));
+    const int nrb = adapter_dy_row_blocks(R), nct = (int)(Kin / 128);
+    ARP_TRY(dO.ensure((size_t)R * Kin * sizeof(T)));
+    ARP_TRY(dC.ensure((size_t)nrb * tokens * D * 4));
+    ARP_TRY(dP.ensure((size_t)nrb * nct * 4));
+    ARP_TRY(dS.ensure((size_t)(D + 4) * 4));
+    AdapterDyArgs a;
+    a.dz = ddz.p; a.Wi = dWi.p; a.A = dA.p; a.x32 = dx.as<float>(); a.rw = drw.as<float>(); a.dApre = dO.p; a.colpart = dC.as<float>();
+    a.dres_part = dP.as<float>(); a.R = R; a.E = E; a.Kin = (int)Kin; a.D = D;
+    ARP_TRY(launch_adapter_dy(__is_same(T, bf16_t) ? 1 : 2, a, nullptr));
+    hipLaunchKernelGGL(colsum_kernel, dim3(cdiv(D, 64)), dim3(256), 0, nullptr, dC.as<float>(), nrb * tokens, D, dS.as<float>(), 1.f);
+    hipLaunchKernelGGL(reduce_sum_kernel, dim3(1), dim3(256), 0, nullptr, dP.as<float>(), nrb * nct, 1.f, dS.as<float>() + D, 0);
+    ARP_HIP_OK(hipGetLastError());
+    ARP_TRY(download_from<T>(st, dO, dApre, (size_t)R * Kin));
+    ARP_HIP_OK(hipMemcpy(colsum, dS.p, (size_t)D * 4, hipMemcpyDeviceToHost));
+    ARP_HIP_OK(hipMemcpy(dres, dS.as<float>() + D, 4, hipMemcpyDeviceToHost));
+    return 0;
 }
 }  // namespace
 

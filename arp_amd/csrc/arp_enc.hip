@@ -115,9 +115,9 @@ struct HostTensor {
 
 struct arp_enc {
     arp_enc_cfg cfg;
-    hipStream_t stream = nullptr;
+    Stream stream;  // serves arp_enc_forward only; created by its first call
     std::map<std::string, HostTensor> staged;
-    std::vector<void*> owned;
+    std::vector<DevBuf> owned;  // every device allocation holding weights
     bool finalized = false;
     TowerW tower;
     void* w_emb = nullptr;  // T [D, P*P*3]
@@ -131,8 +131,8 @@ struct arp_enc {
         DevBuf patches, pe, x, h, qkv, ao, fc;
         DevBuf a3;  // ARP_MODE_F16X3: the [hi | lo | hi] operand of the current GEMM, binary16 [rows, 3 * (mlp_ratio * width)]
                     // ARP_MODE_F16C: the [hi | x4 | dx4] operand rows (3 bytes per value): [M, D] for LayerNorm / attention outputs, then [M, H] for the hidden activation
-        hipStream_t stream = nullptr;  // parts 1..: the part's own stream (part 0 runs on the caller's)
-        hipEvent_t done = nullptr;
+        Stream stream;  // parts 1..: the part's own stream (part 0 runs on the caller's)
+        Event done;
     };
     static constexpr int MAX_PARTS = 4;
     Ws ws[MAX_PARTS];
@@ -142,7 +142,7 @@ struct arp_enc {
     // times, so that one part's GEMM grid tails and LayerNorms keep meeting the other's full rounds instead of its tails: 9.05-9.08 against 9.19-9.26 ms per 32-sample step
     // (three boxes, three repetitions each: profiles/r6_n1_streams.txt, r6_plans_time.txt, r6_n1_split_final.txt); 56 + 72 the same, 43 + 43 + 42 slower
     int first_part = 0;
-    hipEvent_t ev_fork = nullptr;
+    Event ev_fork;
     bool shared_chip = false; // the pass being enqueued runs beside another part's kernels (tower.h: out_proj's kernel choice)
     DevBuf img_in, out;
     // ARP_MODE_F16C: per GEMM g in {in_proj, out_proj, fc1, fc2} the correction plan (0 plain, 1 weights, 2 weights + activations) and, per layer, the
@@ -162,21 +162,16 @@ struct arp_enc {
     size_t esz() const { return (cfg.mode == ARP_MODE_F32 || cfg.mode == ARP_MODE_F16X3) ? 4 : 2; }  // element size of the ACTIVATION buffers
     size_t wsz() const { return cfg.mode == ARP_MODE_F32 ? 4 : 2; }
 };
+static_assert(!std::is_copy_constructible_v<arp_enc>);
 
 namespace {
 
 int up_f32(arp_enc* c, const float* v, size_t n, float** out) {
-    void* p = nullptr;
-    ARP_HIP_OK(hipMalloc(&p, std::max<size_t>(n * 4, 16)));
-    ARP_HIP_OK(hipMemcpy(p, v, n * 4, hipMemcpyHostToDevice));
-    c->owned.push_back(p);
-    *out = static_cast<float*>(p);
-    return 0;
+    return upload_owned(c->owned, v, n * 4, std::max<size_t>(n * 4, 16), reinterpret_cast<void**>(out));
 }
 // [out, 3 in] = [W_hi | W_hi | W_lo] from the transposed kernel t [out, in] (ARP_MODE_F16X3; the patch embedding of ARP_MODE_F16C)
 int up_kernel_x3(arp_enc* c, const std::vector<float>& t, int in, int out_, void** out) {
     const size_t n = (size_t)in * out_;
-    void* p = nullptr;
     std::vector<f16_t> hb(3 * n);
     for (int o = 0; o < out_; ++o)
         for (int i = 0; i < in; ++i) {
@@ -188,11 +183,7 @@ int up_kernel_x3(arp_enc* c, const std::vector<float>& t, int in, int out_, void
             row[in + i] = h;
             row[2 * in + i] = host_f2h(w - hf);
         }
-    ARP_HIP_OK(hipMalloc(&p, 3 * n * 2));
-    ARP_HIP_OK(hipMemcpy(p, hb.data(), 3 * n * 2, hipMemcpyHostToDevice));
-    c->owned.push_back(p);
-    *out = p;
-    return 0;
+    return upload_owned(c->owned, hb.data(), 3 * n * 2, 3 * n * 2, out);
 }
 // Flax kernel [in, out] -> device [out, in] in the operand type
 int up_kernel(arp_enc* c, const float* src, int in, int out_, void** out) {
@@ -200,23 +191,19 @@ int up_kernel(arp_enc* c, const float* src, int in, int out_, void** out) {
     std::vector<float> t(n);
     for (int i = 0; i < in; ++i)
         for (int o = 0; o < out_; ++o) t[(size_t)o * in + i] = src[(size_t)i * out_ + o];
-    void* p = nullptr;
     if (c->cfg.mode == ARP_MODE_F16X3) return up_kernel_x3(c, t, in, out_, out);
-    ARP_HIP_OK(hipMalloc(&p, std::max<size_t>(n * c->wsz(), 16)));
+    const size_t alloc = std::max<size_t>(n * c->wsz(), 16);
     if (c->cfg.mode == ARP_MODE_BF16) {
         std::vector<bf16_t> hb(n);
         for (size_t i = 0; i < n; ++i) hb[i] = host_f2bf(t[i]);
-        ARP_HIP_OK(hipMemcpy(p, hb.data(), n * 2, hipMemcpyHostToDevice));
-    } else if (c->cfg.mode == ARP_MODE_F16 || c->cfg.mode == ARP_MODE_F16C) {
+        return upload_owned(c->owned, hb.data(), n * 2, alloc, out);
+    }
+    if (c->cfg.mode == ARP_MODE_F16 || c->cfg.mode == ARP_MODE_F16C) {
         std::vector<f16_t> hb(n);
         for (size_t i = 0; i < n; ++i) hb[i] = host_f2h(t[i]);
-        ARP_HIP_OK(hipMemcpy(p, hb.data(), n * 2, hipMemcpyHostToDevice));
-    } else {
-        ARP_HIP_OK(hipMemcpy(p, t.data(), n * 4, hipMemcpyHostToDevice));
+        return upload_owned(c->owned, hb.data(), n * 2, alloc, out);
     }
-    c->owned.push_back(p);
-    *out = p;
-    return 0;
+    return upload_owned(c->owned, t.data(), n * 4, alloc, out);
 }
 // ARP_MODE_F16C: Flax kernel [in, out] -> device rows [W_hi: binary16 x in | dW4: e2m1 x in (| W4: e2m1 x in)] (plan 1 / 2; plan 0: binary16 only)
 // src(i, o) = the weight of input i, output o.  Rows [W_hi: binary16 x in | dW4: e2m1 x in (| W4: e2m1 x in)] for plan 1 (2); two e2m1 values per byte, value 2j in the
@@ -253,12 +240,7 @@ template <typename F> void pack_weight_c(F src, int in, int out_, int plan, std:
 int up_kernel_c(arp_enc* c, const float* src, int in, int out_, int plan, void** out, int* sd, int* sw) {
     std::vector<uint8_t> hb;
     pack_weight_c([&](int i, int o) { return src[(size_t)i * out_ + o]; }, in, out_, plan, hb, sd, sw);
-    void* p = nullptr;
-    ARP_HIP_OK(hipMalloc(&p, hb.size() + 512));  // + the 256 bytes gemm256 MIXC reads past the last row (GemmArgs::mix_nk16)
-    ARP_HIP_OK(hipMemcpy(p, hb.data(), hb.size(), hipMemcpyHostToDevice));
-    c->owned.push_back(p);
-    *out = p;
-    return 0;
+    return upload_owned(c->owned, hb.data(), hb.size(), hb.size() + 512, out);  // + the 256 bytes gemm256 MIXC reads past the last row (GemmArgs::mix_nk16)
 }
 int staged(arp_enc* c, const std::string& name, std::vector<int64_t> shape, const HostTensor** out) {
     auto it = c->staged.find(name);
@@ -505,10 +487,10 @@ int enc_forward_on(arp_enc* c, hipStream_t stream, const float* images_dev, int 
         for (int i = 1; i <= parts; ++i) cut[i] = (int)((long long)nb * i / parts);
         if (parts == 2 && c->first_part > 0 && c->first_part < nb) cut[1] = c->first_part;
         else if (parts == 2 && c->first_part == 0 && nb >= 32) cut[1] = (int)(((long long)nb * 15 + 16) / 32);
-        if (!c->ev_fork) ARP_HIP_OK(hipEventCreateWithFlags(&c->ev_fork, hipEventDisableTiming));
+        if (!c->ev_fork) ARP_TRY(c->ev_fork.create());
         for (int i = 1; i < parts; ++i) {
-            if (!c->ws[i].stream) ARP_HIP_OK(hipStreamCreateWithFlags(&c->ws[i].stream, hipStreamNonBlocking));
-            if (!c->ws[i].done) ARP_HIP_OK(hipEventCreateWithFlags(&c->ws[i].done, hipEventDisableTiming));
+            if (!c->ws[i].stream) ARP_TRY(c->ws[i].stream.create());
+            if (!c->ws[i].done) ARP_TRY(c->ws[i].done.create());
         }
         ARP_HIP_OK(hipEventRecord(c->ev_fork, stream));
         c->shared_chip = true;
@@ -577,17 +559,6 @@ int arp_enc_destroy(arp_enc* c) {
     if (!c) return 0;
     (void)hipSetDevice(c->cfg.device);
     (void)hipDeviceSynchronize();
-    c->prof.destroy();
-    for (void* p : c->owned) (void)hipFree(p);
-    for (auto& w : c->ws) {
-        DevBuf* bufs[] = {&w.patches, &w.pe, &w.x, &w.h, &w.qkv, &w.ao, &w.fc, &w.a3};
-        for (auto* b : bufs) b->release();
-        if (w.stream) (void)hipStreamDestroy(w.stream);
-        if (w.done) (void)hipEventDestroy(w.done);
-    }
-    if (c->ev_fork) (void)hipEventDestroy(c->ev_fork);
-    c->img_in.release(); c->out.release();
-    if (c->stream) (void)hipStreamDestroy(c->stream);
     delete c;
     return 0;
 }
@@ -701,7 +672,7 @@ int arp_enc_forward(arp_enc* c, const float* images, int n, float* out) {
     ARP_HIP_OK(hipSetDevice(c->cfg.device));
     const size_t fi = (size_t)c->cfg.img_res * c->cfg.img_res * 3, fo = (size_t)c->tokens() * c->cfg.width;
     const int mb = c->cfg.max_frames;
-    if (!c->stream) ARP_HIP_OK(hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking));
+    if (!c->stream) ARP_TRY(c->stream.create());
     ARP_TRY(c->img_in.ensure((size_t)std::min(n, mb) * fi * 4));
     ARP_TRY(c->out.ensure((size_t)std::min(n, mb) * fo * 4));
     for (int off = 0; off < n; off += mb) {
@@ -743,45 +714,40 @@ int arp_enc_profile_json(arp_enc* c, char* buf, int buf_len) {
 int arp_op_gemm_f16c(int plan, const float* A, const float* W, const float* bias, float* out, int M, int N, int K, int* sd_sw) {
     if (!A || !W || !out || M <= 0 || N <= 0 || K < 512 || K % 256 || N % 8 || plan < 0 || plan > 2) return fail("bad argument (K % 256, K >= 512, N % 8, plan 0..2)");
     DevBuf dA, dW, dB, dO;
-    auto body = [&]() -> int {
-        std::vector<uint8_t> ha((size_t)M * 3 * K, 0), hw;
-        constexpr float sx = (float)(1 << F16C_X_SHIFT), sdx = (float)(1 << F16C_DX_SHIFT);
-        for (int m = 0; m < M; ++m) {
-            uint8_t* row = ha.data() + (size_t)m * 3 * K;
-            for (int k = 0; k < K; ++k) {
-                const float a = A[(size_t)m * K + k];
-                const f16_t h = host_f2h(a);
-                const float hf = (float)__builtin_bit_cast(_Float16, h.b);
-                memcpy(row + 2 * (size_t)k, &h.b, 2);
-                const int sh = (k & 1) * 4;
-                row[2 * (size_t)K + k / 2] |= (uint8_t)(host_f2fp4(hf * sx) << sh);
-                row[2 * (size_t)K + K / 2 + k / 2] |= (uint8_t)(host_f2fp4((a - hf) * sdx) << sh);
-            }
+    std::vector<uint8_t> ha((size_t)M * 3 * K, 0), hw;
+    constexpr float sx = (float)(1 << F16C_X_SHIFT), sdx = (float)(1 << F16C_DX_SHIFT);
+    for (int m = 0; m < M; ++m) {
+        uint8_t* row = ha.data() + (size_t)m * 3 * K;
+        for (int k = 0; k < K; ++k) {
+            const float a = A[(size_t)m * K + k];
+            const f16_t h = host_f2h(a);
+            const float hf = (float)__builtin_bit_cast(_Float16, h.b);
+            memcpy(row + 2 * (size_t)k, &h.b, 2);
+            const int sh = (k & 1) * 4;
+            row[2 * (size_t)K + k / 2] |= (uint8_t)(host_f2fp4(hf * sx) << sh);
+            row[2 * (size_t)K + K / 2 + k / 2] |= (uint8_t)(host_f2fp4((a - hf) * sdx) << sh);
         }
-        int sd = 0, sw = 0;
-        pack_weight_c([&](int i, int o) { return W[(size_t)o * K + i]; }, K, N, plan, hw, &sd, &sw);
-        if (sd_sw) { sd_sw[0] = sd; sd_sw[1] = sw; }
-        ARP_TRY(dA.ensure(ha.size() + 512)); ARP_TRY(dW.ensure(hw.size() + 512)); ARP_TRY(dO.ensure((size_t)M * N * 4));
-        ARP_HIP_OK(hipMemcpy(dA.p, ha.data(), ha.size(), hipMemcpyHostToDevice));
-        ARP_HIP_OK(hipMemcpy(dW.p, hw.data(), hw.size(), hipMemcpyHostToDevice));
-        if (bias) {
-            ARP_TRY(dB.ensure((size_t)N * 4));
-            ARP_HIP_OK(hipMemcpy(dB.p, bias, (size_t)N * 4, hipMemcpyHostToDevice));
-        }
-        GemmArgs g;
-        g.A = dA.p; g.W = dW.p; g.bias = bias ? dB.as<float>() : nullptr; g.out = dO.p;
-        g.M = M; g.N = N; g.lda = K + K / 2; g.ldw = K + plan * K / 4; g.ldr = N; g.ldo = N;
-        g.mix_nk16 = K / 64; g.mix_nkc_a = plan >= 1 ? K / 256 : 0; g.K = K + plan * K / 4;
-        g.mix_sa = F16C_X_SHIFT + sd; g.mix_sb = F16C_DX_SHIFT + sw;
-        if (plan == 0) ARP_TRY((launch_gemm256_nt<f16_t, float, ACT_NONE, false, 8 + SITE_OP>(g, nullptr)));
-        else ARP_TRY((launch_gemm256_nt<f16_t, float, ACT_NONE, false, 8 + SITE_OP, false, 1, true>(g, nullptr)));
-        ARP_HIP_OK(hipDeviceSynchronize());
-        ARP_HIP_OK(hipMemcpy(out, dO.p, (size_t)M * N * 4, hipMemcpyDeviceToHost));
-        return 0;
-    };
-    const int rc = body();
-    dA.release(); dW.release(); dB.release(); dO.release();
-    return rc;
+    }
+    int sd = 0, sw = 0;
+    pack_weight_c([&](int i, int o) { return W[(size_t)o * K + i]; }, K, N, plan, hw, &sd, &sw);
+    if (sd_sw) { sd_sw[0] = sd; sd_sw[1] = sw; }
+    ARP_TRY(dA.ensure(ha.size() + 512)); ARP_TRY(dW.ensure(hw.size() + 512)); ARP_TRY(dO.ensure((size_t)M * N * 4));
+    ARP_HIP_OK(hipMemcpy(dA.p, ha.data(), ha.size(), hipMemcpyHostToDevice));
+    ARP_HIP_OK(hipMemcpy(dW.p, hw.data(), hw.size(), hipMemcpyHostToDevice));
+    if (bias) {
+        ARP_TRY(dB.ensure((size_t)N * 4));
+        ARP_HIP_OK(hipMemcpy(dB.p, bias, (size_t)N * 4, hipMemcpyHostToDevice));
+    }
+    GemmArgs g;
+    g.A = dA.p; g.W = dW.p; g.bias = bias ? dB.as<float>() : nullptr; g.out = dO.p;
+    g.M = M; g.N = N; g.lda = K + K / 2; g.ldw = K + plan * K / 4; g.ldr = N; g.ldo = N;
+    g.mix_nk16 = K / 64; g.mix_nkc_a = plan >= 1 ? K / 256 : 0; g.K = K + plan * K / 4;
+    g.mix_sa = F16C_X_SHIFT + sd; g.mix_sb = F16C_DX_SHIFT + sw;
+    if (plan == 0) ARP_TRY((launch_gemm256_nt<f16_t, float, ACT_NONE, false, 8 + SITE_OP>(g, nullptr)));
+    else ARP_TRY((launch_gemm256_nt<f16_t, float, ACT_NONE, false, 8 + SITE_OP, false, 1, true>(g, nullptr)));
+    ARP_HIP_OK(hipDeviceSynchronize());
+    ARP_HIP_OK(hipMemcpy(out, dO.p, (size_t)M * N * 4, hipMemcpyDeviceToHost));
+    return 0;
 }
 
 }  // extern "C"

@@ -48,7 +48,7 @@ enum { SITE_FT = 24 };
 
 struct arp_ft {
     arp_ft_cfg cfg;
-    hipStream_t stream = nullptr;
+    Stream stream;
     std::vector<FtParam> infos;
     std::map<std::string, int> index;
     size_t P = 0;
@@ -88,8 +88,8 @@ struct arp_ft {
     // The 1.9 GB gradient goes out in SEVEN buckets in the order the backward produces them (inverse model; per tower: second adapter
     // layer, first adapter layer, intermediate linear), each on the communication stream as soon as its last weight-gradient GEMM is
     // enqueued, so that all but the last bucket's all-reduce runs beside the remaining backward (ft_buckets, step_impl).
-    hipStream_t comm_stream = nullptr;
-    hipEvent_t ev_bucket[8] = {}, ev_comm = nullptr;
+    Stream comm_stream;
+    Event ev_bucket[8], ev_comm;
     bool overlap_comm = true;   // ARP_FT_OVERLAP=0: one all-reduce behind the whole backward
     bool force_comm = false;    // ARP_FT_FORCE_COMM=1: run the all-reduce path at world = 1 too (what a 1-GPU box can test)
     bool comm_live = false;     // set by step_impl around backward(): the bucket hooks fire
@@ -108,6 +108,7 @@ struct arp_ft {
     float* g(const std::string& n) { return grads.as<float>() + infos[index.at(n)].off; }
     size_t psize(const std::string& n) { return infos[index.at(n)].size; }
 };
+static_assert(!std::is_copy_constructible_v<arp_ft>);
 
 namespace {
 
@@ -628,10 +629,10 @@ int arp_ft_create(const arp_ft_cfg* cfg, arp_ft** out) {
     c->cfg = k;
     build_layout(c);
     auto body = [&]() -> int {
-        ARP_HIP_OK(hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking));
+        ARP_TRY(c->stream.create());
         // (the communication stream is created with the communicator: a process's streams share GPU_MAX_HW_QUEUES hardware queues, arp_dt.hip)
-        for (auto& e : c->ev_bucket) ARP_HIP_OK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-        ARP_HIP_OK(hipEventCreateWithFlags(&c->ev_comm, hipEventDisableTiming));
+        for (auto& e : c->ev_bucket) ARP_TRY(e.create());
+        ARP_TRY(c->ev_comm.create());
         if (const char* e = getenv("ARP_FT_OVERLAP")) c->overlap_comm = atoi(e) != 0;
         if (const char* e = getenv("ARP_FT_FORCE_COMM")) c->force_comm = atoi(e) != 0;
         if (const char* e = getenv("ARP_FT_FUSE_ADAM")) c->fuse_adam = atoi(e) != 0;
@@ -665,24 +666,7 @@ int arp_ft_destroy(arp_ft* c) {
     (void)hipSetDevice(c->cfg.device);
     if (c->stream) (void)hipStreamSynchronize(c->stream);
     if (c->has_comm && rccl_api()) (void)rccl_api()->CommDestroy(c->comm);
-    c->prof.destroy();
-    DevBuf* all[] = {&c->params, &c->grads, &c->mu, &c->nu, &c->mirror, &c->sV1t, &c->r, &c->action, &c->scores, &c->ds, &c->dist, &c->C, &c->CT_, &c->Ct, &c->Hinv, &c->logits,
-                     &c->dlogits, &c->dHinv, &c->dHinvT_, &c->dHinvt, &c->dist, &c->dC, &c->metrics, &c->scal, &c->part};
-    for (auto* b : all) b->release();
-    for (int w = 0; w < 2; ++w) {
-        DevBuf* tw[] = {&c->sW1t[w], &c->sW2t[w], &c->x_in[w], &c->x_fin[w], &c->X[w], &c->XT[w], &c->f[w], &c->fT_[w],
-                        &c->fTt[w], &c->H[w], &c->HT[w], &c->A[w], &c->a[w], &c->nrm[w], &c->da[w], &c->dA[w], &c->dAT_[w], &c->dAt[w], &c->dfd[w], &c->dH[w],
-                        &c->dHp[w], &c->dHpt[w], &c->df[w], &c->dUt[w], &c->dres_part[w]};
-        for (auto* b : tw) b->release();
-    }
-    if (c->comm_stream) {
-        (void)hipStreamSynchronize(c->comm_stream);
-        (void)hipStreamDestroy(c->comm_stream);
-    }
-    for (auto e : c->ev_bucket)
-        if (e) (void)hipEventDestroy(e);
-    if (c->ev_comm) (void)hipEventDestroy(c->ev_comm);
-    if (c->stream) (void)hipStreamDestroy(c->stream);
+    if (c->comm_stream) (void)hipStreamSynchronize(c->comm_stream);
     delete c;
     return 0;
 }
@@ -893,7 +877,7 @@ int arp_ft_comm_init(arp_ft* c, const void* id128, int world, int rank) {
     static_assert(sizeof(ncclUniqueId) == 128, "unexpected ncclUniqueId size");
     memcpy(&id, id128, 128);
     if (!rccl_api()) return fail("librccl.so.1 could not be loaded");
-    if (!c->comm_stream) ARP_HIP_OK(hipStreamCreateWithFlags(&c->comm_stream, hipStreamNonBlocking));  // (before RCCL's own queues: arp_dt.hip::arp_dt_comm_init)
+    if (!c->comm_stream) ARP_TRY(c->comm_stream.create());  // (before RCCL's own queues: arp_dt.hip::arp_dt_comm_init)
     if (ncclResult_t r = rccl_api()->CommInitRank(&c->comm, world, id, rank); r != ncclSuccess) return rccl_fail("ncclCommInitRank", r);
     c->has_comm = true;
     c->world = world;

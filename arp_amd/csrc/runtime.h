@@ -1,8 +1,10 @@
-// Host-side runtime pieces shared by the two hot paths: error string, device buffers, per-site
-// HIP-event profiler.
+// Host-side runtime pieces shared by the hot paths: error string, the owners of device memory, pinned memory, streams and events,
+// per-site HIP-event profiler.
 #pragma once
+#include <atomic>
 #include <map>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 #include "common.h"
@@ -14,27 +16,141 @@ struct arp_event {
 
 namespace arp {
 
+// Ownership rule of the host runtime: every GPU resource a handle or an entry point holds lives in one of the owners below.  An owner is empty by default,
+// move-only, and NEVER creates its resource in a constructor -- creation is an explicit call (ensure / create) at the place and in the order the code
+// wants it (the order of stream creation decides which hardware queue a stream lands on: prime_runtime below).  Its destructor releases what it
+// holds, ignores HIP errors and makes no HIP call when empty.  The arp_*_destroy functions therefore only ORDER things (synchronise, destroy graph execs and
+// communicators) and delete the handle.  Every acquire / release is counted in `live` (arp_debug_live), which is what tests/test_resource_ownership_gpu.py reads.
+struct Live {
+    std::atomic<int64_t> dev_bytes{0}, dev_bufs{0}, streams{0}, events{0}, pin_bytes{0};
+};
+inline Live live;
+
 struct DevBuf {
     void* p = nullptr;
     size_t bytes = 0;
+    DevBuf() = default;
+    DevBuf(const DevBuf&) = delete;
+    DevBuf& operator=(const DevBuf&) = delete;
+    DevBuf(DevBuf&& o) noexcept : p(o.p), bytes(o.bytes) { o.p = nullptr; o.bytes = 0; }
+    DevBuf& operator=(DevBuf&& o) noexcept {
+        if (this != &o) {
+            release();
+            p = o.p; bytes = o.bytes;
+            o.p = nullptr; o.bytes = 0;
+        }
+        return *this;
+    }
+    ~DevBuf() { release(); }
     int ensure(size_t need) {
         if (need <= bytes) return 0;
         if (p) {
             ARP_HIP_OK(hipFree(p));
-            p = nullptr;
-            bytes = 0;
+            forget();
         }
         ARP_HIP_OK(hipMalloc(&p, need));
         bytes = need;
+        live.dev_bytes += (int64_t)need;
+        live.dev_bufs += 1;
         return 0;
     }
     void release() {
-        if (p) (void)hipFree(p);
+        if (!p) return;
+        (void)hipFree(p);
+        forget();
+    }
+    template <typename T> T* as() const { return static_cast<T*>(p); }
+
+  private:
+    void forget() {
+        live.dev_bytes -= (int64_t)bytes;
+        live.dev_bufs -= 1;
         p = nullptr;
         bytes = 0;
     }
-    template <typename T> T* as() const { return static_cast<T*>(p); }
 };
+static_assert(!std::is_copy_constructible_v<DevBuf> && std::is_nothrow_move_constructible_v<DevBuf>);
+
+// hipHostMalloc memory; grows like DevBuf (the caller synchronises whatever still reads the old block first)
+struct PinBuf {
+    void* p = nullptr;
+    size_t bytes = 0;
+    PinBuf() = default;
+    PinBuf(const PinBuf&) = delete;
+    PinBuf& operator=(const PinBuf&) = delete;
+    ~PinBuf() { release(); }
+    int ensure(size_t need) {
+        if (need <= bytes) return 0;
+        if (p) {
+            ARP_HIP_OK(hipHostFree(p));
+            forget();
+        }
+        ARP_HIP_OK(hipHostMalloc(&p, need, hipHostMallocDefault));
+        bytes = need;
+        live.pin_bytes += (int64_t)need;
+        return 0;
+    }
+    void release() {
+        if (!p) return;
+        (void)hipHostFree(p);
+        forget();
+    }
+    template <typename T> T* as() const { return static_cast<T*>(p); }
+
+  private:
+    void forget() {
+        live.pin_bytes -= (int64_t)bytes;
+        p = nullptr;
+        bytes = 0;
+    }
+};
+
+// a non-blocking stream; reads as the raw handle at launch sites
+struct Stream {
+    hipStream_t s = nullptr;
+    Stream() = default;
+    Stream(const Stream&) = delete;
+    Stream& operator=(const Stream&) = delete;
+    ~Stream() {
+        if (!s) return;
+        (void)hipStreamDestroy(s);
+        live.streams -= 1;
+    }
+    int create() {
+        ARP_HIP_OK(hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
+        live.streams += 1;
+        return 0;
+    }
+    operator hipStream_t() const { return s; }
+};
+
+struct Event {
+    hipEvent_t e = nullptr;
+    Event() = default;
+    Event(const Event&) = delete;
+    Event& operator=(const Event&) = delete;
+    Event(Event&& o) noexcept : e(o.e) { o.e = nullptr; }
+    ~Event() {
+        if (!e) return;
+        (void)hipEventDestroy(e);
+        live.events -= 1;
+    }
+    int create(unsigned flags = hipEventDisableTiming) {
+        ARP_HIP_OK(hipEventCreateWithFlags(&e, flags));
+        live.events += 1;
+        return 0;
+    }
+    operator hipEvent_t() const { return e; }
+};
+
+// One weight allocation of `alloc` bytes holding the first `n` bytes of src.  `owned` has it from before the copy: a failed upload is freed with the handle.
+inline int upload_owned(std::vector<DevBuf>& owned, const void* src, size_t n, size_t alloc, void** out) {
+    DevBuf& b = owned.emplace_back();
+    ARP_TRY(b.ensure(alloc));
+    ARP_HIP_OK(hipMemcpy(b.p, src, n, hipMemcpyHostToDevice));
+    *out = b.p;
+    return 0;
+}
 
 // One synchronous host -> device copy on the NULL stream before the process creates its first stream (round 6, profiles/r6_n1_flow.txt / r6_n1_flow3.txt).
 // Measured on one box, same binary, same kernels: the encoder-inside policy step with two encoder part streams + the encode-ahead stream runs 11.7 ms per
@@ -62,6 +178,10 @@ inline int prime_runtime(int device) {
 // stream time per launch).
 struct Profiler {
     bool on = false;
+    Profiler() = default;
+    Profiler(const Profiler&) = delete;
+    Profiler& operator=(const Profiler&) = delete;
+    ~Profiler() { destroy(); }
     struct Span { int site; hipEvent_t a, b; };
     std::vector<std::string> names;
     std::map<std::string, int> index;
@@ -87,7 +207,7 @@ struct Profiler {
             return e;
         }
         hipEvent_t e = nullptr;
-        (void)hipEventCreate(&e);
+        if (hipEventCreate(&e) == hipSuccess) live.events += 1;
         return e;
     }
     hipEvent_t begin(hipStream_t s) {
@@ -129,7 +249,11 @@ struct Profiler {
     }
     void destroy() {
         collect();
-        for (auto e : pool) (void)hipEventDestroy(e);
+        for (auto e : pool) {
+            if (!e) continue;
+            (void)hipEventDestroy(e);
+            live.events -= 1;
+        }
         pool.clear();
     }
 };

@@ -47,6 +47,9 @@ extern "C" {
 
 const char* arp_last_error(void);
 int arp_version(void);
+/* test hook: what the library's handles and entry points hold right now, process-wide: out5 = {device bytes, device buffers, streams, events, pinned host bytes}.
+   Counts the library's own allocations only (not arp_dev_malloc / arp_event_create, which the caller frees). */
+int arp_debug_live(int64_t out5[5]);
 int arp_device_count(void); /* number of visible HIP devices; 0 when there is none (never fails) */
 
 /* ---- raw device memory + events (for HBM-resident benchmarking; no torch types anywhere) ------ */
