@@ -193,6 +193,7 @@ SIGNATURES = {
     "arp_enc_finalize_weights": (_i, [_vp]),
     "arp_enc_forward": (_i, [_vp, _fp, _i, _fp]),
     "arp_enc_set_streams": (_i, [_vp, _i, _i, _i]),
+    "arp_enc_set_latency": (_i, [_vp, _i, _i]),
     "arp_enc_profile_enable": (_i, [_vp, _i]),
     "arp_enc_profile_json": (_i, [_vp, C.c_char_p, _i]),
     "arp_dt_attach_encoder": (_i, [_vp, _vp]),
@@ -210,6 +211,16 @@ SIGNATURES = {
     "arp_ds_nbytes": (C.c_int64, [_vp]),
     "arp_dt_upload_batch_indices_async": (_i, [_vp, _i, _vp, _i64p, _i, _i]),
     "arp_dt_set_batch_indices": (_i, [_vp, _vp, _i64p, _i, _i]),
+    "arp_rollout_create": (_i, [_vp, _vp, _i, _i, _i, _f, C.POINTER(_vp)]),
+    "arp_rollout_create_with_encoder": (_i, [_vp, _vp, _vp, _i, _i, _i, _f, C.POINTER(_vp)]),
+    "arp_rollout_destroy": (_i, [_vp]),
+    "arp_rollout_reset": (_i, [_vp, _i32p, _i, _fp]),
+    "arp_rollout_set_lut": (_i, [_vp, _fp]),
+    "arp_rollout_set_reward_norm": (_i, [_vp, _i, _f]),
+    "arp_rollout_step": (_i, [_vp, _u8p, _fp, _i, _i32p]),
+    "arp_rollout_read": (_i, [_vp, C.c_char_p, _vp, C.c_int64]),
+    "arp_rollout_debug_set_tail": (_i, [_vp, _f, _i]),
+    "arp_op_rollout_decide": (_i, [_fp, _i32p, _i, _i, _i, _i32p]),
     "arp_h5_write_rows_deflated": (_i, [_vp, C.c_int64, C.c_int64, _vp, C.c_uint64, C.c_uint64, C.c_uint64, _i, _i]),
     "arp_h5_inflate_last_frames": (_i, [_i, _i, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), _u8p, C.c_uint64, C.c_uint64,
                                         C.POINTER(C.c_uint64), C.POINTER(C.c_uint32), _u8p, _i]),

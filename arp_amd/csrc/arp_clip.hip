@@ -16,6 +16,7 @@
 #include "common.h"
 #include "gemm.h"
 #include "gemm256.h"
+#include "clip_internal.h"
 #include "tower.h"
 #include "preprocess.h"
 #include "preprocess_host.h"
@@ -665,6 +666,13 @@ static int label_dev(arp_clip* c, const uint8_t* frames_dev, int n, int H, int W
         ARP_HIP_OK(hipEventRecord(c->ev_join[i - 1], c->siblings[i - 1]->stream));
         ARP_HIP_OK(hipStreamWaitEvent(c->stream, c->ev_join[i - 1], 0));
     }
+    return 0;
+}
+
+int clip_stream_of(arp_clip* c, hipStream_t* stream, int* device) {
+    ARP_TRY(check_ready(c, true));
+    *stream = c->stream;
+    *device = c->cfg.device;
     return 0;
 }
 

@@ -18,6 +18,7 @@
 #include "attention.h"
 #include "common.h"
 #include "ds_internal.h"
+#include "dt_internal.h"
 #include "dtops.h"
 #include "enc_internal.h"
 #include "gemm.h"
@@ -1773,6 +1774,49 @@ int arp_dt_encode_ahead(arp_dt* c, int slot) {
     std::lock_guard<std::mutex> lock(c->capture_mu);
     return enqueue_encode(c, slot, slot == 2);
 }
+
+}  // extern "C"
+
+namespace arp {
+
+int dt_rollout_info(arp_dt* c, DtRolloutInfo* o) {
+    if (!c || !o) return fail("null argument");
+    o->window = c->cfg.window; o->enc_tokens = c->cfg.enc_tokens; o->enc_dim = c->cfg.enc_dim; o->n_actions = c->cfg.n_actions;
+    o->device = c->cfg.device; o->bc = c->bc() ? 1 : 0; o->enc = c->enc; o->stream = c->stream;
+    return 0;
+}
+
+int dt_rollout_bind(arp_dt* c, int B, float** enc32, int32_t** action, float** rtg) {
+    if (!c || B <= 0) return fail("bad argument");
+    ARP_HIP_OK(hipSetDevice(c->cfg.device));
+    c->cur = 2;  // the synchronous slot, as arp_dt_set_batch
+    arp_dt::BatchSlot& b = c->bt[2];
+    if (b.enc_ahead && c->enc_stream) ARP_HIP_OK(hipStreamSynchronize(c->enc_stream));  // (an encode-ahead pass still writing the buffer about to be filled)
+    b.enc_ahead = false;
+    const size_t R = (size_t)B * c->cfg.window;
+    if (b.enc32.bytes < R * c->cfg.enc_tokens * c->cfg.enc_dim * 4 || b.action.bytes < R * 4 || (!c->bc() && b.rtg.bytes < R * 4))
+        ARP_HIP_OK(hipStreamSynchronize(c->stream));  // (the buffers grow: nothing queued may still read the old ones)
+    ARP_TRY(b.action.ensure(R * 4));
+    if (!c->bc()) ARP_TRY(b.rtg.ensure(R * 4));
+    ARP_TRY(b.enc32.ensure(R * c->cfg.enc_tokens * c->cfg.enc_dim * 4));
+    b.B = B;
+    b.images = false;
+    ARP_TRY(ensure_buffers(c, B));
+    c->use_images = false;
+    *enc32 = b.enc32.as<float>(); *action = b.action.as<int32_t>(); *rtg = c->bc() ? nullptr : b.rtg.as<float>();
+    return 0;
+}
+
+int dt_rollout_forward(arp_dt* c, const float** logits) {
+    if (!c || c->B <= 0) return fail("no batch bound");
+    ARP_TRY(c->cfg.mode == ARP_MODE_BF16 ? fwd_bwd_graphed<bf16_t>(c, 3) : (c->cfg.mode == ARP_MODE_F16 ? fwd_bwd_graphed<f16_t>(c, 3) : fwd_bwd_graphed<float>(c, 3)));
+    *logits = c->logits.as<float>();
+    return 0;
+}
+
+}  // namespace arp
+
+extern "C" {
 
 int arp_dt_forward(arp_dt* c, float* action_logits, float* return_pred, float* metrics) {
     if (!c) return fail("null handle");

@@ -145,6 +145,16 @@ struct arp_enc {
     Event ev_fork;
     bool shared_chip = false; // the pass being enqueued runs beside another part's kernels (tower.h: out_proj's kernel choice)
     DevBuf img_in, out;
+    // Latency path (the rollout session's per-step pass of its E new frames): a call of at most lat_rows token rows IN TOTAL, in the plain 16-bit
+    // modes, runs as ONE part on tower.h's latency path -- the W-tiled skinny GEMMs (patch embedding, in_proj, c_fc), out_proj / c_proj as split-K slabs whose
+    // reduction kernel adds bias + residual and applies the next LayerNorm.  Only callers that ask for it (enc_forward_on's `latency`: the rollout session, and
+    // arp_enc_forward once arp_enc_set_latency turned lat_host on) take it; the training paths never do, whatever their row count.
+    // Default 514 = two frames at 257 tokens, the largest row count at which the path was measured faster inside a rollout step (ViT-B/16, f16 / bf16:
+    // 257 rows 1.10 against 1.56 ms per step, 514 rows 1.39 against 1.69, 771 rows 1.80 against 1.69 -- slower; profiles/rollout_step_timing.txt).
+    int lat_rows = 514;  // arp_enc_set_latency / ARP_ENC_LAT_ROWS (up to SKINNY_MAX_M); 0 = the throughput kernels at every size
+    bool lat_host = false;        // arp_enc_forward asks for the latency path too (off: host calls keep the bits they always had)
+    bool lat_now = false;         // the pass being enqueued runs on the latency path
+    DevBuf lat_part;              // split-K slabs, f32 [<= 4][rows][width]
     // ARP_MODE_F16C: per GEMM g in {in_proj, out_proj, fc1, fc2} the correction plan (0 plain, 1 weights, 2 weights + activations) and, per layer, the
     // power-of-two exponents the e2m1 (fp4) weight segments were scaled by: dW4 = fp4(dW * 2^sw_d), W4 = fp4(W * 2^sw_w)
     bool vperm = true;  // ARP_MODE_F16C: V's columns permuted inside every head so that the attention's [hi | x4 | dx4] rows leave in whole pieces (attention.h, outc == 2); cleared by geometry
@@ -274,6 +284,9 @@ template <typename T> int forward_chunk(arp_enc* c, arp_enc::Ws& w, hipStream_t 
     const int G = k.img_res / k.patch, N = c->tokens(), D = k.width, KP = k.patch * k.patch * 3;
     TowerCtx t;
     t.stream = stream; t.prof = &c->prof; t.attn_impl = k.attn_impl; t.gemm_force = c->gemm_force; t.shared_chip = c->shared_chip;
+    if (sizeof(T) == 2 && c->lat_now) {  // (the patch embedding below then goes through tower_gemm's skinny route where skinny_supported holds)
+        t.skinny = true; t.part = c->lat_part.as<float>(); t.part_floats = c->lat_part.bytes / 4;
+    }
     {
         ProfScope ps(c->prof, stream, "m3ae.patchify");
         const size_t tot = (size_t)nb * G * G * KP;
@@ -466,11 +479,19 @@ int enc_op_gemm_site(const arp_gemm_site& d) {
 // Enqueues the encoder of `n` device-resident frames behind everything already on `stream`; `stream` continues behind the last part.  Safe under a
 // stream capture of `stream` (the part streams join the capture through the fork event and leave it through the join events), but every buffer must
 // exist beforehand: the first call of a geometry allocates and must run eagerly (arp_dt.hip runs two eager steps before it captures).
-int enc_forward_on(arp_enc* c, hipStream_t stream, const float* images_dev, int n, float* out_dev) {
+int enc_forward_on(arp_enc* c, hipStream_t stream, const float* images_dev, int n, float* out_dev, bool latency) {
     if (!c || !c->finalized) return fail("encoder weights not finalized");
     if (n <= 0) return 0;
     const int mb = c->cfg.max_frames;
     const size_t fi = (size_t)c->cfg.img_res * c->cfg.img_res * 3, fo = (size_t)c->tokens() * c->cfg.width;
+    // the latency path: decided on the call's TOTAL rows (never per part or per chunk: a frame's bits must not depend on how a call is cut), one part
+    if (latency && (c->cfg.mode == ARP_MODE_F16 || c->cfg.mode == ARP_MODE_BF16) && n <= mb && (long)n * c->tokens() <= c->lat_rows) {
+        ARP_TRY(c->lat_part.ensure((size_t)4 * n * c->tokens() * c->cfg.width * 4));
+        c->lat_now = true;
+        const int rc = forward_part(c, c->ws[0], stream, images_dev, n, out_dev);
+        c->lat_now = false;
+        return rc;
+    }
     for (int off = 0; off < n; off += mb) {
         const int nb = std::min(mb, n - off);
         const float* img = images_dev + off * fi;
@@ -543,6 +564,7 @@ int arp_enc_create(const arp_enc_cfg* cfg, arp_enc** out) {
     if (const char* e = getenv("ARP_ENC_STREAMS")) c->n_parts = std::max(1, std::min(atoi(e), (int)arp_enc::MAX_PARTS));
     if (const char* e = getenv("ARP_ENC_SPLIT")) c->first_part = std::max(-1, atoi(e));
     if (const char* e = getenv("ARP_ENC_MIN_PART")) c->min_part_frames = std::max(1, atoi(e));
+    if (const char* e = getenv("ARP_ENC_LAT_ROWS")) c->lat_rows = std::min(std::max(atoi(e), 0), SKINNY_MAX_M);
     // fc1's plan-0 instance has no e2m1 side output, which fc2's correction K-tiles read: such a plan would run on stale operand segments
     if (c->plan[2] == 0 && c->plan[3] >= 1) {
         delete c;
@@ -678,7 +700,7 @@ int arp_enc_forward(arp_enc* c, const float* images, int n, float* out) {
     for (int off = 0; off < n; off += mb) {
         const int nb = std::min(mb, n - off);
         ARP_HIP_OK(hipMemcpyAsync(c->img_in.p, images + off * fi, nb * fi * 4, hipMemcpyHostToDevice, c->stream));
-        ARP_TRY(enc_forward_on(c, c->stream, c->img_in.as<float>(), nb, c->out.as<float>()));
+        ARP_TRY(enc_forward_on(c, c->stream, c->img_in.as<float>(), nb, c->out.as<float>(), c->lat_host && n <= mb));
         ARP_HIP_OK(hipMemcpyAsync(out + off * fo, c->out.p, nb * fo * 4, hipMemcpyDeviceToHost, c->stream));
         ARP_HIP_OK(hipStreamSynchronize(c->stream));
     }
@@ -692,6 +714,15 @@ int arp_enc_set_streams(arp_enc* c, int n_streams, int first_part_frames, int mi
     c->n_parts = n_streams;
     c->first_part = first_part_frames;
     if (min_part_frames > 0) c->min_part_frames = min_part_frames;
+    return 0;
+}
+
+// The latency path's row limit (arp_enc::lat_rows; 0 disables the path for every caller) and whether arp_enc_forward takes the path too (host_calls: 0 / 1,
+// < 0 leaves it).  Takes effect from the next call.
+int arp_enc_set_latency(arp_enc* c, int rows, int host_calls) {
+    if (!c || rows < 0) return fail("set_latency: rows must be >= 0");
+    c->lat_rows = std::min(rows, SKINNY_MAX_M);
+    if (host_calls >= 0) c->lat_host = host_calls != 0;
     return 0;
 }
 

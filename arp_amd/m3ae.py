@@ -37,6 +37,9 @@ def flops_per_frame(cfg):
     return 2 * macs
 
 
+LATENCY_ROWS_DEFAULT = 514  # arp_enc::lat_rows as the library sets it: two frames at 257 tokens
+
+
 class M3AEEncoder:
     def __init__(self, cfg, params, mode="bf16", device=0, max_frames=128, attn_impl=0):
         """mode: "f16" / "bf16" (16-bit GEMM operands: throughput modes with a stated error), "f32" (f32-input MFMA: the parity mode) or
@@ -66,6 +69,12 @@ class M3AEEncoder:
     def set_streams(self, n_streams=2, first_part_frames=0, min_part_frames=0):
         """Part streams of a call (``arp_enc_set_streams``): contiguous parts of the frames on HIP streams of their own; same encodings for every setting."""
         check(lib.arp_enc_set_streams(self._h, int(n_streams), int(first_part_frames), int(min_part_frames)))
+
+    def set_latency_rows(self, rows, host_calls=None):
+        """The latency path's row limit (``arp_enc_set_latency``): a call of at most ``rows`` token rows in total (frames x tokens; f16 / bf16) runs the skinny
+        GEMMs instead of the throughput tiles.  A rollout session's per-step pass takes the path by default; ``host_calls=True`` makes
+        :meth:`forward_representation` take it too.  ``rows=0`` turns it off for every caller."""
+        check(lib.arp_enc_set_latency(self._h, int(rows), -1 if host_calls is None else int(bool(host_calls))))
 
     def profile(self, on=True):
         check(lib.arp_enc_profile_enable(self._h, int(on)))

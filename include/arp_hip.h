@@ -383,6 +383,13 @@ int arp_enc_forward(arp_enc* h, const float* images_host, int n, float* out_host
  * for the labelling pass.  first_part_frames > 0: that many frames in part 0 of two; 0: the default cut (15/32 of the frames: parts that end at different times
  * fill each other's grid tails better, -1.5 % per step); < 0: equal parts.  A part of fewer than min_part_frames frames (<= 0: keep the default, 24) is not cut off.  Encodings are bit-identical for every setting. */
 int arp_enc_set_streams(arp_enc* h, int n_streams, int first_part_frames, int min_part_frames);
+/* Latency path: a call of at most `rows` token rows in total (frames x tokens; default 514: two frames at 257 tokens, beyond which the path
+ * measured slower; capped at 1024), in ARP_MODE_F16 / ARP_MODE_BF16,
+ * runs the W-tiled skinny GEMMs with split-K out_proj / c_proj whose reduction applies the next LayerNorm (csrc/tower.h::run_blocks) instead of the throughput
+ * tiles: same operands, same accumulation type, another summation order.  Only a rollout session's per-step pass takes it by default; host_calls = 1 makes
+ * arp_enc_forward take it too (0: not; < 0: unchanged).  rows = 0 turns the path off for every caller.  The training paths never take it.
+ * Environment: ARP_ENC_LAT_ROWS sets `rows` at create. */
+int arp_enc_set_latency(arp_enc* h, int rows, int host_calls);
 int arp_enc_profile_enable(arp_enc* h, int on);
 int arp_enc_profile_json(arp_enc* h, char* buf, int buf_len);
 /* Put the frozen encoder INSIDE the policy step: after attaching, arp_dt_set_batch_images stages raw frames
@@ -420,6 +427,39 @@ int64_t arp_ds_nbytes(arp_ds* ds); /* HBM the handle holds */
  * [enc_tokens, enc_dim] per row) and its labels.  Every index and every geometry is checked on the host first; idx need not outlive the call. */
 int arp_dt_upload_batch_indices_async(arp_dt* h, int slot, arp_ds* ds, const int64_t* idx, int B, int use_encodings);
 int arp_dt_set_batch_indices(arp_dt* h, arp_ds* ds, const int64_t* idx, int B, int use_encodings);
+
+/* ---- row N4: a device-resident rollout session ------------------------------------------------------
+ * batch_rollout's inner loop (arp_dt/envs/rollout_procgen.py:96-166, driven by create_test_step, main_procgen.py:171-229) for n_envs independent
+ * environments: per step one uint8 frame [H, W, 3] per environment goes in and one greedy action comes out, with ONE host synchronisation.  The session keeps,
+ * in HBM, a ring of the last `window` encodings, actions and returns-to-go per environment, the current return-to-go and the episode length; a step encodes
+ * only the NEW frames (the frozen encoder attached to `policy`, on its latency path where that applies), builds the policy's batch on the device -- the
+ * L = min(steps since reset + 1, window) real steps at the FRONT in time order, zeros behind: prepare_input's short windows at the start of an episode --
+ * runs the policy's own forward and takes the argmax of the logits row L - 1.  With a reward handle the CLIP reward of the same frames
+ * (get_torch_clip_reward, envs/vl_reward.py:11-23, with the handle's prompt reduction) is computed beside that on the reward handle's stream and a kernel
+ * applies rtg -= (r - (use_normalize ? reward_min : 0)) / scale (:152-155); without one, `rewards` (any of VL_REWARD_FNS, computed by the caller) does, and
+ * with neither the return-to-go stays constant.  H and W must be the encoder's img_res.  The policy must have a frozen encoder attached (model BC, which
+ * refuses one: arp_rollout_create_with_encoder).  After a step that failed behind its first launch the session refuses further steps.  The policy and reward handles stay the caller's and must outlive the session; a session call
+ * must not run beside another host thread's call on either handle. */
+typedef struct arp_rollout arp_rollout;
+int arp_rollout_create(arp_dt* policy, arp_clip* reward_or_null, int n_envs, int H, int W, float scale, arp_rollout** out);
+/* The same with the session's encoder passed in instead of read from the policy handle.  This is how model BC runs (two tokens per step, no return-to-go
+ * ring): a BC handle refuses arp_dt_attach_encoder, and goes on refusing it -- the session only borrows `encoder` for its own passes, and its geometry must be
+ * the policy's enc_tokens x enc_dim.  For a BC policy a reward handle, arp_rollout_set_reward_norm and `rewards` in arp_rollout_step are refused with an
+ * error string (BC.encode reads no return-to-go), and "rtg_window" does not exist. */
+int arp_rollout_create_with_encoder(arp_dt* policy, arp_enc* encoder, arp_clip* reward_or_null, int n_envs, int H, int W, float scale, arp_rollout** out);
+int arp_rollout_destroy(arp_rollout* h);
+/* start an episode in the n listed environments: return-to-go rtg0[i] (already divided by scale, as :90), episode length 0 */
+int arp_rollout_reset(arp_rollout* h, const int32_t* env_ids, int n, const float* rtg0);
+int arp_rollout_set_lut(arp_rollout* h, const float* lut768); /* lut[c * 256 + u]: the f32 value of byte u in channel c (as arp_ds_set_lut); required */
+int arp_rollout_set_reward_norm(arp_rollout* h, int use_normalize, float reward_min);
+int arp_rollout_step(arp_rollout* h, const uint8_t* frames_host /* [E, H, W, 3] */, const float* rewards_or_null /* [E] */, int use_crop,
+                     int32_t* actions_out /* [E] */);
+/* test / logging accessor; synchronises.  what: "enc_window" f32 [E, T, tokens, dim], "action_window" int32 [E, T], "rtg_window" f32 [E, T] (the policy batch of
+ * the last step), "len" int32 [E] (steps since reset), "rtg" f32 [E], "reward" f32 [E] (last step), "logits" f32 [E, T, n_actions], "enc_ring" f32
+ * [T, E, tokens, dim] (slot-major), "head" int32 (the slot the next step writes).  bytes must be the item's size. */
+int arp_rollout_read(arp_rollout* h, const char* what, void* out, int64_t bytes);
+/* test hook: the value the window kernel writes into the padded tail (time steps L .. T - 1: encodings and return-to-go) and its action id; default 0, 0 */
+int arp_rollout_debug_set_tail(arp_rollout* h, float value, int action);
 
 /* ---- host I/O of path (1) (no GPU involved) -------------------------------
  * Reads n stored chunks of a gzip-chunked dataset (`ob` of data/PPG/trajectory_recorder.py:148-176: one chunk = one row =
@@ -534,6 +574,9 @@ int arp_op_attention_forms(int mode, int impl, const float* qkv, void* out, size
  * out: caller-filled byte buffer as above, rows of D values of the mode's type. */
 int arp_op_qkv_attention(int mode, const float* A, const float* W, const float* bias, void* out, size_t out_bytes, int B, int N, int K, int heads, int causal,
                          int nq);
+/* The rollout session's decide kernel: logits [E, T, n_actions], lens[e] = window length L in [1, T] -> actions_out[e] = argmax of row L - 1 (the lowest
+ * index wins a tie, the first NaN wins: numpy.argmax). */
+int arp_op_rollout_decide(const float* logits, const int32_t* lens, int E, int T, int n_actions, int32_t* actions_out);
 
 #ifdef __cplusplus
 }
