@@ -23,6 +23,8 @@ if os.environ.get("ARP_LIB"):
 MODE_F32, MODE_BF16, MODE_F16, MODE_F16X3, MODE_F16C = 0, 1, 2, 3, 4
 ACT_NONE, ACT_QGELU, ACT_RELU, ACT_TANH, ACT_GELU_TANH = 0, 1, 2, 3, 4
 ATTN_OUT_PLAIN, ATTN_OUT_E4M3, ATTN_OUT_F16C, ATTN_OUT_SPLIT3 = 0, 1, 2, 3  # arp_op_attention_forms
+LN_OUT_F32, LN_OUT_BF16, LN_OUT_F16, LN_OUT_E4M3, LN_OUT_SPLIT3, LN_OUT_F16C, LN_OUT_F16C2 = 0, 1, 2, 3, 4, 5, 6  # arp_op_layernorm_forms
+ASM_LNPRE, ASM_LAT_LN1, ASM_LAT_STATS = 0, 1, 2  # arp_op_vit_assemble
 
 
 class ArpError(RuntimeError):
@@ -239,6 +241,17 @@ SIGNATURES = {
     "arp_op_attention": (_i, [_i, _i, _fp, _fp, _i, _i, _i, _i, _i]),
     "arp_op_attention_forms": (_i, [_i, _i, _fp, _vp, C.c_size_t, _i, _i, _i, _i, _i, _i, _i, _f, _i]),
     "arp_op_qkv_attention": (_i, [_i, _fp, _fp, _fp, _vp, C.c_size_t, _i, _i, _i, _i, _i, _i]),
+    "arp_op_layernorm_forms": (_i, [_i, _fp, C.c_size_t, C.c_size_t, _i32p, _fp, _fp, _vp, C.c_size_t, _i, _i, _i, _f]),
+    "arp_op_row_stats": (_i, [_i, _fp, _vp, C.c_size_t, _vp, C.c_size_t, _i, _i]),
+    "arp_op_vit_assemble": (_i, [_i, _i, _fp, C.c_size_t, _i, C.c_size_t, _fp, C.c_size_t, _fp, _fp, _fp, _fp, _fp, _vp, C.c_size_t, _vp, C.c_size_t,
+                                 _vp, C.c_size_t, _i, _i, _i, _f]),
+    "arp_op_text_embed": (_i, [_i32p, _fp, _i, _fp, _vp, C.c_size_t, _i, _i, _i]),
+    "arp_op_rows_gather": (_i, [_fp, C.c_size_t, _i, _i32p, _i, _vp, C.c_size_t, _i, _i, _i]),
+    "arp_op_l2_normalize": (_i, [_vp, C.c_size_t, _i, _i]),
+    "arp_op_reward": (_i, [_fp, _fp, _f, _vp, C.c_size_t, _i, _i]),
+    "arp_op_convert_f16c": (_i, [_i, _fp, _vp, C.c_size_t, _vp, C.c_size_t, _i, _i]),
+    "arp_op_extract_hi": (_i, [_vp, C.c_size_t, _i, _vp, C.c_size_t, _i, _i]),
+    "arp_op_split3": (_i, [_fp, _vp, C.c_size_t, _i, _i]),
 }
 
 for _name, (_res, _args) in SIGNATURES.items():

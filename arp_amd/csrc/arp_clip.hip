@@ -435,13 +435,9 @@ static int forward_chunk(arp_clip* c, const uint8_t* frames_dev, int nb, ResizeP
             }
             ProfScope ps(c->prof, c->stream, "vit.assemble_ln_pre_ln_1");
             const bool f0 = c->vis.lat_folded && c->lat_stats.p && (D & 15) == 0;
-#define ARP_ASML_CALL(NV)                                                                                                                \
-    hipLaunchKernelGGL((vit_assemble_lat_kernel<T, NV>), dim3(nb * N), dim3(64), 0, c->stream, c->part.as<float>(), S, (size_t)Mp * D, c->cls, c->pos, \
-                       c->lnpre_w, c->lnpre_b, c->x.as<float>(), c->h.as<T>(), c->vis.L[0].ln1_w, c->vis.L[0].ln1_b, N, D, 1e-5f,         \
-                       f0 ? c->lat_stats.as<float>() : nullptr, D >> 4)
-            ARP_NV_DISPATCH(D, ARP_ASML_CALL);
-#undef ARP_ASML_CALL
-            ARP_HIP_OK(hipGetLastError());
+            ARP_TRY(launch_vit_assemble_lat<T>(c->stream, c->part.as<float>(), S, (size_t)Mp * D, c->cls, c->pos, c->lnpre_w, c->lnpre_b, c->x.as<float>(),
+                                               c->h.as<T>(), c->vis.L[0].ln1_w, c->vis.L[0].ln1_b, nb * N, N, D, 1e-5f,
+                                               f0 ? c->lat_stats.as<float>() : nullptr, D >> 4));
             assembled = true;
             c->lat_h0 = !f0;
             c->lat_f0 = f0;
@@ -452,12 +448,7 @@ static int forward_chunk(arp_clip* c, const uint8_t* frames_dev, int nb, ResizeP
                                                          nb * G * G, D, KP)));
     {
         ProfScope ps(c->prof, c->stream, "vit.assemble_ln_pre");
-#define ARP_ASM_CALL(NV)                                                                                                      \
-    hipLaunchKernelGGL((vit_assemble_lnpre_kernel<NV>), dim3((nb * N + 3) / 4), dim3(256), 0, c->stream, c->pe.as<float>(), \
-                       c->cls, c->pos, c->lnpre_w, c->lnpre_b, c->x.as<float>(), nb* N, N, D, 1e-5f)
-        ARP_NV_DISPATCH(D, ARP_ASM_CALL);
-#undef ARP_ASM_CALL
-        ARP_HIP_OK(hipGetLastError());
+        ARP_TRY(launch_vit_assemble_lnpre(c->stream, c->pe.as<float>(), c->cls, c->pos, c->lnpre_w, c->lnpre_b, c->x.as<float>(), nb * N, N, D, 1e-5f));
     }
     }
     ARP_TRY(run_blocks<T>(c, c->vis, "vit", c->x.as<float>(), c->h.as<T>(), c->qkv.as<T>(), c->ao.as<T>(), c->fc.as<T>(), nb, N, 0, c->stats.as<float>()));
@@ -501,25 +492,17 @@ template <typename T> static int run_text(arp_clip* c, const int32_t* tokens, in
     if (ms_host) ARP_TRY(ms.ensure((size_t)np * c->txt.layers * Tw * 4));
     ARP_HIP_OK(hipMemcpyAsync(tok.p, tokens, (size_t)M * 4, hipMemcpyHostToDevice, c->stream));
     ARP_HIP_OK(hipMemcpyAsync(eot.p, eot_rows.data(), (size_t)np * 4, hipMemcpyHostToDevice, c->stream));
-    hipLaunchKernelGGL(text_embed_kernel, dim3((M + 3) / 4), dim3(256), 0, c->stream, tok.as<int>(), c->tok_emb, c->tpos,
-                       x.as<float>(), M, ctx, Tw);
-    ARP_HIP_OK(hipGetLastError());
+    ARP_TRY(launch_text_embed(c->stream, tok.as<int>(), c->tok_emb, c->tpos, x.as<float>(), M, ctx, Tw));
     if (ms_host) { c->ms_out = ms.as<float>(); c->ms_ld = c->txt.layers * Tw; c->ms_rows = eot.as<int>(); }
     const int rb = run_blocks<T>(c, txt, "text", x.as<float>(), h.as<T>(), qkv.as<T>(), ao.as<T>(), fc.as<T>(), np, ctx, 1);
     c->ms_out = nullptr; c->ms_rows = nullptr;
     ARP_TRY(rb);
     // ln_final, EOT row, text_projection (arp_dt/models/openai/layers.py:367-369)
-#define ARP_LNG_CALL(NV)                                                                                                     \
-hipLaunchKernelGGL((layernorm_gather_kernel<T, NV>), dim3((np + 3) / 4), dim3(256), 0, c->stream, x.as<float>(), (size_t)Tw, \
-                   eot.as<int>(), hs.as<T>(), Tw, c->lnf_w, c->lnf_b, np, Tw, 1e-5f)
-    ARP_NV_DISPATCH(Tw, ARP_LNG_CALL);
-#undef ARP_LNG_CALL
-    ARP_HIP_OK(hipGetLastError());
+    ARP_TRY(launch_layernorm_gather<T>(c->stream, x.as<float>(), (size_t)Tw, eot.as<int>(), hs.as<T>(), Tw, c->lnf_w, c->lnf_b, np, Tw, 1e-5f));
     ARP_TRY((gemm<T, float, ACT_NONE, false, SITE_PROJ>(c, "text.proj", hs.p, tproj, nullptr, nullptr, feat.p, np,
                                                         k.embed, Tw)));
     if (normalize) {
-        hipLaunchKernelGGL(l2_normalize_kernel, dim3((np + 3) / 4), dim3(256), 0, c->stream, feat.as<float>(), np, k.embed);
-        ARP_HIP_OK(hipGetLastError());
+        ARP_TRY(launch_l2_normalize(c->stream, feat.as<float>(), np, k.embed));
     }
     const hipMemcpyKind okind = dev_out ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
     if (out_host) ARP_HIP_OK(hipMemcpyAsync(out_host, feat.p, (size_t)np * k.embed * 4, okind, c->stream));
@@ -552,10 +535,7 @@ static int label_dev_single(arp_clip* c, const uint8_t* frames_dev, int n, int H
         ARP_TRY(forward_chunk_dispatch(c, fr, nb, plan));
         ProfScope ps(c->prof, c->stream, "reward");
         // mean over prompts of scale <img_n, txt_p> = scale <img_n, mean_p txt_p>: the same kernel on the mean prompt vector
-        hipLaunchKernelGGL(reward_kernel, dim3((nb + 3) / 4), dim3(256), 0, c->stream, c->feat.as<float>(),
-                           o->prompt_reduce ? o->txt_mean.as<float>() : o->txt_feat.as<float>(), scale, rw, nb, c->cfg.embed);
-        ARP_HIP_OK(hipGetLastError());
-        return 0;
+        return launch_reward(c->stream, c->feat.as<float>(), o->prompt_reduce ? o->txt_mean.as<float>() : o->txt_feat.as<float>(), scale, rw, nb, c->cfg.embed);
     };
     // replay the captured pass
     if (c->lat_graph && small && !c->prof.on && !c->ms_out && !c->pre_bilinear) {
@@ -975,10 +955,7 @@ int arp_clip_encode_image(arp_clip* c, const uint8_t* frames, int n, int H, int 
         const int nb = std::min(mb, n - off);
         ARP_HIP_OK(hipMemcpyAsync(c->frames_in.p, frames + (size_t)off * fb, (size_t)nb * fb, hipMemcpyHostToDevice, c->stream));
         ARP_TRY(forward_chunk_dispatch(c, c->frames_in.as<uint8_t>(), nb, plan));
-        if (normalize) {
-            hipLaunchKernelGGL(l2_normalize_kernel, dim3((nb + 3) / 4), dim3(256), 0, c->stream, c->feat.as<float>(), nb, E);
-            ARP_HIP_OK(hipGetLastError());
-        }
+        if (normalize) ARP_TRY(launch_l2_normalize(c->stream, c->feat.as<float>(), nb, E));
         ARP_HIP_OK(hipMemcpyAsync(out + (size_t)off * E, c->feat.p, (size_t)nb * E * 4, hipMemcpyDeviceToHost, c->stream));
         ARP_HIP_OK(hipStreamSynchronize(c->stream));
     }
@@ -1554,6 +1531,212 @@ int arp_op_qkv_attention(int mode, const float* A, const float* W, const float* 
     if (mode == ARP_MODE_F16) return op_qkv_attn<f16_t>(A, W, bias, o, out_bytes, B, N, K, heads, causal, nq);
     if (mode == ARP_MODE_BF16) return op_qkv_attn<bf16_t>(A, W, bias, o, out_bytes, B, N, K, heads, causal, nq);
     return fail("qkv_attention: 16-bit modes only");
+}
+
+}  // extern "C"
+
+// ---- the towers' row kernels, each through the product's own launch helper, on byte buffers the caller fills (include/arp_hip.h) ----------------------------
+// A CallerBuf goes up before the launch and comes back after it whatever the launcher returned: the caller sees the bytes the kernel left alone.
+namespace {
+struct CallerBuf {
+    DevBuf d;
+    void* host = nullptr;
+    size_t n = 0;
+    int up(void* h, size_t bytes) {
+        host = h; n = bytes;
+        ARP_TRY(d.ensure(std::max<size_t>(bytes, 16)));
+        if (bytes) ARP_HIP_OK(hipMemcpy(d.p, h, bytes, hipMemcpyHostToDevice));
+        return 0;
+    }
+    int down() {
+        if (n) ARP_HIP_OK(hipMemcpy(host, d.p, n, hipMemcpyDeviceToHost));
+        return 0;
+    }
+};
+int up_i32(const int32_t* src, size_t n, DevBuf& d) {
+    ARP_TRY(d.ensure(std::max<size_t>(n * 4, 16)));
+    ARP_HIP_OK(hipMemcpy(d.p, src, n * 4, hipMemcpyHostToDevice));
+    return 0;
+}
+// launch result first, then the synchronisation, then the copies back: the first failure is the one reported
+int finish(int rc, std::initializer_list<CallerBuf*> bufs) {
+    const hipError_t e = hipDeviceSynchronize();
+    for (CallerBuf* b : bufs) {
+        const int r = b->down();
+        if (rc == 0 && r != 0) rc = r;
+    }
+    ARP_TRY(rc);
+    ARP_HIP_OK(e);
+    return 0;
+}
+
+template <typename OutT>
+int op_ln_form(const float* x, size_t in_stride, const int* idx, void* out, int out_stride, const float* w, const float* b, int rows, int D, float eps) {
+    if (idx) {
+        if constexpr (std::is_same_v<OutT, float> || std::is_same_v<OutT, bf16_t> || std::is_same_v<OutT, f16_t>)
+            return launch_layernorm_gather<OutT>(nullptr, x, in_stride, idx, static_cast<OutT*>(out), out_stride, w, b, rows, D, eps);
+        else
+            return fail("layernorm_forms: the gathered kernel is instantiated for the f32, bf16 and binary16 outputs only (run_text)");
+    }
+    Profiler prof;
+    TowerCtx c;
+    c.prof = &prof;
+    return tower_layernorm<OutT>(c, "op.layernorm", x, in_stride, static_cast<OutT*>(out), out_stride, w, b, rows, D, eps);
+}
+
+template <typename T>
+int op_assemble_lat(const float* patch, int S, size_t slice_stride, const float* cls, const float* pos, const float* w, const float* b, float* x, void* h,
+                    const float* w1, const float* b1, int rows, int ntok, int D, float eps, float* stats) {
+    return launch_vit_assemble_lat<T>(nullptr, patch, S, slice_stride, cls, pos, w, b, x, static_cast<T*>(h), w1, b1, rows, ntok, D, eps, stats, D >> 4);
+}
+}  // namespace
+
+extern "C" {
+
+int arp_op_layernorm_forms(int form, const float* x, size_t x_floats, size_t in_stride, const int32_t* row_idx, const float* w, const float* b, void* out,
+                           size_t out_bytes, int out_stride, int rows, int D, float eps) {
+    if (!x || !w || !b || !out || rows <= 0 || D <= 0 || out_stride <= 0) return fail("layernorm_forms: bad argument");
+    size_t esz, row_elems;  // bytes per element of the form's storage type (the unit of out_stride), elements per row
+    switch (form) {
+        case ARP_LN_OUT_F32: esz = 4; row_elems = D; break;
+        case ARP_LN_OUT_BF16: case ARP_LN_OUT_F16: esz = 2; row_elems = D; break;
+        case ARP_LN_OUT_E4M3: esz = 1; row_elems = D; break;
+        case ARP_LN_OUT_SPLIT3: esz = 2; row_elems = (size_t)3 * D; break;
+        case ARP_LN_OUT_F16C: case ARP_LN_OUT_F16C2: esz = 2; row_elems = (size_t)3 * D / 2; break;
+        default: return fail("layernorm_forms: unknown output form");
+    }
+    // the rules of the launchers that consume these rows
+    if ((form == ARP_LN_OUT_F16C || form == ARP_LN_OUT_F16C2) && D % 256)
+        return fail("layernorm_forms: [hi | x4 | dx4] rows feed gemm_c (\"f16c: widths must be multiples of 256\")");
+    if (form == ARP_LN_OUT_SPLIT3 && (3 * D) % 64)
+        return fail("layernorm_forms: (hi, lo, hi) rows are the A operand of a K = 3 D binary16 product (gemm_nt / gemm256_nt: K % 64 == 0)");
+    if ((in_stride & 3) || (out_stride & 3) || in_stride < (size_t)D || (size_t)out_stride < row_elems)
+        return fail("layernorm_forms: strides must be multiples of 4 elements and cover a row");
+    if (row_idx) {
+        for (int r = 0; r < rows; ++r)
+            if (row_idx[r] < 0 || (size_t)row_idx[r] * in_stride + D > x_floats) return fail("layernorm_forms: row index outside x");
+    } else if ((size_t)(rows - 1) * in_stride + D > x_floats) {
+        return fail("layernorm_forms: x shorter than the rows it is read as");
+    }
+    if (out_bytes < ((size_t)(rows - 1) * out_stride + row_elems) * esz) return fail("layernorm_forms: output buffer shorter than its rows");
+    DevBuf dx, dw, db, di;
+    CallerBuf o;
+    ARP_TRY(to_dev<float>(x, x_floats, dx)); ARP_TRY(to_dev<float>(w, D, dw)); ARP_TRY(to_dev<float>(b, D, db));
+    if (row_idx) ARP_TRY(up_i32(row_idx, rows, di));
+    ARP_TRY(o.up(out, out_bytes));
+    const int* idx = row_idx ? di.as<int>() : nullptr;
+    int rc;
+#define ARP_LNF_CASE(F, OutT) \
+    case F: rc = op_ln_form<OutT>(dx.as<float>(), in_stride, idx, o.d.p, out_stride, dw.as<float>(), db.as<float>(), rows, D, eps); break;
+    switch (form) {
+        ARP_LNF_CASE(ARP_LN_OUT_F32, float) ARP_LNF_CASE(ARP_LN_OUT_BF16, bf16_t) ARP_LNF_CASE(ARP_LN_OUT_F16, f16_t) ARP_LNF_CASE(ARP_LN_OUT_E4M3, fp8_t)
+        ARP_LNF_CASE(ARP_LN_OUT_SPLIT3, f16x3_t) ARP_LNF_CASE(ARP_LN_OUT_F16C, f16c_t)
+        default: rc = op_ln_form<f16c2_t>(dx.as<float>(), in_stride, idx, o.d.p, out_stride, dw.as<float>(), db.as<float>(), rows, D, eps); break;
+    }
+#undef ARP_LNF_CASE
+    return finish(rc, {&o});
+}
+
+int arp_op_row_stats(int mode, const float* x, void* xb, size_t xb_bytes, void* stats, size_t stats_bytes, int rows, int D) {
+    if (!x || !xb || !stats || rows <= 0 || D <= 0) return fail("row_stats: bad argument");
+    if (mode != ARP_MODE_BF16 && mode != ARP_MODE_F16) return fail("row_stats: 16-bit modes only");
+    if (D & 127) return fail("row_stats: the folded towers need a width that is a multiple of 128 (run_blocks: one (sum, sum of squares) pair per 128 columns)");
+    if (xb_bytes < (size_t)rows * D * 2 || stats_bytes < (size_t)rows * (D >> 7) * 8) return fail("row_stats: output buffer too short");
+    DevBuf dx;
+    CallerBuf b, s;
+    ARP_TRY(to_dev<float>(x, (size_t)rows * D, dx));
+    ARP_TRY(b.up(xb, xb_bytes)); ARP_TRY(s.up(stats, stats_bytes));
+    const int rc = mode == ARP_MODE_BF16 ? launch_row_stats<bf16_t>(nullptr, dx.as<float>(), b.d.as<bf16_t>(), s.d.as<float>(), rows, D)
+                                         : launch_row_stats<f16_t>(nullptr, dx.as<float>(), b.d.as<f16_t>(), s.d.as<float>(), rows, D);
+    return finish(rc, {&b, &s});
+}
+
+int arp_op_vit_assemble(int mode, int tail, const float* patch, size_t patch_floats, int S, size_t slice_stride, const float* cls, size_t cls_floats,
+                        const float* pos, const float* w, const float* b, const float* w1, const float* b1, void* x, size_t x_bytes, void* h, size_t h_bytes,
+                        void* stats, size_t stats_bytes, int B, int ntok, int D, float eps) {
+    if (!patch || !cls || !pos || !w || !b || !x || B <= 0 || ntok <= 0 || D <= 0 || tail < ARP_ASM_LNPRE || tail > ARP_ASM_LAT_STATS)
+        return fail("vit_assemble: bad argument");
+    const size_t rows = (size_t)B * ntok, prow = (size_t)B * (ntok - 1) * D;
+    if (cls_floats < (size_t)D || x_bytes < rows * D * 4) return fail("vit_assemble: cls or x too short");
+    DevBuf dp, dc, dpos, dw, db, dw1, db1;
+    CallerBuf ox, oh, os;
+    if (tail == ARP_ASM_LNPRE) {
+        if (patch_floats < prow) return fail("vit_assemble: patch matrix too short");
+    } else {
+        if (mode != ARP_MODE_BF16 && mode != ARP_MODE_F16) return fail("vit_assemble: the latency kernel exists in the 16-bit modes only");
+        if (S >= 1 && patch_floats < (size_t)(S - 1) * slice_stride + prow) return fail("vit_assemble: patch slabs too short");
+        if ((slice_stride & 3) && S > 1) return fail("vit_assemble: slab stride must be a multiple of 4 floats");
+        if (!h || h_bytes < rows * D * 2) return fail("vit_assemble: h too short");
+        if (tail == ARP_ASM_LAT_LN1 && (!w1 || !b1)) return fail("vit_assemble: the ln_1 tail needs w1 and b1");
+        if (tail == ARP_ASM_LAT_STATS && (!stats || stats_bytes < rows * (size_t)(D >> 4) * 8)) return fail("vit_assemble: stats too short");
+    }
+    ARP_TRY(to_dev<float>(patch, patch_floats, dp)); ARP_TRY(to_dev<float>(cls, cls_floats, dc));
+    ARP_TRY(to_dev<float>(pos, (size_t)ntok * D, dpos)); ARP_TRY(to_dev<float>(w, D, dw)); ARP_TRY(to_dev<float>(b, D, db));
+    if (w1) ARP_TRY(to_dev<float>(w1, D, dw1));
+    if (b1) ARP_TRY(to_dev<float>(b1, D, db1));
+    ARP_TRY(ox.up(x, x_bytes));
+    int rc;
+    if (tail == ARP_ASM_LNPRE) {
+        rc = launch_vit_assemble_lnpre(nullptr, dp.as<float>(), dc.as<float>(), dpos.as<float>(), dw.as<float>(), db.as<float>(), ox.d.as<float>(), (int)rows, ntok,
+                                       D, eps);
+        return finish(rc, {&ox});
+    }
+    ARP_TRY(oh.up(h, h_bytes));
+    if (tail == ARP_ASM_LAT_STATS) ARP_TRY(os.up(stats, stats_bytes));
+    float* st = tail == ARP_ASM_LAT_STATS ? os.d.as<float>() : nullptr;
+    if (mode == ARP_MODE_BF16)
+        rc = op_assemble_lat<bf16_t>(dp.as<float>(), S, slice_stride, dc.as<float>(), dpos.as<float>(), dw.as<float>(), db.as<float>(), ox.d.as<float>(), oh.d.p,
+                                     dw1.as<float>(), db1.as<float>(), (int)rows, ntok, D, eps, st);
+    else
+        rc = op_assemble_lat<f16_t>(dp.as<float>(), S, slice_stride, dc.as<float>(), dpos.as<float>(), dw.as<float>(), db.as<float>(), ox.d.as<float>(), oh.d.p,
+                                    dw1.as<float>(), db1.as<float>(), (int)rows, ntok, D, eps, st);
+    if (tail == ARP_ASM_LAT_STATS) return finish(rc, {&ox, &oh, &os});
+    return finish(rc, {&ox, &oh});
+}
+
+int arp_op_text_embed(const int32_t* tokens, const float* emb, int vocab, const float* pos, void* x, size_t x_bytes, int rows, int ctx, int D) {
+    if (!tokens || !emb || !pos || !x || vocab <= 0 || rows <= 0 || ctx <= 0 || D <= 0) return fail("text_embed: bad argument");
+    if (D & 3) return fail("text_embed: the width must be a multiple of 4 (float4 accesses)");
+    for (int r = 0; r < rows; ++r)
+        if (tokens[r] < 0 || tokens[r] >= vocab) return fail("text_embed: token id out of range");
+    if (x_bytes < (size_t)rows * D * 4) return fail("text_embed: output buffer too short");
+    DevBuf dt, de, dp;
+    CallerBuf o;
+    ARP_TRY(up_i32(tokens, rows, dt)); ARP_TRY(to_dev<float>(emb, (size_t)vocab * D, de)); ARP_TRY(to_dev<float>(pos, (size_t)ctx * D, dp));
+    ARP_TRY(o.up(x, x_bytes));
+    return finish(launch_text_embed(nullptr, dt.as<int>(), de.as<float>(), dp.as<float>(), o.d.as<float>(), rows, ctx, D), {&o});
+}
+
+int arp_op_rows_gather(const float* x, size_t x_floats, int D, const int32_t* rows, int row_stride, void* out, size_t out_bytes, int ld, int col0, int B) {
+    if (!x || !out || D <= 0 || B <= 0 || col0 < 0 || ld < col0 + D || (!rows && row_stride < 0)) return fail("rows_gather: bad argument");
+    for (int i = 0; i < B; ++i) {
+        if (rows && rows[i] < 0) return fail("rows_gather: negative row index");
+        const size_t r = rows ? (size_t)rows[i] : (size_t)i * row_stride;
+        if ((r + 1) * D > x_floats) return fail("rows_gather: row outside x");
+    }
+    if (out_bytes < ((size_t)(B - 1) * ld + col0 + D) * 4) return fail("rows_gather: output buffer too short");
+    DevBuf dx, dr;
+    CallerBuf o;
+    ARP_TRY(to_dev<float>(x, x_floats, dx));
+    if (rows) ARP_TRY(up_i32(rows, B, dr));
+    ARP_TRY(o.up(out, out_bytes));
+    return finish(launch_rows_gather(nullptr, dx.as<float>(), D, rows ? dr.as<int>() : nullptr, row_stride, o.d.as<float>(), ld, col0, B), {&o});
+}
+
+int arp_op_l2_normalize(void* f, size_t f_bytes, int rows, int E) {
+    if (!f || rows <= 0 || E <= 0 || f_bytes < (size_t)rows * E * 4) return fail("l2_normalize: bad argument");
+    CallerBuf o;
+    ARP_TRY(o.up(f, f_bytes));
+    return finish(launch_l2_normalize(nullptr, o.d.as<float>(), rows, E), {&o});
+}
+
+int arp_op_reward(const float* img, const float* txt_n, float scale, void* reward, size_t reward_bytes, int rows, int E) {
+    if (!img || !txt_n || !reward || rows <= 0 || E <= 0 || reward_bytes < (size_t)rows * 4) return fail("reward: bad argument");
+    DevBuf di, dt;
+    CallerBuf o;
+    ARP_TRY(to_dev<float>(img, (size_t)rows * E, di)); ARP_TRY(to_dev<float>(txt_n, E, dt));
+    ARP_TRY(o.up(reward, reward_bytes));
+    return finish(launch_reward(nullptr, di.as<float>(), dt.as<float>(), scale, o.d.as<float>(), rows, E), {&o});
 }
 
 }  // extern "C"

@@ -787,13 +787,7 @@ template <typename T> int forward(arp_dt* c, bool with_bwd = false) {
             // mix + its binary16 copy for the backward (ac_a_exact) or in binary16 only; the plain binary16 Xb the backward reads comes out of the conversion pass.
             {
                 ProfScope ps(c->prof, c->stream, "dt.enc_convert");
-                if (D % 16 == 0) {
-                    if (c->ac_plan1 >= 2) hipLaunchKernelGGL((convert_f16c16_kernel<true>), dim3(cdiv(Mx * D, 4096)), dim3(256), 0, c->stream, c->bt[c->cur].enc32.as<float>(), c->Xb.as<f16_t>(), c->Xc.as<f16_t>(), Mx, D);
-                    else hipLaunchKernelGGL((convert_f16c16_kernel<false>), dim3(cdiv(Mx * D, 4096)), dim3(256), 0, c->stream, c->bt[c->cur].enc32.as<float>(), c->Xb.as<f16_t>(), c->Xc.as<f16_t>(), Mx, D);
-                } else {
-                    hipLaunchKernelGGL(convert_f16c_kernel, dim3(cdiv(Mx * D, 1024)), dim3(256), 0, c->stream, c->bt[c->cur].enc32.as<float>(), c->Xb.as<f16_t>(), c->Xc.as<f16_t>(), Mx, D);
-                }
-                ARP_HIP_OK(hipGetLastError());
+                ARP_TRY(launch_convert_f16c(c->stream, c->ac_plan1 >= 2, c->bt[c->cur].enc32.as<float>(), c->Xb.as<f16_t>(), c->Xc.as<f16_t>(), Mx, D));
             }
             const int* sc = reinterpret_cast<const int*>(c->wc_scal.p);
             auto mixc = [&](GemmArgs& g, const void* A, const void* W, const float* bias, const int* sptr, int plan) {
@@ -816,8 +810,7 @@ template <typename T> int forward(arp_dt* c, bool with_bwd = false) {
                 c->h1_ptr = c->H1c.p; c->h1_ld = D + D / 2;
             } else {
                 ProfScope ps(c->prof, c->stream, "dt.adapter_fc1");
-                hipLaunchKernelGGL(extract_hi_kernel, dim3(cdiv(Mx * D, 2048)), dim3(256), 0, c->stream, c->H1c.as<f16_t>(), D + D / 2, c->H1.as<f16_t>(), Mx, D);
-                ARP_HIP_OK(hipGetLastError());
+                ARP_TRY(launch_extract_hi(c->stream, c->H1c.as<f16_t>(), D + D / 2, c->H1.as<f16_t>(), Mx, D));
             }
             {
                 GemmArgs g;
@@ -2231,6 +2224,34 @@ int arp_op_adapter_dy(int mode, const float* dz, const float* Wi, const float* A
     if (mode == ARP_MODE_F16) return op_adapter_dy<f16_t>(dz, Wi, A, x, rw, dApre, colsum, dres, R, E, tokens, D);
     if (mode == ARP_MODE_BF16) return op_adapter_dy<bf16_t>(dz, Wi, A, x, rw, dApre, colsum, dres, R, E, tokens, D);
     return fail("arp_op_adapter_dy: 16-bit modes only");
+}
+// The adapter's operand builders through the train step's own launchers (dtops.h::launch_convert_f16c picks the 16- or 4-value kernel; launch_extract_hi).
+// Outputs are byte buffers the caller fills: up before the launch, back after it whatever the launcher returned.
+int arp_op_convert_f16c(int with_dx, const float* x, void* xb, size_t xb_bytes, void* xc, size_t xc_bytes, int rows, int D) {
+    if (!x || !xb || !xc || rows <= 0 || D <= 0) return fail("arp_op_convert_f16c: bad argument");
+    if (xb_bytes < (size_t)rows * D * 2 || xc_bytes < (size_t)rows * D * 3) return fail("arp_op_convert_f16c: output buffer too short");
+    DevBuf dx, db, dc;
+    ARP_TRY(dx.ensure((size_t)rows * D * 4)); ARP_TRY(db.ensure(xb_bytes)); ARP_TRY(dc.ensure(xc_bytes));
+    ARP_HIP_OK(hipMemcpy(dx.p, x, (size_t)rows * D * 4, hipMemcpyHostToDevice));
+    ARP_HIP_OK(hipMemcpy(db.p, xb, xb_bytes, hipMemcpyHostToDevice));
+    ARP_HIP_OK(hipMemcpy(dc.p, xc, xc_bytes, hipMemcpyHostToDevice));
+    const int rc = launch_convert_f16c(nullptr, with_dx != 0, dx.as<float>(), db.as<f16_t>(), dc.as<f16_t>(), (size_t)rows, D);
+    ARP_HIP_OK(hipDeviceSynchronize());
+    ARP_HIP_OK(hipMemcpy(xb, db.p, xb_bytes, hipMemcpyDeviceToHost));
+    ARP_HIP_OK(hipMemcpy(xc, dc.p, xc_bytes, hipMemcpyDeviceToHost));
+    return rc;
+}
+int arp_op_extract_hi(const void* in, size_t in_bytes, int ld, void* out, size_t out_bytes, int rows, int D) {
+    if (!in || !out || rows <= 0 || D <= 0 || ld < D) return fail("arp_op_extract_hi: bad argument");
+    if (in_bytes < ((size_t)(rows - 1) * ld + D) * 2 || out_bytes < (size_t)rows * D * 2) return fail("arp_op_extract_hi: buffer too short");
+    DevBuf di, dout;
+    ARP_TRY(di.ensure(in_bytes)); ARP_TRY(dout.ensure(out_bytes));
+    ARP_HIP_OK(hipMemcpy(di.p, in, in_bytes, hipMemcpyHostToDevice));
+    ARP_HIP_OK(hipMemcpy(dout.p, out, out_bytes, hipMemcpyHostToDevice));
+    const int rc = launch_extract_hi(nullptr, di.as<f16_t>(), ld, dout.as<f16_t>(), (size_t)rows, D);
+    ARP_HIP_OK(hipDeviceSynchronize());
+    ARP_HIP_OK(hipMemcpy(out, dout.p, out_bytes, hipMemcpyDeviceToHost));
+    return rc;
 }
 
 int arp_dt_profile_enable(arp_dt* c, int on) {

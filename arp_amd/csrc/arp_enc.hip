@@ -80,6 +80,13 @@ __global__ __launch_bounds__(256) void split3_kernel(const float* __restrict__ x
     *reinterpret_cast<uint4*>(o + 2 * (size_t)K) = make_uint4(hi[0], hi[1], hi[2], hi[3]);
 }
 
+int launch_split3(hipStream_t stream, const float* src, f16_t* out, size_t rows, int K) {
+    if (K % 8) return fail("f16x3: widths must be multiples of 8");
+    hipLaunchKernelGGL(split3_kernel, dim3((unsigned)((rows * K / 8 + 255) / 256)), dim3(256), 0, stream, src, out, rows, K);
+    ARP_HIP_OK(hipGetLastError());
+    return 0;
+}
+
 // patchify_kernel<float> + split3_kernel in one pass (round 6; f16x3 and f16c modes): the f32 patch matrix is never written (100 MB per 128 frames written and
 // read back).  Same values: each element is loaded once, hi = rn16(v), lo = rn16(v - hi) as split3_kernel forms them.
 __global__ __launch_bounds__(256) void patchify_split3_kernel(const float* __restrict__ img, f16_t* __restrict__ out, int n, int res, int P) {
@@ -319,11 +326,8 @@ int forward_chunk_x3(arp_enc* c, arp_enc::Ws& w, hipStream_t stream, const float
     t.stream = stream; t.prof = &c->prof; t.attn_impl = k.attn_impl; t.gemm_force = c->gemm_force; t.shared_chip = c->shared_chip;
     f16_t* a3 = w.a3.as<f16_t>();
     auto split = [&](const char* site, const float* src, size_t rows, int K) -> int {
-        if (K % 8) return fail("f16x3: widths must be multiples of 8");
         ProfScope ps(c->prof, stream, site);
-        hipLaunchKernelGGL(split3_kernel, dim3((unsigned)((rows * K / 8 + 255) / 256)), dim3(256), 0, stream, src, a3, rows, K);
-        ARP_HIP_OK(hipGetLastError());
-        return 0;
+        return launch_split3(stream, src, a3, rows, K);
     };
     {   // frames -> (hi, lo, hi) patch triples in one pass
         ProfScope ps(c->prof, stream, "m3ae.patchify");
@@ -779,6 +783,20 @@ int arp_op_gemm_f16c(int plan, const float* A, const float* W, const float* bias
     ARP_HIP_OK(hipDeviceSynchronize());
     ARP_HIP_OK(hipMemcpy(out, dO.p, (size_t)M * N * 4, hipMemcpyDeviceToHost));
     return 0;
+}
+
+// split3_kernel through the f16x3 encoder's own launcher: x f32 [rows, K] -> out, a byte buffer the caller fills (up before the launch, back after it
+// whatever the launcher returned), rows of 3 K binary16 values [hi | lo | hi]
+int arp_op_split3(const float* x, void* out, size_t out_bytes, int rows, int K) {
+    if (!x || !out || rows <= 0 || K <= 0 || out_bytes < (size_t)rows * K * 6) return fail("arp_op_split3: bad argument");
+    DevBuf dx, dout;
+    ARP_TRY(dx.ensure((size_t)rows * K * 4)); ARP_TRY(dout.ensure(out_bytes));
+    ARP_HIP_OK(hipMemcpy(dx.p, x, (size_t)rows * K * 4, hipMemcpyHostToDevice));
+    ARP_HIP_OK(hipMemcpy(dout.p, out, out_bytes, hipMemcpyHostToDevice));
+    const int rc = launch_split3(nullptr, dx.as<float>(), dout.as<f16_t>(), (size_t)rows, K);
+    ARP_HIP_OK(hipDeviceSynchronize());
+    ARP_HIP_OK(hipMemcpy(out, dout.p, out_bytes, hipMemcpyDeviceToHost));
+    return rc;
 }
 
 }  // extern "C"

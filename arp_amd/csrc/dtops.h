@@ -528,6 +528,26 @@ static __global__ __launch_bounds__(256) void extract_hi_kernel(const f16_t* __r
     const int c = (int)(i - r * D);
     *reinterpret_cast<u32x4_v*>(out + i) = *reinterpret_cast<const u32x4_v*>(in + r * (size_t)ld + c);
 }
+// enc -> xb and the [hi | x4 (| dx4)] rows: sixteen values per lane where the width allows it (with_dx = the consumer's plan wants the dx4 segment), else the
+// four-value form, which always writes dx4.  A row is 3 D bytes and the four-value form stores 8 bytes at a time: D % 8.
+static int launch_convert_f16c(hipStream_t stream, bool with_dx, const float* in, f16_t* xb, f16_t* xc, size_t rows, int D) {
+    if (D <= 0 || D % 8) return fail("convert_f16c: the width must be a multiple of 8 (8-byte stores into rows of 3 D bytes)");
+    const size_t n = rows * (size_t)D;
+    if (D % 16 == 0) {
+        if (with_dx) hipLaunchKernelGGL((convert_f16c16_kernel<true>), dim3((unsigned)((n + 4095) / 4096)), dim3(256), 0, stream, in, xb, xc, rows, D);
+        else hipLaunchKernelGGL((convert_f16c16_kernel<false>), dim3((unsigned)((n + 4095) / 4096)), dim3(256), 0, stream, in, xb, xc, rows, D);
+    } else {
+        hipLaunchKernelGGL(convert_f16c_kernel, dim3((unsigned)((n + 1023) / 1024)), dim3(256), 0, stream, in, xb, xc, rows, D);
+    }
+    ARP_HIP_OK(hipGetLastError());
+    return 0;
+}
+static int launch_extract_hi(hipStream_t stream, const f16_t* in, int ld, f16_t* out, size_t rows, int D) {
+    if (D <= 0 || D % 8 || ld % 8 || ld < D) return fail("extract_hi: width and row stride must be multiples of 8 (16-byte copies)");
+    hipLaunchKernelGGL(extract_hi_kernel, dim3((unsigned)((rows * (size_t)D + 2047) / 2048)), dim3(256), 0, stream, in, ld, out, rows, D);
+    ARP_HIP_OK(hipGetLastError());
+    return 0;
+}
 // max |w - rn16(w)| and max |w| of a weight tensor -> mx[0], mx[1] (as non-negative float bits; mx zeroed by the caller)
 static __global__ __launch_bounds__(256) void wc_absmax_kernel(const float* __restrict__ w, size_t n, unsigned int* __restrict__ mx) {
     float md = 0.f, mw = 0.f;

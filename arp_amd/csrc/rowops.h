@@ -101,6 +101,19 @@ __global__ __launch_bounds__(256) void layernorm_gather_kernel(const float* __re
     ln_row_store<OutT, NV>(v, D, lane, w, b, eps, out + (size_t)row * out_stride);
 }
 
+template <typename OutT>
+static int launch_layernorm_gather(hipStream_t stream, const float* in, size_t in_stride, const int* row_idx, OutT* out, int out_stride, const float* w,
+                                   const float* b, int rows, int D, float eps) {
+    if (D % 4 || D > ROW_MAX_V4 * 256) return fail("layernorm_gather: unsupported width " + std::to_string(D));
+#define ARP_LNG_CALL(NV)                                                                                                                         \
+    hipLaunchKernelGGL((layernorm_gather_kernel<OutT, NV>), dim3((rows + 3) / 4), dim3(256), 0, stream, in, in_stride, row_idx, out, out_stride, w, b, \
+                       rows, D, eps)
+    ARP_NV_DISPATCH(D, ARP_LNG_CALL);
+#undef ARP_LNG_CALL
+    ARP_HIP_OK(hipGetLastError());
+    return 0;
+}
+
 // ViT token assembly + ln_pre (arp_dt/models/openai/layers.py:301-322):
 //   row (b, 0)   = class_embedding + pos[0]
 //   row (b, 1+p) = patch_embed[b*GG + p] + pos[1+p]
@@ -129,6 +142,17 @@ __global__ __launch_bounds__(256) void vit_assemble_lnpre_kernel(const float* __
         }
     }
     ln_row_store<float, NV>(v, D, lane, w, b, eps, x + (size_t)row * D);
+}
+
+static int launch_vit_assemble_lnpre(hipStream_t stream, const float* patch, const float* cls, const float* pos, const float* w, const float* b, float* x,
+                                     int rows, int ntok, int D, float eps) {
+    if (D % 4 || D > ROW_MAX_V4 * 256) return fail("vit_assemble_lnpre: unsupported width " + std::to_string(D));
+#define ARP_ASM_CALL(NV) \
+    hipLaunchKernelGGL((vit_assemble_lnpre_kernel<NV>), dim3((rows + 3) / 4), dim3(256), 0, stream, patch, cls, pos, w, b, x, rows, ntok, D, eps)
+    ARP_NV_DISPATCH(D, ARP_ASM_CALL);
+#undef ARP_ASM_CALL
+    ARP_HIP_OK(hipGetLastError());
+    return 0;
 }
 
 // Latency-path variant (one frame, or a few): the patch embedding arrives as S split-K slabs of the skinny GEMM, and the row that
@@ -218,6 +242,22 @@ __global__ __launch_bounds__(64) void vit_assemble_lat_kernel(const float* __res
     ln_row_store<T, NV>(v, D, lane, w1, b1, eps, h + (size_t)row * D);
 }
 
+// rows = B * ntok; stats == null: h = ln_1(x) with (w1, b1); else h = the operand copy of x and stats [rows][parts][2]
+template <typename T>
+static int launch_vit_assemble_lat(hipStream_t stream, const float* patch, int S, size_t slice_stride, const float* cls, const float* pos, const float* w,
+                                   const float* b, float* x, T* h, const float* w1, const float* b1, int rows, int ntok, int D, float eps, float* stats,
+                                   int parts) {
+    if (D % 4 || D > ROW_MAX_V4 * 256) return fail("vit_assemble_lat: unsupported width " + std::to_string(D));
+    if (S < 1 || S > 4) return fail("vit_assemble_lat: the kernel sums 1 to 4 split-K slabs, not " + std::to_string(S));  // (it holds three extra slabs in registers)
+#define ARP_ASML_CALL(NV)                                                                                                                             \
+    hipLaunchKernelGGL((vit_assemble_lat_kernel<T, NV>), dim3(rows), dim3(64), 0, stream, patch, S, slice_stride, cls, pos, w, b, x, h, w1, b1, ntok, D, eps, \
+                       stats, parts)
+    ARP_NV_DISPATCH(D, ARP_ASML_CALL);
+#undef ARP_ASML_CALL
+    ARP_HIP_OK(hipGetLastError());
+    return 0;
+}
+
 // Text token embedding (arp_dt/models/openai/layers.py:364-365): x[p*ctx + t] = tok_emb[tokens] + pos[t]
 static __global__ __launch_bounds__(256) void text_embed_kernel(const int* __restrict__ tokens, const float* __restrict__ emb,
                                                          const float* __restrict__ pos, float* __restrict__ x, int rows, int ctx,
@@ -235,6 +275,12 @@ static __global__ __launch_bounds__(256) void text_embed_kernel(const int* __res
     }
 }
 
+static int launch_text_embed(hipStream_t stream, const int* tokens, const float* emb, const float* pos, float* x, int rows, int ctx, int D) {
+    hipLaunchKernelGGL(text_embed_kernel, dim3((rows + 3) / 4), dim3(256), 0, stream, tokens, emb, pos, x, rows, ctx, D);
+    ARP_HIP_OK(hipGetLastError());
+    return 0;
+}
+
 // f[r, :] /= ||f[r, :]||   (arp_dt/models/openai/layers.py:429-439), in place, f32.
 static __global__ __launch_bounds__(256) void l2_normalize_kernel(float* __restrict__ f, int rows, int E) {
     const int lane = threadIdx.x & 63;
@@ -245,6 +291,12 @@ static __global__ __launch_bounds__(256) void l2_normalize_kernel(float* __restr
     for (int c = lane; c < E; c += 64) s += r[c] * r[c];
     const float inv = 1.0f / sqrtf(wave_sum(s));
     for (int c = lane; c < E; c += 64) r[c] *= inv;
+}
+
+static int launch_l2_normalize(hipStream_t stream, float* f, int rows, int E) {
+    hipLaunchKernelGGL(l2_normalize_kernel, dim3((rows + 3) / 4), dim3(256), 0, stream, f, rows, E);
+    ARP_HIP_OK(hipGetLastError());
+    return 0;
 }
 
 // reward[i] = exp(logit_scale) * < img[i]/||img[i]||, txt_n >  -- the "image x text GEMV"
@@ -264,6 +316,12 @@ static __global__ __launch_bounds__(256) void reward_kernel(const float* __restr
     ss = wave_sum(ss);
     dt = wave_sum(dt);
     if (lane == 0) reward[row] = scale * (dt / sqrtf(ss));
+}
+
+static int launch_reward(hipStream_t stream, const float* img, const float* txt_n, float scale, float* reward, int rows, int E) {
+    hipLaunchKernelGGL(reward_kernel, dim3((rows + 3) / 4), dim3(256), 0, stream, img, txt_n, scale, reward, rows, E);
+    ARP_HIP_OK(hipGetLastError());
+    return 0;
 }
 
 }  // namespace arp

@@ -106,6 +106,13 @@ __global__ __launch_bounds__(256) void row_stats_kernel(const float* __restrict_
     }
 }
 
+template <typename T>
+static int launch_row_stats(hipStream_t stream, const float* x, T* xb, float* stats, int rows, int D) {
+    hipLaunchKernelGGL((row_stats_kernel<T>), dim3((rows + 3) / 4), dim3(256), 0, stream, x, xb, stats, rows, D);
+    ARP_HIP_OK(hipGetLastError());
+    return 0;
+}
+
 // optional LayerNorm-fold plumbing of one GEMM launch
 struct GemmFold {
     const float* stats = nullptr;  // consumer
@@ -167,12 +174,14 @@ static __global__ __launch_bounds__(256) void rows_gather_kernel(const float* __
     const size_t row = rows ? (size_t)rows[b] : (size_t)b * row_stride;
     out[(size_t)b * ld + col0 + d] = x[row * D + d];
 }
-static int tower_export_rows(TowerCtx& c, const float* x, int D, int layer, int B, int N) {
-    if (!c.ms_out) return 0;
-    hipLaunchKernelGGL(rows_gather_kernel, dim3((unsigned)(((size_t)B * D + 255) / 256)), dim3(256), 0, c.stream, x, D, c.ms_rows, N, c.ms_out, c.ms_ld,
-                       layer * D, B);
+static int launch_rows_gather(hipStream_t stream, const float* x, int D, const int* rows, int row_stride, float* out, int ld, int col0, int B) {
+    hipLaunchKernelGGL(rows_gather_kernel, dim3((unsigned)(((size_t)B * D + 255) / 256)), dim3(256), 0, stream, x, D, rows, row_stride, out, ld, col0, B);
     ARP_HIP_OK(hipGetLastError());
     return 0;
+}
+static int tower_export_rows(TowerCtx& c, const float* x, int D, int layer, int B, int N) {
+    if (!c.ms_out) return 0;
+    return launch_rows_gather(c.stream, x, D, c.ms_rows, N, c.ms_out, c.ms_ld, layer * D, B);
 }
 
 template <typename T, typename OutT, int ACT, bool RESID, int SITE>
@@ -476,8 +485,7 @@ static int run_blocks(TowerCtx& c, const TowerW& tw, const char* tag, float* x, 
         prod.xb_out = h; prod.ldxb = D; prod.stats_out = stats;
         {
             ProfScope ps(*c.prof, c.stream, s_st.c_str());
-            hipLaunchKernelGGL((row_stats_kernel<T>), dim3((M + 3) / 4), dim3(256), 0, c.stream, x, h, stats, M, D);
-            ARP_HIP_OK(hipGetLastError());
+            ARP_TRY(launch_row_stats<T>(c.stream, x, h, stats, M, D));
         }
         for (int i = 0; i < tw.layers; ++i) {
             const LayerW& L = tw.L[i];

@@ -574,6 +574,60 @@ int arp_op_attention_forms(int mode, int impl, const float* qkv, void* out, size
  * out: caller-filled byte buffer as above, rows of D values of the mode's type. */
 int arp_op_qkv_attention(int mode, const float* A, const float* W, const float* bias, void* out, size_t out_bytes, int B, int N, int K, int heads, int causal,
                          int nq);
+/* ---- the towers' row kernels and the operand converters, each through the launch helper the product itself calls ----
+ * Every output is a raw byte buffer the CALLER fills, uploaded before the launch and downloaded after it (also when the launcher refuses: its error is
+ * returned unchanged), so the caller sees every byte the kernel did not write.
+ *
+ * arp_op_layernorm_forms: out[r] = LayerNorm(x[r * in_stride .. + D]; w, b, eps) in one of the output forms the product instantiates.  out_stride counts
+ * elements of the form's storage type (the unit the product passes):
+ *   ARP_LN_OUT_F32 / BF16 / F16   D values of 4 / 2 / 2 bytes
+ *   ARP_LN_OUT_E4M3               D bytes, e4m3 (round to nearest even, saturating at +-448)
+ *   ARP_LN_OUT_SPLIT3             3 D binary16 values [hi | lo | hi]; refused unless 3 D % 64 == 0, the K rule of the binary16 GEMM that reads the rows
+ *   ARP_LN_OUT_F16C / F16C2       3 D bytes = 3 D / 2 binary16 units [hi: binary16 x D | x4: e2m1 x D | dx4: e2m1 x D]; F16C leaves the dx4 bytes alone;
+ *                                 refused unless D % 256 == 0 (the rule of the f16c encoder's GEMM launcher)
+ * D % 4 == 0 and D <= 2048 (the launcher's rule); strides are multiples of 4 elements.  x holds x_floats floats.  row_idx != NULL (f32, bf16, binary16
+ * forms): row r reads x[row_idx[r] * in_stride ..] on the gathered kernel (the text tower's EOT rows). */
+#define ARP_LN_OUT_F32 0
+#define ARP_LN_OUT_BF16 1
+#define ARP_LN_OUT_F16 2
+#define ARP_LN_OUT_E4M3 3
+#define ARP_LN_OUT_SPLIT3 4
+#define ARP_LN_OUT_F16C 5
+#define ARP_LN_OUT_F16C2 6
+int arp_op_layernorm_forms(int form, const float* x, size_t x_floats, size_t in_stride, const int32_t* row_idx, const float* w, const float* b, void* out,
+                           size_t out_bytes, int out_stride, int rows, int D, float eps);
+/* row_stats_kernel (csrc/tower.h; 16-bit modes, D % 128 == 0): xb [rows, D] = x in the mode's type, stats [rows][D / 128][2] f32 = per-128-column
+ * (sum, sum of squares). */
+int arp_op_row_stats(int mode, const float* x, void* xb, size_t xb_bytes, void* stats, size_t stats_bytes, int rows, int D);
+/* ViT token assembly (csrc/rowops.h): x [B * ntok, D] f32 = ln_pre(class / patch embedding + position; w, b).
+ *   ARP_ASM_LNPRE      vit_assemble_lnpre_kernel: patch [B * (ntok - 1), D]; mode, S, slice_stride, h, stats unused
+ *   ARP_ASM_LAT_LN1    vit_assemble_lat_kernel (16-bit modes): patch = S split-K slabs slice_stride floats apart, summed in slab order; h [B * ntok, D] in
+ *                      the mode's type = LayerNorm(x; w1, b1)
+ *   ARP_ASM_LAT_STATS  the same kernel's folded tail: h = x in the mode's type, stats [B * ntok][D / 16][2] f32: strip 0 = the row's (sum, sum of squares),
+ *                      every other strip 0
+ * S outside 1 .. 4 is refused (the kernel holds three extra slabs).  cls holds cls_floats >= D floats: the class embedding first; anything behind it is what
+ * a class row would read if the kernel added slabs to it. */
+#define ARP_ASM_LNPRE 0
+#define ARP_ASM_LAT_LN1 1
+#define ARP_ASM_LAT_STATS 2
+int arp_op_vit_assemble(int mode, int tail, const float* patch, size_t patch_floats, int S, size_t slice_stride, const float* cls, size_t cls_floats,
+                        const float* pos, const float* w, const float* b, const float* w1, const float* b1, void* x, size_t x_bytes, void* h, size_t h_bytes,
+                        void* stats, size_t stats_bytes, int B, int ntok, int D, float eps);
+/* x[r] = emb[tokens[r]] + pos[r % ctx]  (f32 [rows, D], D % 4 == 0; emb [vocab, D], pos [ctx, D]) */
+int arp_op_text_embed(const int32_t* tokens, const float* emb, int vocab, const float* pos, void* x, size_t x_bytes, int rows, int ctx, int D);
+/* out[b * ld + col0 + d] = x[row(b) * D + d], row(b) = rows[b], or b * row_stride when rows == NULL  (f32) */
+int arp_op_rows_gather(const float* x, size_t x_floats, int D, const int32_t* rows, int row_stride, void* out, size_t out_bytes, int ld, int col0, int B);
+/* f [rows, E] f32, in place: f[r] /= ||f[r]|| */
+int arp_op_l2_normalize(void* f, size_t f_bytes, int rows, int E);
+/* reward[r] = scale * <img[r], txt_n> / ||img[r]||  (f32) */
+int arp_op_reward(const float* img, const float* txt_n, float scale, void* reward, size_t reward_bytes, int rows, int E);
+/* The policy step's operand builders (csrc/dtops.h) through the function that picks between the 16- and the 4-value kernel (D % 16 == 0 or not; D % 8):
+ * x f32 [rows, D] -> xb [rows, D] binary16 and xc, rows of 3 D bytes [hi | x4 | dx4]; with_dx = 0 leaves the dx4 bytes alone on the 16-value kernel (the
+ * 4-value kernel always writes them).  arp_op_extract_hi: in = binary16 rows of stride ld -> out [rows, D] (D, ld % 8). */
+int arp_op_convert_f16c(int with_dx, const float* x, void* xb, size_t xb_bytes, void* xc, size_t xc_bytes, int rows, int D);
+int arp_op_extract_hi(const void* in, size_t in_bytes, int ld, void* out, size_t out_bytes, int rows, int D);
+/* The f16x3 encoder's split pass: x f32 [rows, K] -> rows of 3 K binary16 values [hi | lo | hi], hi = rn16(x), lo = rn16(x - hi)  (K % 8 == 0) */
+int arp_op_split3(const float* x, void* out, size_t out_bytes, int rows, int K);
 /* The rollout session's decide kernel: logits [E, T, n_actions], lens[e] = window length L in [1, T] -> actions_out[e] = argmax of row L - 1 (the lowest
  * index wins a tie, the first NaN wins: numpy.argmax). */
 int arp_op_rollout_decide(const float* logits, const int32_t* lens, int E, int T, int n_actions, int32_t* actions_out);

@@ -1,5 +1,6 @@
 """Host-side encoders / decoders of the narrow number formats the kernels store (binary16, bf16, OCP e2m1 nibbles, OCP e4m3 bytes), shared by the
-op-level GPU test modules (tests/test_gemm_epilogues_gpu.py, tests/test_attention_forms_gpu.py).  Plain numpy; nothing here calls the library."""
+op-level GPU test modules (tests/test_gemm_epilogues_gpu.py, tests/test_attention_forms_gpu.py, tests/test_row_kernels_gpu.py).  Plain numpy; nothing
+here calls the library."""
 import numpy as np
 
 from conftest import bf16_round
@@ -19,6 +20,30 @@ def _val16(b, mode):
     if mode == F16:
         return b.view(np.float16).astype(np.float64)
     return (b.astype(np.uint32) << 16).view(np.float32).astype(np.float64)
+
+
+# format -> (significand bits incl. the hidden one, exponent of the smallest normal, largest finite value, what an overflow becomes)
+_FORMATS = {"f16": (11, -14, 65504.0, np.inf), "bf16": (8, -126, float.fromhex("0x1.fep127"), np.inf), "e4m3": (4, -6, 448.0, 448.0),
+            "e2m1": (2, 0, 6.0, 6.0)}
+
+
+def quantize(x, fmt):
+    """float64 -> the format's round-to-nearest-even value, as float64, in ONE rounding (no detour through f32): subnormals on the format's own grid,
+    e4m3 / e2m1 saturating at their largest value, binary16 / bf16 overflowing to infinity.  Monotone non-decreasing in x, which is what the acceptance
+    rule q(v - delta) <= stored <= q(v + delta) of tests/test_row_kernels_gpu.py rests on."""
+    p, emin, vmax, over = _FORMATS[fmt]
+    x = np.asarray(x, np.float64)
+    _, e = np.frexp(x)                           # |x| in [2^(e-1), 2^e)
+    ulp = np.ldexp(1.0, np.maximum(e, emin + 1) - p)
+    q = np.rint(x / ulp) * ulp                   # x / ulp is exact (a power of two); rint rounds half to even
+    return np.where(np.abs(q) > vmax, np.copysign(over, x), q)
+
+
+def fp4_codes_signed(x):
+    """f32 / f64 values -> e2m1 codes of their round-to-nearest-even, saturating quantisation; the sign bit is the value's own (a negative value that
+    rounds to zero keeps it, as csrc/common.h::host_f2fp4 does)"""
+    x = np.asarray(x, np.float64)
+    return (np.searchsorted(_GRID, np.abs(quantize(x, "e2m1"))) | np.where(np.signbit(x), 8, 0)).astype(np.uint8)
 
 
 _GRID = np.array([0.0, 0.5, 1.0, 1.5, 2.0, 3.0, 4.0, 6.0])
