@@ -176,6 +176,14 @@ SIGNATURES = {
     "arp_ft_set_batch": (_i, [_vp, _fp, _fp, _fp, _fp, _fp, _i32p, _i]),
     "arp_ft_forward": (_i, [_vp, _fp, _fp, _fp]),
     "arp_ft_encode": (_i, [_vp, _i, _fp, _fp, _i, _fp]),
+    "arp_ft_reward_set_text": (_i, [_vp, _vp, _i32p, _i]),
+    "arp_ft_reward_set_reduce": (_i, [_vp, _i]),
+    "arp_ft_reward_dev_async": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
+    "arp_ft_reward": (_i, [_vp, _vp, _u8p, _i, _i, _i, _i, _i, _fp]),
+    "arp_ft_reward_set_rows": (_i, [_vp, _i]),
+    "arp_ft_reward_stats": (_i, [_vp, _i64p]),
+    "arp_op_ft_rows_gemm": (_i, [_i, _i, _fp, _i, _fp, _i, _fp, _fp, _i, _i, _i, _i, _i, _i, _i]),
+    "arp_op_ft_reward":(_i, [_fp, _fp, _f, _fp, _i, _i, _f, _fp, _i, _i]),
     "arp_ft_backward": (_i, [_vp]),
     "arp_ft_train_step": (_i, [_vp, C.c_float, _fp]),
     "arp_ft_train_step_async": (_i, [_vp, C.c_float]),
@@ -215,6 +223,7 @@ SIGNATURES = {
     "arp_dt_set_batch_indices": (_i, [_vp, _vp, _i64p, _i, _i]),
     "arp_rollout_create": (_i, [_vp, _vp, _i, _i, _i, _f, C.POINTER(_vp)]),
     "arp_rollout_create_with_encoder": (_i, [_vp, _vp, _vp, _i, _i, _i, _f, C.POINTER(_vp)]),
+    "arp_rollout_create_ft": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _f, C.POINTER(_vp)]),
     "arp_rollout_destroy": (_i, [_vp]),
     "arp_rollout_reset": (_i, [_vp, _i32p, _i, _fp]),
     "arp_rollout_set_lut": (_i, [_vp, _fp]),

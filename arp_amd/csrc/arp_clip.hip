@@ -103,6 +103,10 @@ struct arp_clip : ClipModel {
     std::map<long long, std::unique_ptr<ResizePlan>> plans;
 
     DevBuf ms_keep;         // multi-scale export buffer kept between calls of the online adapter reward (a hipMalloc per call would cost more than the head)
+    // resident reward path of the fine-tune head (clip_internal.h: clip_ms_prepare / clip_ms_enqueue): the export the head reads in place, and the centre
+    // crop of the fine-tune transform.  res_gen counts every move of a buffer a captured pass of the head may hold a pointer into.
+    DevBuf ms_res, crop_buf;
+    uint64_t res_gen = 0;
 
     // workspace for `ws_frames` frames
     int ws_frames = 0;
@@ -380,6 +384,7 @@ static int ensure_workspace(arp_clip* c, int frames) {
     ARP_TRY(c->feat.ensure(B * k.embed * 4));
     ARP_TRY(c->stats.ensure(M * (size_t)std::max(D >> 7, 1) * 8));
     c->ws_frames = frames;
+    c->res_gen += 1;
     return 0;
 }
 
@@ -653,6 +658,100 @@ int clip_stream_of(arp_clip* c, hipStream_t* stream, int* device) {
     ARP_TRY(check_ready(c, true));
     *stream = c->stream;
     *device = c->cfg.device;
+    return 0;
+}
+
+int clip_ms_info(arp_clip* c, ClipMsInfo* out) {
+    ARP_TRY(check_ready(c, false));
+    if (c->primary) return fail("a part stream's sibling is not a handle of its own");
+    *out = ClipMsInfo{c->cfg.width, c->vis.layers, c->cfg.embed, c->cfg.txt_width, c->txt.layers, c->cfg.max_batch, c->cfg.device, c->stream};
+    return 0;
+}
+
+// dst[f, y, x, :] = src[f, y0 + y, x0 + x, :]: the centre crop of the clip_ft labelling branch (label_reward.py:15-36,203) on frames that never left the device
+static __global__ __launch_bounds__(256) void crop_u8_kernel(const uint8_t* __restrict__ src, uint8_t* __restrict__ dst, int n, int H, int W, int y0, int x0,
+                                                             int cs) {
+    const size_t row_bytes = (size_t)cs * 3, total = (size_t)n * cs * row_bytes;
+    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (size_t)gridDim.x * 256) {
+        const size_t r = i / row_bytes, b = i - r * row_bytes;
+        const size_t f = r / cs, y = r - f * cs;
+        dst[i] = src[((f * H + y0 + y) * W + x0) * 3 + b];
+    }
+}
+
+// the frames the fine-tune transform's resize reads: the whole frame, or its centre crop of side W / 2
+static int ms_finetune_geometry(const arp_clip* c, int H, int W, int use_crop, int* h, int* w, int* y0, int* x0) {
+    const int R = c->cfg.img_res;
+    *h = H; *w = W; *y0 = 0; *x0 = 0;
+    if (use_crop) {
+        const int cs = W / 2;
+        if (cs <= 0 || cs > H) return fail("use_crop: the centre crop of side W / 2 does not fit the frame");
+        *h = *w = cs;
+        *y0 = (int)((H - cs) / 2); *x0 = (int)((W - cs) / 2);
+    }
+    if ((*h != R) != (*w != R)) return fail("the reference resizes only when BOTH sides differ from 224 (clip_multiscale_adapter.py:127): "
+                                            "a frame with exactly one side at 224 cannot enter the tower");
+    return 0;
+}
+
+int clip_ms_prepare(arp_clip* c, int nb, int H, int W, int use_crop, int transform, uint64_t* generation, int* capturable) {
+    ARP_TRY(check_ready(c, false));
+    if (c->primary) return fail("a part stream's sibling is not a handle of its own");
+    if (nb <= 0 || nb > c->cfg.max_batch) return fail("clip_ms_prepare: 1 .. max_batch frames per pass");
+    if (H <= 0 || W <= 0 || H > 0xffff || W > 0xffff) return fail("bad frame geometry");
+    if (transform != CLIP_TF_FINETUNE && transform != CLIP_TF_LABEL) return fail("transform is 0 (fine-tune: bilinear) or 1 (label: Pillow bicubic)");
+    ARP_HIP_OK(hipSetDevice(c->cfg.device));
+    const bool small = (long)nb * c->ntok() <= c->lat_rows;
+    size_t crop_bytes = 0;
+    if (transform == CLIP_TF_LABEL) {
+        ResizePlan* plan;
+        ARP_TRY(get_plan(c, H, W, use_crop, &plan, small));
+    } else {
+        int h, w, y0, x0;
+        ARP_TRY(ms_finetune_geometry(c, H, W, use_crop, &h, &w, &y0, &x0));
+        if (use_crop) crop_bytes = (size_t)nb * h * w * 3;
+    }
+    const size_t ms_bytes = (size_t)nb * c->vis.layers * c->cfg.width * 4;
+    if (ms_bytes > c->ms_res.bytes || crop_bytes > c->crop_buf.bytes) {
+        ARP_HIP_OK(hipStreamSynchronize(c->stream));  // (a pass still in flight reads the buffers about to move)
+        ARP_TRY(c->ms_res.ensure(ms_bytes));
+        ARP_TRY(c->crop_buf.ensure(crop_bytes));
+        c->res_gen += 1;
+    }
+    ARP_TRY(ensure_workspace(c, nb));
+    *generation = c->res_gen;
+    *capturable = c->lat_graph && small && !c->prof.on ? 1 : 0;
+    return 0;
+}
+
+int clip_ms_enqueue(arp_clip* c, const uint8_t* frames_dev, int nb, int H, int W, int use_crop, int transform, const float** inter, const float** final_feat) {
+    if (!c || !frames_dev || !inter || !final_feat) return fail("null argument");
+    if (nb <= 0 || nb > c->ws_frames || (size_t)nb * c->vis.layers * c->cfg.width * 4 > c->ms_res.bytes) return fail("clip_ms_enqueue: call clip_ms_prepare first");
+    ResizePlan* plan = nullptr;
+    const uint8_t* src = frames_dev;
+    int pre = 0;
+    if (transform == CLIP_TF_LABEL) {
+        ARP_TRY(get_plan(c, H, W, use_crop, &plan, (long)nb * c->ntok() <= c->lat_rows));
+    } else {
+        int h, w, y0, x0;
+        ARP_TRY(ms_finetune_geometry(c, H, W, use_crop, &h, &w, &y0, &x0));
+        if (use_crop) {
+            const size_t total = (size_t)nb * h * w * 3;
+            if (total > c->crop_buf.bytes) return fail("clip_ms_enqueue: call clip_ms_prepare first");
+            ProfScope ps(c->prof, c->stream, "crop");
+            hipLaunchKernelGGL(crop_u8_kernel, dim3((unsigned)std::min<size_t>((total + 255) / 256, 4096)), dim3(256), 0, c->stream, frames_dev,
+                               c->crop_buf.as<uint8_t>(), nb, H, W, y0, x0, h);
+            ARP_HIP_OK(hipGetLastError());
+            src = c->crop_buf.as<uint8_t>();
+        }
+        pre = (h << 16) | w;
+    }
+    c->ms_out = c->ms_res.as<float>(); c->ms_ld = c->vis.layers * c->cfg.width; c->ms_rows = nullptr; c->pre_bilinear = pre;
+    const int r = forward_chunk_dispatch(c, src, nb, plan);
+    c->ms_out = nullptr; c->pre_bilinear = 0;
+    ARP_TRY(r);
+    *inter = c->ms_res.as<float>();
+    *final_feat = c->feat.as<float>();
     return 0;
 }
 

@@ -25,9 +25,11 @@
 #include <vector>
 
 #include "../../include/arp_hip.h"
+#include "clip_internal.h"
 #include "common.h"
 #include "dtops.h"
 #include "ftops.h"
+#include "ftrows.h"
 #include "gemm.h"
 #include "gemm256.h"
 #include "gemm_tn.h"
@@ -45,6 +47,8 @@ struct FtParam {
 inline int cdiv(size_t a, size_t b) { return (int)((a + b - 1) / b); }
 enum { SITE_FT = 24 };
 }  // namespace
+struct arp_ft;
+static int res_order(arp_ft* c, bool host_wait);  // the parameters are about to move: behind the reward calls still in flight on the towers' stream
 
 struct arp_ft {
     arp_ft_cfg cfg;
@@ -79,6 +83,36 @@ struct arp_ft {
     DevBuf X[2], XT[2], f[2], fT_[2], fTt[2], H[2], HT[2], A[2], a[2], nrm[2], da[2], dA[2], dAT_[2], dAt[2], dfd[2], dH[2], dHp[2], dHpt[2], df[2], dUt[2],
         dres_part[2];
     DevBuf scores, ds, C, CT_, Ct, Hinv, logits, dlogits, dHinv, dHinvT_, dHinvt, dC, metrics, scal, part;
+    // ---- the resident reward path (arp_ft_reward_*): frames in HBM -> fine-tuned rewards in HBM on the TOWERS' stream.  Inference only, with a workspace
+    // of its own (a batch staged with arp_ft_set_batch survives a reward call) and the adapted prompts cached on the device.
+    uint64_t version = 1;  // of the parameters: every host write, every AdamW update and every broadcast moves it
+    struct Resident {
+        int rows = 0;                  // the workspace below holds this many rows of one call
+        DevBuf X, f, fT, H, A, part;   // X: tower features as T; f = [U | final] f32 and as T; H: hidden as T; A f32; part: split-K slabs
+        DevBuf t_inter, t_final, t, t_mean, nrm;  // prompts: tower features, adapted + normalised t [n_prompts, F] f32, its row mean
+        int n_prompts = 0;
+        uint64_t text_version = 0;     // the parameter version the cached prompts were computed under
+        arp_clip* text_towers = nullptr;  // the towers the cached prompts came through: a reward call through another handle is refused
+        Event ev_done;                 // recorded on the towers' stream behind every reward call: whatever moves the parameters waits for it first
+        bool pending = false;
+        bool use_rows = true;          // calls of <= 16 rows take the weight-streaming GEMM (ftrows.h; 16-bit modes); ARP_FT_ROWS=0 / arp_ft_reward_set_rows
+        int64_t n_replayed = 0, n_captured = 0, n_launched = 0, n_rows = 0;  // arp_ft_reward_stats: graph replays, captures, launch-by-launch passes, rows-kernel products
+        int reduce = 0;                // 0: prompt 0; 1: mean over the prompts
+        DevBuf frames, rewards;        // host-fed calls (arp_ft_reward): one chunk of frames and its rewards
+        PinBuf pin_frames, pin_rewards;
+        // latency-size calls: towers + head + reward kernel as one captured chain per (buffers, n, geometry, transform, reduction)
+        struct Graph {
+            arp_clip* towers;
+            const uint8_t* frames;
+            float* rewards;
+            int n, H, W, key;          // key: bit 0 use_crop, bit 1 transform, bit 2 reduction
+            uint64_t gen;              // the towers' buffer generation (clip_ms_prepare) the pointers inside belong to
+            hipGraph_t graph;
+            hipGraphExec_t exec;
+        };
+        std::vector<Graph> graphs;
+        bool use_graph = true;         // ARP_FT_REWARD_GRAPH=0, or a capture that did not take: launch by launch
+    } res;
     Profiler prof;
     // data parallelism (BASELINE configs[4]: DP = 8): one process per GPU, one all-reduce(sum) of the flat gradient per step
     ncclComm_t comm = nullptr;
@@ -109,6 +143,13 @@ struct arp_ft {
     size_t psize(const std::string& n) { return infos[index.at(n)].size; }
 };
 static_assert(!std::is_copy_constructible_v<arp_ft>);
+static int res_order(arp_ft* c, bool host_wait) {
+    if (!c->res.pending) return 0;
+    if (host_wait) ARP_HIP_OK(hipEventSynchronize(c->res.ev_done));
+    else ARP_HIP_OK(hipStreamWaitEvent(c->stream, c->res.ev_done, 0));
+    c->res.pending = false;
+    return 0;
+}
 
 namespace {
 
@@ -181,19 +222,25 @@ static FtSkip ft_skip_ranges(arp_ft* c) {
     return skip;
 }
 
-// out[M, N] (ldo) = act(A[M, K] . W[N, K]^T + bias) (+ resid, same view as out).  Split over K whenever the 128x128
-// grid alone would leave most of the chip idle (the row counts of this step are <= 192).
-template <typename T, typename OutT>
-int ft_gemm(arp_ft* c, const char* site, const void* A, int lda, const void* W, int ldw, const float* bias, int act, const float* resid, OutT* out,
-            int ldo, int M, int N, int K) {
+// the number of K slices ft_gemm cuts a product into
+template <typename T> int ft_gemm_split(int M, int N, int K) {
     constexpr int EPB = 128 / (int)sizeof(T);
     const int nk = K / EPB;
     const int tiles = cdiv(M, 128) * cdiv(N, 128);
     constexpr int wg_target = 512;  // one resident round (2 WG/CU x 256 CUs); measured best of 256..2048
     int S = std::max(1, std::min(nk, wg_target / std::max(tiles, 1)));
     const int per = (nk + S - 1) / S;
-    S = (nk + per - 1) / per;
-    ProfScope ps(c->prof, c->stream, site);
+    return (nk + per - 1) / per;
+}
+// out[M, N] (ldo) = act(A[M, K] . W[N, K]^T + bias) (+ resid, same view as out).  Split over K whenever the 128x128
+// grid alone would leave most of the chip idle (the row counts of this step are <= 192).
+// (st, part: the stream to enqueue on and the owner of the split-K slabs -- the step's own, or the resident reward path's on the towers' stream)
+template <typename T, typename OutT>
+int ft_gemm_on(arp_ft* c, hipStream_t st, DevBuf& part, const char* site, const void* A, int lda, const void* W, int ldw, const float* bias, int act,
+               const float* resid, OutT* out, int ldo, int M, int N, int K) {
+    const int tiles = cdiv(M, 128) * cdiv(N, 128);
+    const int S = ft_gemm_split<T>(M, N, K);
+    ProfScope ps(c->prof, st, site);
     GemmArgs g;
     g.A = A; g.W = W; g.M = M; g.N = N; g.K = K; g.lda = lda; g.ldw = ldw;
     if (S == 1 && act == ACT_NONE && !resid && tiles >= 256) {  // big output, short contraction: the weight-gradient GEMMs
@@ -215,20 +262,26 @@ int ft_gemm(arp_ft* c, const char* site, const void* A, int lda, const void* W, 
                 g.adam_eps = c->cfg.eps; g.adam_bc1 = c->fuse_bc1; g.adam_bc2 = c->fuse_bc2;
                 g.adam_mask = c->cfg.mode == ARP_MODE_F16; g.adam_dropped = c->dropped.as<unsigned int>();
                 c->fused.emplace_back(off, off + (size_t)M * N);
-                return launch_gemm_nt<T, float, ACT_NONE, false, GEMM_SITE_ADAMW>(g, c->stream);
+                return launch_gemm_nt<T, float, ACT_NONE, false, GEMM_SITE_ADAMW>(g, st);
             }
         }
-        return launch_gemm_auto<T, OutT, ACT_NONE, false, SITE_FT>(g, c->stream, 0);
+        return launch_gemm_auto<T, OutT, ACT_NONE, false, SITE_FT>(g, st, 0);
     }
-    ARP_TRY(c->part.ensure((size_t)S * M * N * 4));
-    g.bias = nullptr; g.resid = nullptr; g.out = c->part.p; g.ldr = N; g.ldo = N;
+    ARP_TRY(part.ensure((size_t)S * M * N * 4));
+    g.bias = nullptr; g.resid = nullptr; g.out = part.p; g.ldr = N; g.ldo = N;
     g.ksplit = S; g.slice_stride = (size_t)M * N;
     g.m_fast = M <= 4 * GEMM_BM ? 1 : 0;  // the image tower's 192 rows = two row tiles over the same weight stream
-    ARP_TRY((launch_gemm_nt<T, float, ACT_NONE, false, SITE_FT + 1>(g, c->stream)));
+    ARP_TRY((launch_gemm_nt<T, float, ACT_NONE, false, SITE_FT + 1>(g, st)));
     const size_t MN = (size_t)M * N;
-    launch_splitk_reduce<OutT>(c->stream, c->part.as<float>(), S, MN, N, bias, act, out, resid, ldo == N ? 0 : ldo);
+    launch_splitk_reduce<OutT>(st, part.as<float>(), S, MN, N, bias, act, out, resid, ldo == N ? 0 : ldo);
     ARP_HIP_OK(hipGetLastError());
     return 0;
+}
+
+template <typename T, typename OutT>
+int ft_gemm(arp_ft* c, const char* site, const void* A, int lda, const void* W, int ldw, const float* bias, int act, const float* resid, OutT* out,
+            int ldo, int M, int N, int K) {
+    return ft_gemm_on<T, OutT>(c, c->stream, c->part, site, A, lda, W, ldw, bias, act, resid, out, ldo, M, N, K);
 }
 
 // dX[M, N] (ldo) = dY[M, K] . W[K, N] (+ resid) with W = the operand-type mirror of a weight [out = K, in = N] as it lies in memory: the NN kernel,
@@ -554,10 +607,13 @@ int apply_update(arp_ft* c, float lr) {
     ARP_HIP_OK(hipGetLastError());
     c->step += 1;
     c->transposed_stale = true;
+    c->version += 1;
     return 0;
 }
 
 template <typename T> int step_impl(arp_ft* c, float lr, float* aux) {
+    c->version += 1;  // (here, not only behind AdamW: a step that fails part way may already have moved weights from inside its GEMMs)
+    ARP_TRY(res_order(c, false));
     ARP_TRY(forward<T>(c));
     const bool comm = c->has_comm && (c->world > 1 || c->force_comm);
     if (comm && c->overlap_comm) {
@@ -605,7 +661,207 @@ template <typename T> int step_impl(arp_ft* c, float lr, float* aux) {
     return 0;
 }
 
+// ---- the resident reward path ------------------------------------------------------------------------------------------------
+// uint8 frames in HBM -> towers (clip_ms_enqueue: the multi-scale export stays in the towers' buffers) -> ft_infer_image -> ft_reward_kernel -> f32 rewards
+// in HBM, all on the towers' stream and without a host synchronisation.  ft_infer_image rounds where encode_tower does -- tower features, f = [U | final]
+// and the hidden layer after its ReLU become T; A, the mix, the norm and the product with the prompt stay f32 -- but keeps nothing for a backward: no
+// transposed copies, and nothing of the step's workspace is touched.
+void res_drop_graphs(arp_ft* c) {
+    for (auto& g : c->res.graphs) {
+        (void)hipGraphExecDestroy(g.exec);
+        (void)hipGraphDestroy(g.graph);
+    }
+    c->res.graphs.clear();
+}
+
+template <typename T> int res_ensure(arp_ft* c, hipStream_t st, int rows) {
+    if (rows <= c->res.rows) return 0;
+    ARP_HIP_OK(hipStreamSynchronize(st));  // (a call still in flight reads the buffers about to move; so do the captured chains)
+    res_drop_graphs(c);
+    const size_t e = sizeof(T), R = rows, Din = std::max(c->Dv(), c->Dt()), F = c->F(), Hd = c->Hd();
+    if (e == 2) { ARP_TRY(c->res.X.ensure(R * Din * e)); ARP_TRY(c->res.fT.ensure(R * F * e)); }
+    ARP_TRY(c->res.f.ensure(R * F * 4)); ARP_TRY(c->res.H.ensure(R * Hd * e)); ARP_TRY(c->res.A.ensure(R * F * 4));
+    size_t slab = 0;  // the largest split-K slab set of any call of 1 .. rows rows (the slice count falls as the row tiles grow)
+    for (int M = 1; M <= rows; ++M)
+        for (int D : {c->Dv(), c->Dt()})
+            slab = std::max({slab, (size_t)ft_gemm_split<T>(M, c->Dt(), D) * M * c->Dt(), (size_t)ft_gemm_split<T>(M, (int)Hd, (int)F) * M * Hd,
+                             (size_t)ft_gemm_split<T>(M, (int)F, (int)Hd) * M * F});
+    if (e == 2)
+        for (int M = 1; M <= std::min(rows, (int)ROWS_MAX_M); ++M)
+            for (int D : {c->Dv(), c->Dt()})
+                slab = std::max({slab, (size_t)rows_gemm_split(c->Dt(), D) * M * c->Dt(), (size_t)rows_gemm_split((int)Hd, (int)F) * M * Hd,
+                                 (size_t)rows_gemm_split((int)F, (int)Hd) * M * F});
+    ARP_TRY(c->res.part.ensure(slab * 4));
+    c->res.rows = rows;
+    return 0;
+}
+
+// A product of the resident path: the weight-streaming rows kernel where its domain holds (16-bit modes, M <= 16, ftrows.h), ft_gemm's route otherwise.
+template <typename T, typename OutT>
+int res_gemm(arp_ft* c, hipStream_t st, const char* site, const void* A, int lda, const void* W, int ldw, const float* bias, int act, OutT* out, int ldo,
+             int M, int N, int K) {
+    arp_ft::Resident& r = c->res;
+    if constexpr (sizeof(T) == 2) {
+        if (r.use_rows && rows_gemm_supported(M, N, K, lda, ldw, A, W)) {
+            int S = rows_gemm_split(N, K);
+            if ((size_t)S * M * N * 4 <= r.part.bytes) {
+                ProfScope ps(c->prof, st, site);
+                ARP_TRY(launch_rows_gemm<T>(st, A, lda, W, ldw, r.part.as<float>(), M, N, K, &S));
+                launch_splitk_reduce<OutT>(st, r.part.as<float>(), S, (size_t)M * N, N, bias, act, out, (const float*)nullptr, ldo == N ? 0 : ldo);
+                ARP_HIP_OK(hipGetLastError());
+                r.n_rows += 1;
+                return 0;
+            }
+        }
+    }
+    return ft_gemm_on<T, OutT>(c, st, r.part, site, A, lda, W, ldw, bias, act, nullptr, out, ldo, M, N, K);
+}
+
+// One tower's head on M <= res.rows rows of tower features in device memory (w = 0: image, 1: text): leaves f (f32) and A (f32) in the resident workspace.
+template <typename T> int ft_infer_image(arp_ft* c, hipStream_t st, int w, int M, const float* inter, const float* final_feat) {
+    arp_ft::Resident& r = c->res;
+    const int F = c->F(), Hd = c->Hd(), E = c->cfg.embed, Dt = c->Dt(), Din = w == 0 ? c->Dv() : Dt;
+    if (M <= 0 || M > r.rows) return fail("ft_infer_image: the resident workspace holds fewer rows");
+    const std::string a = std::string(TW[w]) + "_adapter";
+    const void* Xop = inter;
+    if constexpr (sizeof(T) == 2) {  // tower features -> T
+        ProfScope ps(c->prof, st, "ft.res_rowops");
+        hipLaunchKernelGGL((convert_kernel<T>), dim3(cdiv((size_t)M * Din, 1024)), dim3(256), 0, st, inter, r.X.as<T>(), (size_t)M * Din);
+        ARP_HIP_OK(hipGetLastError());
+        Xop = r.X.p;
+    }
+    // U = X Wint^T into the first Dt columns of the f32 row; the pack kernel puts the CLIP feature behind it and writes the row as T
+    ARP_TRY((res_gemm<T, float>(c, st, "ft.res_inter", Xop, Din, fwd_w<T>(c, std::string(TW[w]) + "_intermediate_linear.weight"), Din, nullptr,
+                                  ACT_NONE, r.f.as<float>(), F, M, Dt, Din)));
+    {
+        ProfScope ps(c->prof, st, "ft.res_rowops");
+        hipLaunchKernelGGL((ft_pack_f_kernel<T>), dim3(M), dim3(256), 0, st, final_feat, E, r.f.as<float>(), sizeof(T) == 2 ? r.fT.as<T>() : (T*)nullptr, F);
+        ARP_HIP_OK(hipGetLastError());
+    }
+    const void* fop = sizeof(T) == 2 ? r.fT.p : r.f.p;
+    ARP_TRY((res_gemm<T, T>(c, st, "ft.res_fc1", fop, F, fwd_w<T>(c, a + ".layers.0.weight"), F, c->p(a + ".layers.0.bias"), ACT_RELU,
+                              r.H.as<T>(), Hd, M, Hd, F)));
+    ARP_TRY((res_gemm<T, float>(c, st, "ft.res_fc2", r.H.p, Hd, fwd_w<T>(c, a + ".layers.3.weight"), Hd, c->p(a + ".layers.3.bias"), ACT_NONE,
+                                r.A.as<float>(), F, M, F, Hd)));
+    return 0;
+}
+int ft_infer_dispatch(arp_ft* c, hipStream_t st, int w, int M, const float* inter, const float* final_feat) {
+    if (c->cfg.mode == ARP_MODE_BF16) return ft_infer_image<bf16_t>(c, st, w, M, inter, final_feat);
+    if (c->cfg.mode == ARP_MODE_F16) return ft_infer_image<f16_t>(c, st, w, M, inter, final_feat);
+    return ft_infer_image<float>(c, st, w, M, inter, final_feat);
+}
+int res_ensure_dispatch(arp_ft* c, hipStream_t st, int rows) {
+    if (c->cfg.mode == ARP_MODE_F32) return res_ensure<float>(c, st, rows);
+    return c->cfg.mode == ARP_MODE_BF16 ? res_ensure<bf16_t>(c, st, rows) : res_ensure<f16_t>(c, st, rows);
+}
+
+// what every entry of the path refuses before it touches the device
+int res_check(arp_ft* c, arp_clip* towers, ClipMsInfo* ci) {
+    if (!c || !towers) return fail("null handle");
+    if (c->cfg.goal_conditioned) return fail("the resident reward path has no goal frames: a goal_conditioned head is refused (pass rewards= computed by the caller)");
+    ARP_TRY(clip_ms_info(towers, ci));
+    if (ci->device != c->cfg.device)
+        return fail("the towers live on device " + std::to_string(ci->device) + ", the head on device " + std::to_string(c->cfg.device));
+    const arp_ft_cfg& k = c->cfg;
+    if (ci->width != k.width_v || ci->txt_width != k.width_t || ci->layers != k.layers || ci->txt_layers != k.layers || ci->embed != k.embed)
+        return fail("the towers (width " + std::to_string(ci->width) + " / " + std::to_string(ci->txt_width) + ", layers " + std::to_string(ci->layers) + " / " +
+                    std::to_string(ci->txt_layers) + ", embed " + std::to_string(ci->embed) + ") do not match the head's configuration (width_v " +
+                    std::to_string(k.width_v) + ", width_t " + std::to_string(k.width_t) + ", layers " + std::to_string(k.layers) + ", embed " +
+                    std::to_string(k.embed) + ")");
+    return 0;
+}
+int res_check_text(arp_ft* c, arp_clip* towers) {
+    if (c->res.n_prompts <= 0) return fail("no prompts cached: call arp_ft_reward_set_text first");
+    if (c->res.text_towers != towers) return fail("the prompts were cached through another towers handle: call arp_ft_reward_set_text with this one");
+    if (c->res.text_version != c->version)
+        return fail("the head's parameters moved since the prompts were cached (a host write, a train step or a broadcast): call arp_ft_reward_set_text again");
+    return 0;
+}
+
+int res_pass(arp_ft* c, arp_clip* towers, hipStream_t st, const uint8_t* fr, int nb, int H, int W, int use_crop, int transform, float* rw) {
+    const float *inter = nullptr, *fin = nullptr;
+    ARP_TRY(clip_ms_enqueue(towers, fr, nb, H, W, use_crop, transform, &inter, &fin));
+    ARP_TRY(ft_infer_dispatch(c, st, 0, nb, inter, fin));
+    ProfScope ps(c->prof, st, "ft.res_reward");
+    hipLaunchKernelGGL(ft_reward_kernel, dim3(nb), dim3(256), 0, st, c->res.f.as<float>(), c->res.A.as<float>(), c->p("image_residual_weight"),
+                       c->res.reduce ? c->res.t_mean.as<float>() : c->res.t.as<float>(), expf(c->cfg.logit_scale), rw, c->F());
+    ARP_HIP_OK(hipGetLastError());
+    return 0;
+}
+
+int res_reward_dev_impl(arp_ft* c, arp_clip* towers, const uint8_t* frames_dev, int n, int H, int W, int use_crop, int transform, float* rewards_dev, hipStream_t* used) {
+    ClipMsInfo ci;
+    ARP_TRY(res_check(c, towers, &ci));
+    if (!frames_dev || !rewards_dev) return fail("null buffer");
+    if (n <= 0) return fail("empty call: n must be positive");
+    ARP_TRY(res_check_text(c, towers));
+    ARP_HIP_OK(hipSetDevice(c->cfg.device));
+    const int mb = ci.max_batch, nb0 = std::min(n, mb);
+    hipStream_t st = ci.stream;
+    *used = st;
+    uint64_t gen = 0;
+    int capturable = 0;
+    if (n > mb && n % mb) ARP_TRY(clip_ms_prepare(towers, n % mb, H, W, use_crop, transform, &gen, &capturable));  // (a ragged last chunk may want a resize plan of its own)
+    ARP_TRY(clip_ms_prepare(towers, nb0, H, W, use_crop, transform, &gen, &capturable));
+    ARP_TRY(res_ensure_dispatch(c, st, nb0));
+    // a latency-size call: towers, head and reward kernel are one linear chain on one stream -- captured once, replayed afterwards
+    if (capturable && n <= mb && c->res.use_graph && !c->prof.on) {
+        const int key = (use_crop ? 1 : 0) | (transform << 1) | (c->res.reduce << 2) | (c->res.use_rows ? 8 : 0);
+        for (auto& g : c->res.graphs)
+            if (g.towers == towers && g.frames == frames_dev && g.rewards == rewards_dev && g.n == n && g.H == H && g.W == W && g.key == key && g.gen == gen) {
+                ARP_HIP_OK(hipGraphLaunch(g.exec, st));
+                c->res.n_replayed += 1;
+                return 0;
+            }
+        arp_ft::Resident::Graph g{towers, frames_dev, rewards_dev, n, H, W, key, gen, nullptr, nullptr};
+        ARP_HIP_OK(hipStreamBeginCapture(st, hipStreamCaptureModeRelaxed));
+        const int rc = res_pass(c, towers, st, frames_dev, n, H, W, use_crop, transform, rewards_dev);
+        const hipError_t ec = hipStreamEndCapture(st, &g.graph);
+        if (rc != 0 || ec != hipSuccess || !g.graph || hipGraphInstantiate(&g.exec, g.graph, nullptr, nullptr, 0) != hipSuccess) {
+            // a capture that did not take: this handle goes on launch by launch (same kernels, same results)
+            if (g.graph) (void)hipGraphDestroy(g.graph);
+            for (int k = 0; k < 4 && hipGetLastError() != hipSuccess; ++k) {}
+            c->res.use_graph = false;
+            c->res.n_launched += 1;
+            return res_pass(c, towers, st, frames_dev, n, H, W, use_crop, transform, rewards_dev);
+        }
+        if (c->res.graphs.size() >= 8) {  // a caller that keeps changing buffers: forget the oldest (behind whatever still replays it)
+            ARP_HIP_OK(hipStreamSynchronize(st));
+            (void)hipGraphExecDestroy(c->res.graphs.front().exec);
+            (void)hipGraphDestroy(c->res.graphs.front().graph);
+            c->res.graphs.erase(c->res.graphs.begin());
+        }
+        c->res.graphs.push_back(g);
+        ARP_HIP_OK(hipGraphLaunch(g.exec, st));
+        c->res.n_captured += 1;
+        return 0;
+    }
+    const size_t fb = (size_t)H * W * 3;
+    c->res.n_launched += 1;
+    for (int off = 0; off < n; off += mb)  // chunks of max_batch in stream order: the head runs once per chunk on the same workspace
+        ARP_TRY(res_pass(c, towers, st, frames_dev + (size_t)off * fb, std::min(mb, n - off), H, W, use_crop, transform, rewards_dev + off));
+    return 0;
+}
+
+int res_reward_dev(arp_ft* c, arp_clip* towers, const uint8_t* frames_dev, int n, int H, int W, int use_crop, int transform, float* rewards_dev) {
+    hipStream_t st = nullptr;
+    const int rc = res_reward_dev_impl(c, towers, frames_dev, n, H, W, use_crop, transform, rewards_dev, &st);
+    if (st) {  // something may be in flight on the towers' stream that reads the parameters
+        if (!c->res.ev_done) ARP_TRY(c->res.ev_done.create());
+        ARP_HIP_OK(hipEventRecord(c->res.ev_done, st));
+        c->res.pending = true;
+    }
+    return rc;
+}
+
 }  // namespace
+
+namespace arp {
+int ft_reward_check(arp_ft* head, arp_clip* towers) {
+    ClipMsInfo ci;
+    return res_check(head, towers, &ci);
+}
+}  // namespace arp
 
 // =================================== C ABI ===============================================================
 extern "C" {
@@ -637,6 +893,8 @@ int arp_ft_create(const arp_ft_cfg* cfg, arp_ft** out) {
         if (const char* e = getenv("ARP_FT_FORCE_COMM")) c->force_comm = atoi(e) != 0;
         if (const char* e = getenv("ARP_FT_FUSE_ADAM")) c->fuse_adam = atoi(e) != 0;
         if (const char* e = getenv("ARP_FT_NN")) c->nn_dx = atoi(e) != 0;
+        if (const char* e = getenv("ARP_FT_REWARD_GRAPH")) c->res.use_graph = atoi(e) != 0;
+        if (const char* e = getenv("ARP_FT_ROWS")) c->res.use_rows = atoi(e) != 0;
         {   // the NN dX kernel wants output widths in multiples of 128 and contraction lengths in multiples of 64 (16-bit modes only)
             const int Fq = c->F(), Hq = c->Hd();
             c->nn_dx = c->nn_dx && k.mode != ARP_MODE_F32 && Fq % 128 == 0 && Hq % 128 == 0 && k.hidden % 64 == 0;
@@ -665,6 +923,8 @@ int arp_ft_destroy(arp_ft* c) {
     if (!c) return 0;
     (void)hipSetDevice(c->cfg.device);
     if (c->stream) (void)hipStreamSynchronize(c->stream);
+    if (c->res.rows > 0) (void)hipDeviceSynchronize();  // the resident reward path runs on the towers' stream, which this handle does not own
+    res_drop_graphs(c);
     if (c->has_comm && rccl_api()) (void)rccl_api()->CommDestroy(c->comm);
     if (c->comm_stream) (void)hipStreamSynchronize(c->comm_stream);
     delete c;
@@ -702,8 +962,12 @@ static int ft_tensor_io(arp_ft* c, const char* name, int which, float* host, int
     ARP_HIP_OK(hipSetDevice(c->cfg.device));
     ARP_HIP_OK(hipStreamSynchronize(c->stream));
     if (write) {
+        if (which == 0) ARP_TRY(res_order(c, true));
         ARP_HIP_OK(hipMemcpy(dev, host, pi.size * 4, hipMemcpyHostToDevice));
-        if (which == 0) c->shadows_stale = true;
+        if (which == 0) {
+            c->shadows_stale = true;
+            c->version += 1;
+        }
     } else {
         if (which == 1)
             for (const auto& r : c->grads_gone)
@@ -817,6 +1081,180 @@ int arp_ft_encode(arp_ft* c, int which, const float* inter, const float* final_f
     return 0;
 }
 
+// ---- the resident reward path: C ABI ---------------------------------------------------------------------------------------------
+// The text side, once per prompt set: towers' multi-scale text export into the head's buffers, the text head's inference pass, mix + norm -> t [n, F]
+// and its row mean.  Synchronises both handles' streams (it also brings the operand mirror up to date, which the reward calls then read without a check
+// of their own: a reward call made under another parameter version is refused).
+int arp_ft_reward_set_text(arp_ft* c, arp_clip* towers, const int32_t* tokens, int n_prompts) {
+    ClipMsInfo ci;
+    ARP_TRY(res_check(c, towers, &ci));
+    if (!tokens || n_prompts <= 0) return fail("set_text: need at least one prompt");
+    ARP_HIP_OK(hipSetDevice(c->cfg.device));
+    arp_ft::Resident& r = c->res;
+    ARP_HIP_OK(hipStreamSynchronize(ci.stream));
+    res_drop_graphs(c);  // the captured chains read the old prompt vectors
+    r.n_prompts = 0;
+    if (c->cfg.mode == ARP_MODE_BF16) ARP_TRY(refresh_shadows<bf16_t>(c));
+    else if (c->cfg.mode == ARP_MODE_F16) ARP_TRY(refresh_shadows<f16_t>(c));
+    else ARP_TRY(refresh_shadows<float>(c));
+    ARP_HIP_OK(hipStreamSynchronize(c->stream));  // parameters and mirror are at rest from here until the version moves
+    const size_t np = n_prompts, F = c->F();
+    ARP_TRY(r.t_inter.ensure(np * c->Dt() * 4)); ARP_TRY(r.t_final.ensure(np * c->cfg.embed * 4));
+    ARP_TRY(r.t.ensure(np * F * 4)); ARP_TRY(r.t_mean.ensure(F * 4)); ARP_TRY(r.nrm.ensure(np * 4));
+    ARP_TRY(arp_clip_encode_text_multiscale_dev(towers, tokens, n_prompts, r.t_inter.as<float>(), r.t_final.as<float>()));
+    ARP_TRY(res_ensure_dispatch(c, ci.stream, n_prompts));
+    ARP_TRY(ft_infer_dispatch(c, ci.stream, 1, n_prompts, r.t_inter.as<float>(), r.t_final.as<float>()));
+    hipLaunchKernelGGL(ft_mix_norm_fwd_kernel, dim3(n_prompts), dim3(256), 0, ci.stream, r.f.as<float>(), r.A.as<float>(), c->p("text_residual_weight"),
+                       r.t.as<float>(), r.nrm.as<float>(), (int)F);
+    hipLaunchKernelGGL(ft_rows_mean_kernel, dim3(cdiv(F, 256)), dim3(256), 0, ci.stream, r.t.as<float>(), r.t_mean.as<float>(), n_prompts, (int)F);
+    ARP_HIP_OK(hipGetLastError());
+    ARP_HIP_OK(hipStreamSynchronize(ci.stream));
+    r.n_prompts = n_prompts;
+    r.text_towers = towers;
+    r.text_version = c->version;
+    return 0;
+}
+
+int arp_ft_reward_set_reduce(arp_ft* c, int mean) {
+    if (!c) return fail("null handle");
+    if (mean != 0 && mean != 1) return fail("set_reduce: 0 (prompt 0) or 1 (mean over the prompts)");
+    c->res.reduce = mean;  // (the captured chains are keyed by it)
+    return 0;
+}
+
+int arp_ft_reward_set_rows(arp_ft* c, int on) {
+    if (!c) return fail("null handle");
+    c->res.use_rows = on != 0;  // (the captured chains are keyed by it)
+    return 0;
+}
+
+int arp_ft_reward_stats(arp_ft* c, int64_t out4[4]) {
+    if (!c || !out4) return fail("null argument");
+    out4[0] = c->res.n_replayed; out4[1] = c->res.n_captured; out4[2] = c->res.n_launched; out4[3] = c->res.n_rows;
+    return 0;
+}
+
+extern "C++" {
+namespace {
+template <typename T> __global__ __launch_bounds__(256) void ft_widen_kernel(const T* __restrict__ in, float* __restrict__ out, size_t n) {
+    const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (i < n) out[i] = Elem<T>::ld(in + i);
+}
+template <typename T> int op_rows_dev(const float* host, size_t n, DevBuf& stage, DevBuf& dst) {  // host f32 -> device T
+    ARP_TRY(stage.ensure(n * 4)); ARP_TRY(dst.ensure(n * sizeof(T)));
+    ARP_HIP_OK(hipMemcpy(stage.p, host, n * 4, hipMemcpyHostToDevice));
+    hipLaunchKernelGGL((convert_kernel<T>), dim3(cdiv(n, 1024)), dim3(256), 0, nullptr, stage.as<float>(), dst.as<T>(), n);
+    ARP_HIP_OK(hipGetLastError());
+    return 0;
+}
+template <typename T> int op_rows_gemm(int act, const float* A, int lda, const float* W, int ldw, const float* bias, float* out, int ldo, int out_rows,
+                                       int out_f32, int M, int N, int K, int ksplit) {
+    // refusals first: nothing is allocated, nothing is written (operand alignment is the launcher's to refuse; hipMalloc'd operands are aligned)
+    if (!rows_gemm_supported(M, N, K, lda, ldw, nullptr, nullptr))
+        return fail("rows_gemm: needs 1 <= M <= 16, K % 64 == 0, N % 16 == 0, 16-byte aligned operands and leading dimensions");
+    if (ldo < N || out_rows < M || ksplit < 0) return fail("rows_gemm: bad output geometry");
+    DevBuf st, dA, dW, db, dpart, dout, dout32;
+    ARP_TRY(op_rows_dev<T>(A, (size_t)M * lda, st, dA));
+    ARP_TRY(op_rows_dev<T>(W, (size_t)N * ldw, st, dW));
+    if (bias) { ARP_TRY(db.ensure((size_t)N * 4)); ARP_HIP_OK(hipMemcpy(db.p, bias, (size_t)N * 4, hipMemcpyHostToDevice)); }
+    int S = ksplit > 0 ? ksplit : rows_gemm_split(N, K);
+    ARP_TRY(dpart.ensure((size_t)std::min(S, K / 64) * M * N * 4));
+    const size_t no = (size_t)out_rows * ldo;
+    ARP_TRY(dout32.ensure(no * 4));
+    ARP_HIP_OK(hipMemcpy(dout32.p, out, no * 4, hipMemcpyHostToDevice));  // the caller's prefill: guard rows and columns
+    ARP_TRY(launch_rows_gemm<T>(nullptr, dA.p, lda, dW.p, ldw, dpart.as<float>(), M, N, K, &S));
+    const float* bd = bias ? db.as<float>() : nullptr;
+    if (out_f32) {
+        launch_splitk_reduce<float>(nullptr, dpart.as<float>(), S, (size_t)M * N, N, bd, act, dout32.as<float>(), (const float*)nullptr, ldo == N ? 0 : ldo);
+    } else {
+        ARP_TRY(dout.ensure(no * sizeof(T)));
+        hipLaunchKernelGGL((convert_kernel<T>), dim3(cdiv(no, 1024)), dim3(256), 0, nullptr, dout32.as<float>(), dout.as<T>(), no);
+        launch_splitk_reduce<T>(nullptr, dpart.as<float>(), S, (size_t)M * N, N, bd, act, dout.as<T>(), (const float*)nullptr, ldo == N ? 0 : ldo);
+        hipLaunchKernelGGL((ft_widen_kernel<T>), dim3(cdiv(no, 256)), dim3(256), 0, nullptr, dout.as<T>(), dout32.as<float>(), no);
+    }
+    ARP_HIP_OK(hipGetLastError());
+    ARP_HIP_OK(hipDeviceSynchronize());
+    ARP_HIP_OK(hipMemcpy(out, dout32.p, no * 4, hipMemcpyDeviceToHost));
+    return S;
+}
+}  // namespace
+}  // extern "C++"
+
+// The rows kernel alone (ftrows.h) + the split-K reduce behind it: out[m, n] (ldo; out_rows >= M rows, prefilled by the caller: only [0, M) x [0, N) is written)
+// = act(A[M, K] (lda) . W[N, K]^T (ldw) + bias) in the operand type of `mode` (bf16 / f16) or f32.  ksplit = 0: the dispatcher's slice count.  Host f32 arrays
+// in and out (16-bit outputs widened).  Returns the slice count used, or -1 with a message for a geometry outside the kernel's domain -- nothing is written then.
+int arp_op_ft_rows_gemm(int mode, int act, const float* A, int lda, const float* W, int ldw, const float* bias, float* out, int ldo, int out_rows, int out_f32,
+                        int M, int N, int K, int ksplit) {
+    if (!A || !W || !out) return fail("null argument");
+    if (act != ACT_NONE && act != ACT_RELU) return fail("rows_gemm: act is none or relu");
+    if (mode == ARP_MODE_BF16) return op_rows_gemm<bf16_t>(act, A, lda, W, ldw, bias, out, ldo, out_rows, out_f32, M, N, K, ksplit);
+    if (mode == ARP_MODE_F16) return op_rows_gemm<f16_t>(act, A, lda, W, ldw, bias, out, ldo, out_rows, out_f32, M, N, K, ksplit);
+    return fail("rows_gemm: 16-bit modes only");
+}
+
+int arp_ft_reward_dev_async(arp_ft* c, arp_clip* towers, const uint8_t* frames_dev, int n, int H, int W, int use_crop, int transform, float* rewards_dev) {
+    return res_reward_dev(c, towers, frames_dev, n, H, W, use_crop ? 1 : 0, transform, rewards_dev);
+}
+
+int arp_ft_reward(arp_ft* c, arp_clip* towers, const uint8_t* frames, int n, int H, int W, int use_crop, int transform, float* rewards) {
+    ClipMsInfo ci;
+    ARP_TRY(res_check(c, towers, &ci));
+    if (!frames || !rewards) return fail("null buffer");
+    if (n <= 0) return fail("empty call: n must be positive");
+    if (H <= 0 || W <= 0) return fail("bad frame geometry");
+    if (transform != CLIP_TF_FINETUNE && transform != CLIP_TF_LABEL) return fail("transform is 0 (fine-tune: bilinear) or 1 (label: Pillow bicubic)");
+    ARP_TRY(res_check_text(c, towers));
+    ARP_HIP_OK(hipSetDevice(c->cfg.device));
+    arp_ft::Resident& r = c->res;
+    const size_t fb = (size_t)H * W * 3;
+    const int mb = ci.max_batch, nb0 = std::min(n, mb);
+    // frames go up through pinned staging while a chunk is small (the rollout loop's calls: a true DMA behind one CPU copy); a labelling chunk (201 MB at
+    // 1 024 frames of 256 x 256) goes up from the caller's memory as the host path's does -- a CPU copy of it into a staging buffer first measured 8 % off
+    // the labelling rate (18.3 k against 20.0 k frames/s)
+    const bool stage = nb0 * fb <= ((size_t)8 << 20);
+    if (r.frames.bytes < nb0 * fb || r.rewards.bytes < (size_t)nb0 * 4 || (stage && r.pin_frames.bytes < nb0 * fb)) {
+        ARP_HIP_OK(hipStreamSynchronize(ci.stream));
+        ARP_TRY(r.frames.ensure(nb0 * fb)); ARP_TRY(r.rewards.ensure((size_t)std::max(nb0, 16) * 4));
+        if (stage) ARP_TRY(r.pin_frames.ensure(nb0 * fb));
+        ARP_TRY(r.pin_rewards.ensure((size_t)std::max(nb0, 16) * 4));
+    }
+    for (int off = 0; off < n; off += mb) {  // one synchronisation per chunk
+        const int nb = std::min(mb, n - off);
+        const uint8_t* src = frames + (size_t)off * fb;
+        if (stage) {
+            memcpy(r.pin_frames.p, src, (size_t)nb * fb);
+            src = r.pin_frames.as<uint8_t>();
+        }
+        ARP_HIP_OK(hipMemcpyAsync(r.frames.p, src, (size_t)nb * fb, hipMemcpyHostToDevice, ci.stream));
+        ARP_TRY(res_reward_dev(c, towers, r.frames.as<uint8_t>(), nb, H, W, use_crop ? 1 : 0, transform, r.rewards.as<float>()));
+        ARP_HIP_OK(hipMemcpyAsync(r.pin_rewards.p, r.rewards.p, (size_t)nb * 4, hipMemcpyDeviceToHost, ci.stream));
+        ARP_HIP_OK(hipStreamSynchronize(ci.stream));
+        memcpy(rewards + off, r.pin_rewards.p, (size_t)nb * 4);
+    }
+    return 0;
+}
+
+// ft_reward_kernel alone: f, A [rows, F]; rw = the residual weight before its sigmoid; t [n_prompts, F]; mean = 0: prompt 0, 1: the row mean (taken on the
+// device by the kernel the product uses); reward [rows]
+int arp_op_ft_reward(const float* f, const float* A, float rw, const float* t, int n_prompts, int mean, float scale, float* reward, int rows, int F) {
+    if (!f || !A || !t || !reward || rows <= 0 || F <= 0 || n_prompts <= 0 || (mean != 0 && mean != 1)) return fail("bad argument");
+    DevBuf df, dA, dt, dm, dw, dr;
+    const size_t nf = (size_t)rows * F * 4;
+    ARP_TRY(df.ensure(nf)); ARP_TRY(dA.ensure(nf)); ARP_TRY(dt.ensure((size_t)n_prompts * F * 4)); ARP_TRY(dm.ensure((size_t)F * 4));
+    ARP_TRY(dw.ensure(16)); ARP_TRY(dr.ensure((size_t)rows * 4));
+    ARP_HIP_OK(hipMemcpy(df.p, f, nf, hipMemcpyHostToDevice));
+    ARP_HIP_OK(hipMemcpy(dA.p, A, nf, hipMemcpyHostToDevice));
+    ARP_HIP_OK(hipMemcpy(dt.p, t, (size_t)n_prompts * F * 4, hipMemcpyHostToDevice));
+    ARP_HIP_OK(hipMemcpy(dw.p, &rw, 4, hipMemcpyHostToDevice));
+    if (mean) hipLaunchKernelGGL(ft_rows_mean_kernel, dim3(cdiv((size_t)F, 256)), dim3(256), 0, nullptr, dt.as<float>(), dm.as<float>(), n_prompts, F);
+    hipLaunchKernelGGL(ft_reward_kernel, dim3(rows), dim3(256), 0, nullptr, df.as<float>(), dA.as<float>(), dw.as<float>(), mean ? dm.as<float>() : dt.as<float>(),
+                       scale, dr.as<float>(), F);
+    ARP_HIP_OK(hipGetLastError());
+    ARP_HIP_OK(hipDeviceSynchronize());
+    ARP_HIP_OK(hipMemcpy(reward, dr.p, (size_t)rows * 4, hipMemcpyDeviceToHost));
+    return 0;
+}
+
 int arp_ft_backward(arp_ft* c) {
     if (!c) return fail("null handle");
     if (c->B <= 0) return fail("no batch staged: call arp_ft_set_batch first");
@@ -901,6 +1339,7 @@ int arp_ft_broadcast_state(arp_ft* c) {
     if (!c) return fail("null handle");
     if (!c->has_comm) return 0;
     ARP_HIP_OK(hipSetDevice(c->cfg.device));
+    ARP_TRY(res_order(c, false));
     DevBuf* fb[] = {&c->params, &c->mu, &c->nu};
     for (auto* b : fb)
         if (ncclResult_t r = rccl_api()->Broadcast(b->p, b->p, c->P, ncclFloat, 0, c->comm, c->stream); r != ncclSuccess) return rccl_fail("ncclBroadcast", r);
@@ -913,6 +1352,7 @@ int arp_ft_broadcast_state(arp_ft* c) {
     c->step = st;
     c->shadows_stale = true;
     c->transposed_stale = true;
+    c->version += 1;
     return 0;
 }
 

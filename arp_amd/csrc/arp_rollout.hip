@@ -19,6 +19,7 @@
 #include "common.h"
 #include "dt_internal.h"
 #include "enc_internal.h"
+#include "ft_internal.h"
 #include "runtime.h"
 
 using namespace arp;
@@ -124,6 +125,7 @@ __global__ __launch_bounds__(64) void rollout_reset_kernel(const int32_t* __rest
 struct arp_rollout {
     arp_dt* dt = nullptr;
     arp_clip* clip = nullptr;
+    arp_ft* ft = nullptr;  // the fine-tuned reward: `clip` is then its towers (arp_rollout_create_ft)
     arp_enc* enc = nullptr;
     DtRolloutInfo pi{};
     hipStream_t clip_stream = nullptr;
@@ -163,7 +165,7 @@ int quiesce(arp_rollout* s) {
 
 extern "C" {
 
-static int rollout_create(arp_dt* policy, arp_enc* encoder, arp_clip* reward, int n_envs, int H, int W, float scale, arp_rollout** out) {
+static int rollout_create(arp_dt* policy, arp_enc* encoder, arp_clip* reward, arp_ft* head, int n_envs, int H, int W, float scale, arp_rollout** out) {
     if (!policy || !out) return fail("null argument");
     if (n_envs <= 0) return fail("rollout: n_envs must be positive");
     if (!(scale != 0.f)) return fail("rollout: scale must not be zero");
@@ -182,13 +184,19 @@ static int rollout_create(arp_dt* policy, arp_enc* encoder, arp_clip* reward, in
     if (tokens != s->pi.enc_tokens || width != s->pi.enc_dim) return fail("rollout: encoder geometry does not match the policy's enc_tokens / enc_dim");
     if (dev != s->pi.device) return fail("rollout: the encoder lives on another device");
     if (((size_t)H * W) % 4 || ((size_t)tokens * width) % 4) return fail("rollout: H * W and tokens * width must be multiples of 4");
-    if (reward) {
+    if (reward && head) {  // the fine-tuned reward: the towers need no prompt set of their own, the head caches its prompts
+        ARP_TRY(ft_reward_check(head, reward));
+        ClipMsInfo ci;
+        ARP_TRY(clip_ms_info(reward, &ci));
+        if (ci.device != s->pi.device) return fail("rollout: the reward handles live on another device");
+        s->clip_stream = ci.stream;
+    } else if (reward) {
         int cdev = 0;
         ARP_TRY(clip_stream_of(reward, &s->clip_stream, &cdev));
         if (cdev != s->pi.device) return fail("rollout: the reward handle lives on another device");
     }
     ARP_HIP_OK(hipSetDevice(s->pi.device));
-    s->dt = policy; s->clip = reward; s->enc = s->pi.enc;
+    s->dt = policy; s->clip = reward; s->ft = head; s->enc = s->pi.enc;
     s->E = n_envs; s->H = H; s->W = W; s->scale = scale;
     s->F = (size_t)tokens * width;
     const size_t E = n_envs, T = s->pi.window, fb = (size_t)H * W * 3;
@@ -206,11 +214,15 @@ static int rollout_create(arp_dt* policy, arp_enc* encoder, arp_clip* reward, in
 }
 
 int arp_rollout_create(arp_dt* policy, arp_clip* reward, int n_envs, int H, int W, float scale, arp_rollout** out) {
-    return rollout_create(policy, nullptr, reward, n_envs, H, W, scale, out);
+    return rollout_create(policy, nullptr, reward, nullptr, n_envs, H, W, scale, out);
 }
 int arp_rollout_create_with_encoder(arp_dt* policy, arp_enc* encoder, arp_clip* reward, int n_envs, int H, int W, float scale, arp_rollout** out) {
     if (!encoder) return fail("null encoder");
-    return rollout_create(policy, encoder, reward, n_envs, H, W, scale, out);
+    return rollout_create(policy, encoder, reward, nullptr, n_envs, H, W, scale, out);
+}
+int arp_rollout_create_ft(arp_dt* policy, arp_enc* encoder_or_null, arp_clip* towers, arp_ft* head, int n_envs, int H, int W, float scale, arp_rollout** out) {
+    if (!towers || !head) return fail("null reward handle");
+    return rollout_create(policy, encoder_or_null, towers, head, n_envs, H, W, scale, out);
 }
 
 int arp_rollout_destroy(arp_rollout* s) {
@@ -308,7 +320,8 @@ static int rollout_step(arp_rollout* s, const uint8_t* frames_host, const float*
     if (s->clip) {  // 7. the reward pass, beside steps 2-6 on the labelling handle's own stream
         ARP_HIP_OK(hipEventRecord(s->ev_up, S));
         ARP_HIP_OK(hipStreamWaitEvent(s->clip_stream, s->ev_up, 0));
-        ARP_TRY(arp_clip_label_dev_async(s->clip, s->frames_u8.as<uint8_t>(), E, s->H, s->W, use_crop, s->reward.as<float>()));
+        if (s->ft) ARP_TRY(arp_ft_reward_dev_async(s->ft, s->clip, s->frames_u8.as<uint8_t>(), E, s->H, s->W, use_crop, 1 /* label transform */, s->reward.as<float>()));
+        else ARP_TRY(arp_clip_label_dev_async(s->clip, s->frames_u8.as<uint8_t>(), E, s->H, s->W, use_crop, s->reward.as<float>()));
     }
     // 2. ingest
     {

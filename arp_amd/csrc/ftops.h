@@ -43,6 +43,50 @@ static __global__ __launch_bounds__(256) void ft_mix_norm_fwd_kernel(const float
     for (int c = threadIdx.x; c < F; c += 256) a_out[(size_t)m * F + c] = (res * fr[c] + (1.f - res) * ar[c]) / n;
 }
 
+// ---- inference-only pieces of the resident reward path (arp_ft_reward_*) ------------------------------------------------------------
+// f[m, col0 + c] = fin[m, c] (the CLIP feature behind U = X Wint^T, which the GEMM already wrote into columns 0 .. col0 - 1 of the f32 row), then the whole
+// row in the operand type: fT[m, :] = T(f[m, :]).  One workgroup per row; the f32 row stays for the mix.  fT == nullptr (f32 mode): the GEMMs read f itself.
+template <typename T>
+static __global__ __launch_bounds__(256) void ft_pack_f_kernel(const float* __restrict__ fin, int E, float* __restrict__ f, T* __restrict__ fT, int F) {
+    const int m = blockIdx.x, col0 = F - E;
+    float* fr = f + (size_t)m * F;
+    for (int c = threadIdx.x; c < F; c += 256) {
+        float v;
+        if (c < col0) v = fr[c];
+        else fr[c] = v = fin[(size_t)m * E + (c - col0)];
+        if (fT) Elem<T>::st(fT + (size_t)m * F + c, v);
+    }
+}
+
+// reward[m] = scale * <y, t> / max(||y||, 1e-12),  y = res*f[m] + (1-res)*A[m]: mix, norm (ft_mix_norm_fwd_kernel's clamp) and the product with the cached
+// prompt vector in one pass; the adapted feature row is never written.  One workgroup per frame row, fixed summation order.
+static __global__ __launch_bounds__(256) void ft_reward_kernel(const float* __restrict__ f, const float* __restrict__ A, const float* __restrict__ rw,
+                                                               const float* __restrict__ t, float scale, float* __restrict__ reward, int F) {
+    __shared__ float red[4];
+    const int m = blockIdx.x;
+    const float res = 1.0f / (1.0f + expf(-rw[0]));
+    const float* fr = f + (size_t)m * F;
+    const float* ar = A + (size_t)m * F;
+    float ss = 0.f, d = 0.f;
+    for (int c = threadIdx.x; c < F; c += 256) {
+        const float y = res * fr[c] + (1.f - res) * ar[c];
+        ss += y * y;
+        d += y * t[c];
+    }
+    ss = ft_block_sum(ss, red);
+    d = ft_block_sum(d, red);
+    if (threadIdx.x == 0) reward[m] = scale * (d / fmaxf(sqrtf(ss), 1e-12f));
+}
+
+// mean[c] = (t[0, c] + t[1, c] + ...) / np, rows in order   (mean_p s <a, t_p> = s <a, mean_p t_p>)
+static __global__ __launch_bounds__(256) void ft_rows_mean_kernel(const float* __restrict__ t, float* __restrict__ mean, int np, int F) {
+    const int c = blockIdx.x * 256 + threadIdx.x;
+    if (c >= F) return;
+    float s = 0.f;
+    for (int p = 0; p < np; ++p) s += t[(size_t)p * F + c];
+    mean[c] = s / (float)np;
+}
+
 // s[k*B + b] = scale * <a[k*B + b], t[b]>   (the diagonal of logit_scale * a_k t^T, :203-207)
 static __global__ __launch_bounds__(256) void ft_scores_kernel(const float* __restrict__ a, const float* __restrict__ t, float scale,
                                                                float* __restrict__ s, int B, int F) {

@@ -272,12 +272,20 @@ class FinetunedClip:
     """``model = CLIPMultiscaleAdapter(...); model.load_state_dict(ckpt)`` of the ``clip_ft`` labelling branch
     (arp_dt/label_reward.py:166-177): frozen towers (``arp_amd.clip.ClipLabeller``) + trained head on one GPU."""
 
-    def __init__(self, towers, head):
+    TRANSFORMS = {"finetune": 0, "label": 1}   # arp_ft_reward's `transform`
+    REDUCES = {"first": 0, "mean": 1}          # arp_ft_reward_set_reduce
+
+    def __init__(self, towers, head, resident=False):
+        """``resident``: :meth:`label` and :meth:`online_reward` go through the device-resident path (:meth:`reward`) instead of the three host round
+        trips of the feature hand-over; may be switched at any time."""
         self.towers, self.head = towers, head
         self._text = None
+        self.resident = bool(resident)
+        self._reduce = "first"
+        self._resident_text_error = None
 
     @classmethod
-    def from_state_dict(cls, state_dict, mode="bf16", device=0, model="ViT-B/16", logit_scale=None):
+    def from_state_dict(cls, state_dict, mode="bf16", device=0, model="ViT-B/16", logit_scale=None, resident=False):
         """state_dict: the reference checkpoint's tensors as numpy (``clip_model.*`` = the CLIP weights, the rest = the head)."""
         from . import clip as aclip
         sd = {k: np.asarray(v) for k, v in state_dict.items()}
@@ -290,15 +298,78 @@ class FinetunedClip:
         head = FinetuneTrainer(FinetuneConfig(layers=ccfg.layers, width_v=ccfg.width, width_t=ccfg.txt_width, embed=ccfg.embed, hidden=hidden,
                                               n_actions=sd["inverse_layer.layers.3.weight"].shape[0], logit_scale=ls), mode=mode, device=device)
         head.load_state_dict({k: v for k, v in sd.items() if not k.startswith("clip_model.")})
-        return cls(towers, head)
+        return cls(towers, head, resident=resident)
 
     def set_text(self, tokens):
+        """Adapted prompt features on the host (``_text``, what the host path multiplies with) and, for the resident path, cached on the device.
+        After the head's parameters move (``set_tensors``, a train step, ``broadcast_state``) the device cache is stale: call this again."""
         self._text = self.head.encode_text(*self.towers.encode_text_multiscale(tokens))
+        self._resident_text_error = None
+        if not self.head.cfg.goal_conditioned:  # (the resident path refuses such a head: it has no goal frames)
+            t = np.require(np.asarray(tokens, dtype=np.int32).reshape(-1, self.towers.cfg.ctx), requirements="C")
+            try:
+                check(lib.arp_ft_reward_set_text(self.head._h, self.towers._h, _ffi.as_ptr(t, C.c_int32), t.shape[0]))
+            except _ffi.ArpError as e:
+                if self.resident:
+                    raise
+                self._resident_text_error = str(e)  # the host path does not need the cache: a resident call reports it
         return self
+
+    def set_prompt_reduce(self, mode):
+        """"first" (default): a resident reward is the logit of prompt 0 (label_reward.py:228); "mean": the mean over the cached prompts, the rollout
+        loop's branch for a LIST of prompts (envs/vl_reward.py:56-57).  The host path's ``online_reward(mean_over_prompts=...)`` is not affected."""
+        if mode not in self.REDUCES:
+            raise ValueError(f"set_prompt_reduce: {mode!r} is not one of {sorted(self.REDUCES)}")
+        self._reduce = mode
+        if self.head._h:
+            check(lib.arp_ft_reward_set_reduce(self.head._h, self.REDUCES[mode]))
+        return self
+
+    def reward(self, frames, use_crop=False, transform="finetune"):
+        """uint8 frames ``[n, H, W, 3]`` (or one ``[H, W, 3]``) -> float32 ``[n]`` fine-tuned rewards through the device-resident path
+        (``arp_ft_reward``): towers, the head's inference pass and the product with the cached prompt never leave the GPU.  ``transform``:
+        "finetune" (bilinear; what label_reward.py:200-230 feeds the model, ``use_crop`` = its centre crop of side W // 2) or "label" (Pillow
+        bicubic; what envs/vl_reward.py:44-61 feeds it in rollouts, ``use_crop`` as ``ClipLabeller.label``)."""
+        if transform not in self.TRANSFORMS:
+            raise ValueError(f"reward: transform {transform!r} is not one of {sorted(self.TRANSFORMS)}")
+        f = np.asarray(frames)
+        if f.ndim == 3:
+            f = f[None]
+        if f.ndim != 4 or f.shape[-1] != 3 or f.dtype != np.uint8:
+            raise ValueError("frames must be uint8 [n, H, W, 3]")
+        if self._resident_text_error:
+            raise _ffi.ArpError(self._resident_text_error)
+        f = np.require(f, requirements="C")
+        out = np.empty(f.shape[0], np.float32)
+        check(lib.arp_ft_reward(self.head._h, self.towers._h, _ffi.as_ptr(f, C.c_uint8), f.shape[0], f.shape[1], f.shape[2], int(bool(use_crop)),
+                                self.TRANSFORMS[transform], _ffi.as_ptr(out, C.c_float)))
+        return out
+
+    def set_rows_kernel(self, on):
+        """Calls of at most 16 frames run the head on the weight-streaming rows kernel (default) or, ``on=False``, on the training GEMMs (A/B)."""
+        check(lib.arp_ft_reward_set_rows(self.head._h, int(bool(on))))
+        return self
+
+    def reward_stats(self):
+        """Counts since the head was created: captured chains replayed / captured, calls launched one by one, products on the rows kernel."""
+        v = (C.c_int64 * 4)()
+        check(lib.arp_ft_reward_stats(self.head._h, v))
+        return {"replayed": v[0], "captured": v[1], "launched": v[2], "rows_products": v[3]}
+
+    def reward_device_async(self, frames_dev, n, h, w, rewards_dev, use_crop=False, transform="finetune"):
+        """The same on ``arp_amd.clip.DeviceBuffer`` s: enqueued on the towers' stream, nothing is waited for (``self.towers.sync()`` does)."""
+        if transform not in self.TRANSFORMS:
+            raise ValueError(f"reward: transform {transform!r} is not one of {sorted(self.TRANSFORMS)}")
+        if self._resident_text_error:
+            raise _ffi.ArpError(self._resident_text_error)
+        check(lib.arp_ft_reward_dev_async(self.head._h, self.towers._h, frames_dev.ptr if frames_dev is not None else None, int(n), int(h), int(w),
+                                          int(bool(use_crop)), self.TRANSFORMS[transform], rewards_dev.ptr if rewards_dev is not None else None))
 
     def label(self, images, use_crop=False):
         """compute_reward of the clip_ft branch (label_reward.py:197-228): exp(logit_scale) * <adapted image, adapted prompt 0>."""
         images = np.asarray(images)
+        if self.resident:  # (the centre crop is taken on the device; the reduction is set_prompt_reduce's, "first" by default as here)
+            return self.reward(images, use_crop=use_crop, transform="finetune")
         if use_crop:  # center_crop(images, (image_size // 2,) * 2), image_size = the frame WIDTH (label_reward.py:15-36,104,203)
             h, w = images.shape[1:3]
             cs = w // 2
@@ -319,6 +390,15 @@ class FinetunedClip:
     def online_reward(self, obs, mean_over_prompts=False, use_crop=False):
         """get_torch_clip_adapter_reward (vl_reward.py:44-61): exp(logit_scale) * <adapted image, adapted prompt p>, prompt 0 -- or the mean over
         the cached prompts where the reference's ``pos_text`` is a list.  float32 [1]."""
+        if self.resident:  # one frame in, one reward out, through the label transform; the reduction is this call's
+            want, keep = "mean" if mean_over_prompts else "first", self._reduce
+            try:  # (the handle's reduction is shared with a RolloutSession that uses this model: put back what was set)
+                if want != keep:
+                    self.set_prompt_reduce(want)
+                return self.reward(np.asarray(obs), use_crop=use_crop, transform="label")[:1]
+            finally:
+                if want != keep:
+                    self.set_prompt_reduce(keep)
         a = self._online_features(obs, use_crop)
         logit = np.exp(self.head.cfg.logit_scale) * (self._text @ a[0])  # [n_prompts]
         return np.asarray([logit.mean() if mean_over_prompts else logit[0]], np.float32)

@@ -30,9 +30,10 @@ class RolloutSession:
     """``n_envs`` independent environments behind one ARP-DT policy with its frozen encoder attached (``trainer.attach_encoder``).
 
     ``reward_model``: an :class:`arp_amd.clip.ClipLabeller` with its prompts set (its ``prompt_reduce`` and the step's ``use_crop``
-    apply) -- the reward of every frame is then computed on the device and never read by the host; ``None``: pass ``rewards=`` to
-    :meth:`step` (computed by the caller with any of ``VL_REWARD_FNS``: the goal-conditioned and fine-tuned variants), or nothing,
-    and the return-to-go stays constant.  ``return_to_go / scale`` is every episode's first return-to-go (rollout_procgen.py:90).
+    apply), or an :class:`arp_amd.finetune.FinetunedClip` with its prompts set (the fine-tuned reward through the label transform,
+    ``get_torch_clip_adapter_reward``; its ``set_prompt_reduce`` and the step's ``use_crop`` apply) -- the reward of every frame is then
+    computed on the device and never read by the host; ``None``: pass ``rewards=`` to :meth:`step` (computed by the caller with any of
+    ``VL_REWARD_FNS``: the goal-conditioned variants), or nothing, and the return-to-go stays constant.  ``return_to_go / scale`` is every episode's first return-to-go (rollout_procgen.py:90).
     ``encoder``: the encoder to use instead of the trainer's attached one.  Model BC (``PolicyConfig(model="BC")``) runs this way -- it refuses
     ``attach_encoder`` and keeps refusing it, the session borrows the encoder for its own passes: two tokens per step, no return-to-go ring, and a reward
     model, ``use_normalize`` / ``reward_min`` and ``rewards=`` are refused by the library.
@@ -40,14 +41,23 @@ class RolloutSession:
 
     def __init__(self, trainer, reward_model=None, n_envs=1, return_to_go=100.0, scale=100.0, reward_min=0.0, use_normalize=False, lut=None, encoder=None):
         from . import _ffi, dataset
+        from .finetune import FinetunedClip
         self._ffi = _ffi
+        finetuned = isinstance(reward_model, FinetunedClip)
+        if reward_model is not None and not finetuned and not hasattr(reward_model, "_h"):
+            raise ValueError(f"reward_model: a ClipLabeller, a FinetunedClip or None, not {type(reward_model).__name__}")
         enc = encoder if encoder is not None else getattr(trainer, "_encoder", None)
         if getattr(trainer.cfg, "use_symlog", False):
             raise _ffi.ArpError("use_symlog: the session embeds rtg / scale, not its symlog")
         res = enc.cfg.img_res if enc is not None else 0
         h = C.c_void_p()
-        rm = reward_model._h if reward_model is not None else None
-        if encoder is not None:
+        rm = reward_model._h if reward_model is not None and not finetuned else None
+        if finetuned:  # the fine-tuned reward: its towers and its head (both kept alive through reward_model below)
+            if reward_model._resident_text_error:
+                raise _ffi.ArpError(reward_model._resident_text_error)
+            _ffi.check(_ffi.lib.arp_rollout_create_ft(trainer._h, encoder._h if encoder is not None else None, reward_model.towers._h,
+                                                      reward_model.head._h, int(n_envs), res, res, float(scale), C.byref(h)))
+        elif encoder is not None:
             _ffi.check(_ffi.lib.arp_rollout_create_with_encoder(trainer._h, encoder._h, rm, int(n_envs), res, res, float(scale), C.byref(h)))
         else:
             _ffi.check(_ffi.lib.arp_rollout_create(trainer._h, rm, int(n_envs), res, res, float(scale), C.byref(h)))

@@ -333,6 +333,41 @@ int arp_ft_forward(arp_ft* h, float* metrics4, float* scores, float* logits);
  * labelling branch calls them (arp_dt/label_reward.py:165-230): tower features [n, layers*width] + [n, embed] -> adapted,
  * L2-normalised features [n, layers*width_t + embed].  Drops a batch staged with arp_ft_set_batch. */
 int arp_ft_encode(arp_ft* h, int which, const float* inter, const float* final_feat, int n, float* out);
+/* ---- the fine-tuned CLIP reward, resident on the device (model_type = "clip_ft": label_reward.py:165-230, envs/vl_reward.py:44-61) ----
+ * uint8 frames in HBM -> frozen towers (`towers`: a finalized arp_clip on the same device whose widths, layers and embed are the head's) -> the head's
+ * inference pass -> exp(logit_scale) <adapted image, adapted prompt> as one f32 per frame in HBM.  Everything is enqueued on the TOWERS' stream; the only
+ * synchronisations are the ones named below.  The pass has a workspace of its own: a batch staged with arp_ft_set_batch survives it.  It rounds where the
+ * training forward rounds (tower features, [U | final] and the hidden layer become the operand type; the rest is f32).
+ * arp_ft_reward_set_text: the text side, once per prompt set, cached on the device (adapted, normalised prompts and their mean); synchronises.  The cache
+ * belongs to the parameters of that moment: after arp_ft_set_tensor(which = 0), a train step or arp_ft_broadcast_state every reward call is REFUSED until
+ * the text is set again.  transform: 0 = the fine-tune transform (bilinear; use_crop = the centre crop of side W / 2 at int((H - cs) / 2), int((W - cs) / 2),
+ * taken on the device: label_reward.py:200-230), 1 = the label transform (Pillow bicubic, use_crop as arp_clip_label: envs/vl_reward.py:44-61).
+ * arp_ft_reward_dev_async: any n >= 1, chunks of the towers' max_batch in stream order, no synchronisation; a call that fits the towers' latency path is
+ * captured once per (buffers, n, geometry, transform, reduction) and replayed (ARP_FT_REWARD_GRAPH=0: launch by launch).  arp_ft_reward: the same from
+ * and to host memory (pinned staging while a chunk is at most 8 MiB of frames), one synchronisation per chunk; writes rewards[0 .. n - 1] only.
+ * Refused with a message: towers and head on different devices or of different geometry, a goal_conditioned head, no prompts cached, stale prompts, null
+ * or empty buffers.  The two handles stay the caller's; the towers' stream must not be used by another host thread during a call. */
+int arp_ft_reward_set_text(arp_ft* h, arp_clip* towers, const int32_t* tokens /* [n_prompts, ctx] */, int n_prompts);
+int arp_ft_reward_set_reduce(arp_ft* h, int mean); /* 0: prompt 0 (label_reward.py:228), 1: the mean over the prompts (:226, envs/vl_reward.py:56-57) */
+int arp_ft_reward_dev_async(arp_ft* h, arp_clip* towers, const uint8_t* frames_dev, int n, int H, int W, int use_crop, int transform, float* rewards_dev);
+int arp_ft_reward(arp_ft* h, arp_clip* towers, const uint8_t* frames, int n, int H, int W, int use_crop, int transform, float* rewards);
+/* The reward kernel of that path alone: reward[r] = scale * <y, t> / max(||y||, 1e-12), y = s f[r] + (1 - s) A[r], s = sigmoid(rw); t = prompt row 0, or
+ * (mean = 1) the mean of the n_prompts rows [n_prompts, F], taken on the device.  f, A [rows, F]; all f32 host arrays. */
+/* Calls of at most 16 rows run the head's three products on a weight-streaming kernel (csrc/ftrows.h; 16-bit modes) unless on = 0 (or ARP_FT_ROWS=0):
+ * then, as for more rows, the training GEMMs.  arp_ft_reward_stats: out4 = {captured chains replayed, chains captured, calls launched one by one,
+ * products run on the rows kernel} since the handle was created.
+ * Ordering against training: the reward calls run on the TOWERS' stream and read the head's parameters.  Every reward call records an event behind
+ * itself; arp_ft_set_tensor of a parameter, the train steps and arp_ft_broadcast_state wait for it before the parameters move, and the version rule
+ * refuses the reward calls made after that. */
+int arp_ft_reward_set_rows(arp_ft* h, int on);
+int arp_ft_reward_stats(arp_ft* h, int64_t out4[4]);
+/* The rows kernel alone + the split-K reduce behind it: out[m, n] (ldo; out_rows >= M rows prefilled by the caller, only [0, M) x [0, N) is written) =
+ * act(A[M, K] (lda) . W[N, K]^T (ldw) + bias), operands in the type of `mode` (bf16 / f16), output in that type (widened back) or f32.  act: none or relu.
+ * ksplit = 0: the dispatcher's slice count.  Returns the slice count used; -1 with a message outside the domain (1 <= M <= 16, K % 64 == 0, N % 16 == 0,
+ * lda and ldw multiples of 8) -- nothing is written then. */
+int arp_op_ft_rows_gemm(int mode, int act, const float* A, int lda, const float* W, int ldw, const float* bias, float* out, int ldo, int out_rows, int out_f32,
+                        int M, int N, int K, int ksplit);
+int arp_op_ft_reward(const float* f, const float* A, float rw, const float* t, int n_prompts, int mean, float scale, float* reward, int rows, int F);
 int arp_ft_backward(arp_ft* h);                        /* forward + backward: fills every gradient */
 int arp_ft_train_step(arp_ft* h, float lr, float* aux4); /* forward + backward + AdamW; aux4 as metrics4 (pre-update) */
 int arp_ft_train_step_async(arp_ft* h, float lr);
@@ -447,6 +482,12 @@ int arp_rollout_create(arp_dt* policy, arp_clip* reward_or_null, int n_envs, int
  * the policy's enc_tokens x enc_dim.  For a BC policy a reward handle, arp_rollout_set_reward_norm and `rewards` in arp_rollout_step are refused with an
  * error string (BC.encode reads no return-to-go), and "rtg_window" does not exist. */
 int arp_rollout_create_with_encoder(arp_dt* policy, arp_enc* encoder, arp_clip* reward_or_null, int n_envs, int H, int W, float scale, arp_rollout** out);
+/* The same with the FINE-TUNED reward (get_torch_clip_adapter_reward, envs/vl_reward.py:44-61): at the place of the plain CLIP pass the step enqueues
+ * arp_ft_reward_dev_async(head, towers, ..., transform = label) on the towers' stream; events, the return-to-go kernel and use_normalize / reward_min are
+ * unchanged, `rewards` is refused as for any session that owns a reward source, and model BC refuses this reward source too.  encoder_or_null as the two
+ * constructors above.  The head's prompts (arp_ft_reward_set_text, arp_ft_reward_set_reduce) may be set before or after creation, and must be current at
+ * every step.  Refused at creation: towers and head on different devices or of different geometry, a goal_conditioned head. */
+int arp_rollout_create_ft(arp_dt* policy, arp_enc* encoder_or_null, arp_clip* towers, arp_ft* head, int n_envs, int H, int W, float scale, arp_rollout** out);
 int arp_rollout_destroy(arp_rollout* h);
 /* start an episode in the n listed environments: return-to-go rtg0[i] (already divided by scale, as :90), episode length 0 */
 int arp_rollout_reset(arp_rollout* h, const int32_t* env_ids, int n, const float* rtg0);
