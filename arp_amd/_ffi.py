@@ -44,7 +44,7 @@ class DtCfg(C.Structure):
 
 
 # arp_dt_cfg.model (include/arp_hip.h): which policy a handle trains
-DT_MODELS = {"ARPDT": 0, "BC": 1}
+DT_MODELS = {"ARPDT": 0, "BC": 1, "GCBC": 2}
 
 
 class FtCfg(C.Structure):
@@ -202,12 +202,15 @@ SIGNATURES = {
     "arp_enc_load_weight": (_i, [_vp, C.c_char_p, _fp, _i64p, _i]),
     "arp_enc_finalize_weights": (_i, [_vp]),
     "arp_enc_forward": (_i, [_vp, _fp, _i, _fp]),
+    "arp_enc_forward_gc": (_i, [_vp, _fp, _fp, _i, _fp]),
+    "arp_enc_gc_tokens": (_i, [_vp]),
     "arp_enc_set_streams": (_i, [_vp, _i, _i, _i]),
     "arp_enc_set_latency": (_i, [_vp, _i, _i]),
     "arp_enc_profile_enable": (_i, [_vp, _i]),
     "arp_enc_profile_json": (_i, [_vp, C.c_char_p, _i]),
     "arp_dt_attach_encoder": (_i, [_vp, _vp]),
     "arp_dt_set_batch_images": (_i, [_vp, _fp, _i32p, _fp, _i]),
+    "arp_dt_set_batch_images_goal": (_i, [_vp, _fp, _fp, _i32p, _i]),
     "arp_dt_encode_ahead": (_i, [_vp, _i]),
     "arp_ds_create": (_i, [C.c_int64, _i, _i, C.POINTER(_vp)]),
     "arp_ds_destroy": (_i, [_vp]),

@@ -79,6 +79,8 @@ struct arp_dt {
     struct BatchSlot {
         DevBuf enc32, action, rtg;
         DevBuf img32;             // raw frames [B*T, res, res, 3] f32 when the encoder is attached
+        DevBuf goal32;            // model GCBC: the goal frames, same shape (arp_dt_set_batch_images_goal; the synchronous slot only)
+        bool goals = false;       // the frames in img32 come with goals in goal32: the encoder pass is the goal-conditioned one
         int B = 0;
         bool images = false;
         Event up;   // recorded on the copy stream behind the slot's upload
@@ -205,7 +207,10 @@ struct arp_dt {
     DevBuf dres_part;  // per-workgroup d loss / d res partials of adapter_dy_kernel
     int R() const { return B * cfg.window; }
     // model BC (the InstructRL baseline, arp_dt/BC.py): two tokens per time step [image, action] instead of ARP-DT's three
-    bool bc() const { return cfg.model == ARP_DT_MODEL_BC; }
+    // BC's policy: two tokens per time step, no return-to-go, no return head.  GCBC (arp_dt/GCBC.py) is that policy line for line; what it changes is the frozen
+    // encoder call in front (forward_gc_representations on a (frame, goal) pair), so inside the step a GCBC handle IS a BC handle.
+    bool bc() const { return cfg.model == ARP_DT_MODEL_BC || cfg.model == ARP_DT_MODEL_GCBC; }
+    bool gcbc() const { return cfg.model == ARP_DT_MODEL_GCBC; }
     int tps() const { return bc() ? 2 : 3; }
     int L() const { return tps() * cfg.window; }
     float* p(const std::string& n) { return params.as<float>() + infos[index.at(n)].off; }
@@ -245,7 +250,7 @@ void build_layout(arp_dt* c) {
     add_param(c, v, "image_text_input/kernel", {(int64_t)k.enc_tokens * D, E});
     add_param(c, v, "image_text_input/bias", {E});
     add_param(c, v, "action_input/embedding", {k.n_actions, E});
-    const bool bc = k.model == ARP_DT_MODEL_BC;  // BC.py:87-100: no rtg_input, no return_outputs_*; otherwise ARP-DT's tree
+    const bool bc = k.model != ARP_DT_MODEL_ARPDT;  // BC.py:87-100 (GCBC.py: the same tree): no rtg_input, no return_outputs_*; otherwise ARP-DT's tree
     if (!bc) add_param(c, v, "rtg_input/kernel", {1, E});
     for (int i = 0; i < k.depth; ++i) {
         const std::string p = "policy/Block_" + std::to_string(i) + "/";
@@ -448,7 +453,7 @@ bool fused_eligible(const arp_dt_cfg& k) {
     const int E = k.emb, H = k.mlp_ratio * k.emb;
     // instantiated geometries: the shipped one (E = 128, mlp_ratio 4) and the half-width one the tests use
     const bool shape = (E == 128 && H == 512) || (E == 64 && H == 256);
-    const int tps = k.model == ARP_DT_MODEL_BC ? 2 : 3;
+    const int tps = k.model != ARP_DT_MODEL_ARPDT ? 2 : 3;
     return shape && tps * k.window <= 16 && k.n_actions <= 16 && k.depth <= PF_MAX_DEPTH && E % k.heads == 0 && (E / k.heads) % 16 == 0 &&
            pf_lds_bytes(E, H, k.heads, k.depth) <= 160 * 1024;
 }
@@ -692,15 +697,21 @@ int enqueue_encode(arp_dt* c, int slot, bool after_compute) {
         if (b.up_recorded) ARP_HIP_OK(hipStreamWaitEvent(c->enc_stream, b.up, 0));
         if (b.used) ARP_HIP_OK(hipStreamWaitEvent(c->enc_stream, b.use, 0));
     }
-    ARP_TRY(enc_forward_on(c->enc, c->enc_stream, b.img32.as<float>(), b.B * c->cfg.window, b.enc32.as<float>()));
+    if (c->gcbc() && !b.goals) return fail("encode: model GCBC encodes (frame, goal) pairs and this slot holds no goal frames");
+    if (b.goals) ARP_TRY(enc_forward_gc_on(c->enc, c->enc_stream, b.img32.as<float>(), b.goal32.as<float>(), b.B * c->cfg.window, b.enc32.as<float>()));
+    else ARP_TRY(enc_forward_on(c->enc, c->enc_stream, b.img32.as<float>(), b.B * c->cfg.window, b.enc32.as<float>()));
     ARP_HIP_OK(hipEventRecord(b.enc_done, c->enc_stream));
     b.enc_ahead = true;
     return 0;
 }
 // frames -> encodings for the CURRENT slot, ahead of the step's own launches on the compute stream
 int encode_current(arp_dt* c) {
-    if (!c->enc_eager)  // rounds 1-5: on the step's own stream (ARP_DT_ENC_EAGER=0: inside the captured chain)
+    if (c->gcbc() && !c->bt[c->cur].goals) return fail("encode: model GCBC encodes (frame, goal) pairs and this slot holds no goal frames");
+    if (!c->enc_eager) {  // rounds 1-5: on the step's own stream (ARP_DT_ENC_EAGER=0: inside the captured chain)
+        if (c->bt[c->cur].goals)
+            return enc_forward_gc_on(c->enc, c->stream, c->bt[c->cur].img32.as<float>(), c->bt[c->cur].goal32.as<float>(), c->R(), c->bt[c->cur].enc32.as<float>());
         return enc_forward_on(c->enc, c->stream, c->bt[c->cur].img32.as<float>(), c->R(), c->bt[c->cur].enc32.as<float>());
+    }
     arp_dt::BatchSlot& b = c->bt[c->cur];
     if (!b.enc_ahead) {
         std::lock_guard<std::mutex> lock(c->capture_mu);
@@ -1425,8 +1436,9 @@ int arp_dt_create(const arp_dt_cfg* cfg, arp_dt** out) {
     if (hd != 16 && hd != 32 && hd != 64) return fail("head_dim must be 16, 32 or 64");
     const int kq = k.mode == ARP_MODE_F32 ? 32 : 64;
     if (k.enc_dim % kq || k.emb % kq) return fail("enc_dim and emb must be multiples of " + std::to_string(kq));
-    if (k.model != ARP_DT_MODEL_ARPDT && k.model != ARP_DT_MODEL_BC) return fail("model must be ARP_DT_MODEL_ARPDT (0) or ARP_DT_MODEL_BC (1)");
-    const int tps = k.model == ARP_DT_MODEL_BC ? 2 : 3;
+    if (k.model != ARP_DT_MODEL_ARPDT && k.model != ARP_DT_MODEL_BC && k.model != ARP_DT_MODEL_GCBC)
+        return fail("model must be ARP_DT_MODEL_ARPDT (0), ARP_DT_MODEL_BC (1) or ARP_DT_MODEL_GCBC (2)");
+    const int tps = k.model != ARP_DT_MODEL_ARPDT ? 2 : 3;
     if (k.window <= 0 || tps * k.window > 64) return fail(std::string("window must be in 1..") + (tps == 3 ? "21" : "32"));
     if (k.depth <= 0 || k.n_actions <= 0 || k.enc_tokens <= 0 || k.mlp_ratio <= 0) return fail("bad geometry");
     int ndev = 0;
@@ -1569,13 +1581,14 @@ int arp_dt_get_step(arp_dt* c, int64_t* step) {
 
 // Host -> device copy of one batch into slot `si` on stream `st`.  Touches only the slot's own buffers (the caller may be a
 // prefetch thread working beside a running step on the other slot); frames != nullptr: the encoder-in-front boundary (row N1).
-static int stage_slot(arp_dt* c, int si, hipStream_t st, const float* enc, const float* frames, const int32_t* action, const float* rtg, int B) {
+static int stage_slot(arp_dt* c, int si, hipStream_t st, const float* enc, const float* frames, const int32_t* action, const float* rtg, int B,
+                      const float* goals = nullptr) {
     const int R = B * c->cfg.window;
     for (int i = 0; i < R; ++i)
         if (action[i] < 0 || action[i] >= c->cfg.n_actions) return fail("action id out of range");
     arp_dt::BatchSlot& b = c->bt[si];
     ARP_TRY(b.action.ensure((size_t)R * 4));
-    const bool with_rtg = c->cfg.model != ARP_DT_MODEL_BC;  // BC.encode reads no rtg (a non-NULL one is ignored)
+    const bool with_rtg = !c->bc();  // BC.encode reads no rtg (a non-NULL one is ignored)
     if (with_rtg) ARP_TRY(b.rtg.ensure((size_t)R * 4));
     const size_t Mx = (size_t)R * c->cfg.enc_tokens;
     ARP_TRY(b.enc32.ensure(Mx * c->cfg.enc_dim * 4));  // with frames in: the encoder's output buffer
@@ -1585,6 +1598,10 @@ static int stage_slot(arp_dt* c, int si, hipStream_t st, const float* enc, const
         const size_t fb = (size_t)res * res * 3 * 4;
         ARP_TRY(b.img32.ensure((size_t)R * fb));
         ARP_HIP_OK(hipMemcpyAsync(b.img32.p, frames, (size_t)R * fb, hipMemcpyHostToDevice, st));
+        if (goals) {
+            ARP_TRY(b.goal32.ensure((size_t)R * fb));
+            ARP_HIP_OK(hipMemcpyAsync(b.goal32.p, goals, (size_t)R * fb, hipMemcpyHostToDevice, st));
+        }
     } else {
         ARP_HIP_OK(hipMemcpyAsync(b.enc32.p, enc, Mx * c->cfg.enc_dim * 4, hipMemcpyHostToDevice, st));
     }
@@ -1592,6 +1609,7 @@ static int stage_slot(arp_dt* c, int si, hipStream_t st, const float* enc, const
     if (with_rtg) ARP_HIP_OK(hipMemcpyAsync(b.rtg.p, rtg, (size_t)R * 4, hipMemcpyHostToDevice, st));
     b.B = B;
     b.images = frames != nullptr;
+    b.goals = frames != nullptr && goals != nullptr;
     return 0;
 }
 
@@ -1617,6 +1635,7 @@ static int upload_async(arp_dt* c, int slot, const float* enc, const float* fram
     if (!c || (!enc && !frames) || !action || B <= 0 || slot < 0 || slot > 1) return fail("bad argument");
     if (!rtg && !c->bc()) return fail("rtg is NULL (only model BC takes no return-to-go)");
     if (frames && !c->enc) return fail("no encoder attached: call arp_dt_attach_encoder first");
+    if (frames && c->gcbc()) return fail("model GCBC: frames need their goal frames, and goal batches exist in the synchronous slot only (arp_dt_set_batch_images_goal)");
     ARP_HIP_OK(hipSetDevice(c->cfg.device));
     arp_dt::BatchSlot& b = c->bt[slot];
     // Behind the slot's last reader: a HOST-side wait on the event that step recorded (already complete when the caller follows
@@ -1670,9 +1689,10 @@ static int stage_slot_indices(arp_dt* c, int si, hipStream_t st, arp_ds* ds, con
     int tokens = k.enc_tokens, width = k.enc_dim, res = 0, dev = k.device;
     if (!use_encodings) {
         if (!c->enc) return fail("no encoder attached: index batches of frames need arp_dt_attach_encoder first (or use_encodings with cached encodings)");
+        if (c->gcbc()) return fail("model GCBC: the device-resident dataset gathers no goal frames (stage frames and goals with arp_dt_set_batch_images_goal)");
         ARP_TRY(enc_geometry(c->enc, &tokens, &width, &res, &dev));
     }
-    const bool with_rtg = k.model != ARP_DT_MODEL_BC;
+    const bool with_rtg = !c->bc();
     ARP_TRY(ds_check_batch(ds, idx, B, k.window, k.device, k.n_actions, with_rtg, use_encodings ? 1 : 0, res, k.enc_tokens, k.enc_dim));
     arp_dt::BatchSlot& b = c->bt[si];
     const size_t R = (size_t)B * k.window;
@@ -1691,6 +1711,7 @@ static int stage_slot_indices(arp_dt* c, int si, hipStream_t st, arp_ds* ds, con
     if (t0) c->prof.end(use_encodings ? "ds.gather_encodings" : "ds.gather_frames", t0, st);
     b.B = B;
     b.images = !use_encodings;
+    b.goals = false;
     return 0;
 }
 
@@ -1731,23 +1752,40 @@ int arp_dt_attach_encoder(arp_dt* c, arp_enc* enc) {
     if (!c || !enc) return fail("null argument");
     // The reference's InstructRL encoder sees the BERT-tokenized instruction beside the frame (BC.py:286-321: 1 + 256 + 77 tokens); this encoder is
     // M3AE's image path alone, so a BC policy behind it would be a model the reference never trains.
-    if (c->bc()) return fail("model BC takes encodings (enc_tokens per frame, the instruction's text tokens included): the image-only encoder cannot be attached");
+    if (c->bc() && !c->gcbc()) return fail("model BC takes encodings (enc_tokens per frame, the instruction's text tokens included): the image-only encoder cannot be attached");
     int tokens = 0, width = 0, res = 0, dev = 0;
     ARP_TRY(enc_geometry(enc, &tokens, &width, &res, &dev));
+    // GCBC's encoder call reads no text (GCBC.py:462-468: forward_gc_representations(patch, goal_patch)): one sequence of 2 P + 1 tokens per (frame, goal) pair
+    if (c->gcbc()) ARP_TRY(enc_gc_tokens(enc, &tokens));
     if (tokens != c->cfg.enc_tokens || width != c->cfg.enc_dim) return fail("encoder geometry does not match enc_tokens / enc_dim");
     if (dev != c->cfg.device) return fail("encoder lives on another device");
     c->enc = enc;
     return 0;
 }
 
+static int set_batch_frames(arp_dt* c, const float* images, const float* goals, const int32_t* action, const float* rtg, int B);
+
 int arp_dt_set_batch_images(arp_dt* c, const float* images, const int32_t* action, const float* rtg, int B) {
+    if (c && c->gcbc()) return fail("model GCBC encodes (frame, goal) pairs: stage frames and goals with arp_dt_set_batch_images_goal");
     if (!c || !images || !action || !rtg || B <= 0) return fail("bad argument");
+    return set_batch_frames(c, images, nullptr, action, rtg, B);
+}
+
+// Model GCBC's synchronous staging slot: frames and goal frames, both [B, T, res, res, 3] f32, and the actions; the step then runs the goal-conditioned
+// encoder pass (enc_forward_gc_on) where an ARP-DT step runs enc_forward_on.
+int arp_dt_set_batch_images_goal(arp_dt* c, const float* images, const float* goals, const int32_t* action, int B) {
+    if (!c || !images || !goals || !action || B <= 0) return fail("bad argument");
+    if (!c->gcbc()) return fail("goal frames belong to model GCBC (ARP_DT_MODEL_GCBC)");
+    return set_batch_frames(c, images, goals, action, nullptr, B);
+}
+
+static int set_batch_frames(arp_dt* c, const float* images, const float* goals, const int32_t* action, const float* rtg, int B) {
     if (!c->enc) return fail("no encoder attached: call arp_dt_attach_encoder first");  // (never the case for model BC: arp_dt_attach_encoder refuses it)
     ARP_HIP_OK(hipSetDevice(c->cfg.device));
     c->cur = 2;  // the synchronous slot
     if (c->bt[2].enc_ahead && c->enc_stream) ARP_HIP_OK(hipStreamSynchronize(c->enc_stream));  // (an encode-ahead pass still reading the frames about to be replaced)
     c->bt[2].enc_ahead = false;
-    ARP_TRY(stage_slot(c, 2, c->stream, nullptr, images, action, rtg, B));
+    ARP_TRY(stage_slot(c, 2, c->stream, nullptr, images, action, rtg, B, goals));
     ARP_TRY(ensure_buffers(c, B));
     ARP_HIP_OK(hipStreamSynchronize(c->stream));
     c->use_images = true;
@@ -1762,6 +1800,7 @@ int arp_dt_set_batch_images(arp_dt* c, const float* images, const int32_t* actio
 int arp_dt_encode_ahead(arp_dt* c, int slot) {
     if (!c || slot < 0 || slot > 2) return fail("bad argument");
     if (!c->enc) return fail("no encoder attached: call arp_dt_attach_encoder first");
+    if (c->gcbc()) return fail("model GCBC: no encode-ahead (goal batches exist in the synchronous slot only, and their step encodes them)");
     if (!c->enc_eager) return fail("arp_dt_encode_ahead needs the eager encoder path (ARP_DT_ENC_EAGER=0 captures the encoder inside the step's graph)");
     ARP_HIP_OK(hipSetDevice(c->cfg.device));
     std::lock_guard<std::mutex> lock(c->capture_mu);
@@ -1775,7 +1814,7 @@ namespace arp {
 int dt_rollout_info(arp_dt* c, DtRolloutInfo* o) {
     if (!c || !o) return fail("null argument");
     o->window = c->cfg.window; o->enc_tokens = c->cfg.enc_tokens; o->enc_dim = c->cfg.enc_dim; o->n_actions = c->cfg.n_actions;
-    o->device = c->cfg.device; o->bc = c->bc() ? 1 : 0; o->enc = c->enc; o->stream = c->stream;
+    o->device = c->cfg.device; o->bc = c->bc() ? 1 : 0; o->gcbc = c->gcbc() ? 1 : 0; o->enc = c->enc; o->stream = c->stream;
     return 0;
 }
 

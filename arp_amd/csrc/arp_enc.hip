@@ -55,6 +55,37 @@ __global__ __launch_bounds__(256) void enc_assemble_kernel(const float* __restri
     store4(x + i, v[0], v[1], v[2], v[3]);
 }
 
+// The goal-conditioned sequence (forward_gc_representations, arp_dt/models/m3ae/model.py:498-525): class token, the frame's GG patches, the goal frame's GG patches;
+// both patch blocks take the same position (+ type) embedding.  pe holds the patch embeddings of the nb frames first, then those of the nb goals:
+//   x[b, 0] = cls;  x[b, 1 + p] = pe[b*GG + p] + pos[p];  x[b, 1 + GG + p] = pe[(nb + b)*GG + p] + pos[p]
+__global__ __launch_bounds__(256) void enc_assemble_gc_kernel(const float* __restrict__ pe, const float* __restrict__ cls, const float* __restrict__ pos,
+                                                              float* __restrict__ x, int nb, int GG, int D) {
+    const int ntok = 2 * GG + 1;
+    const size_t i = ((size_t)blockIdx.x * 256 + threadIdx.x) * 4;
+    if (i >= (size_t)nb * ntok * D) return;
+    const int c = (int)(i % D);
+    const size_t row = i / D;
+    const int t = (int)(row % ntok);
+    const size_t b = row / ntok;
+    float v[4];
+    if (t == 0) {
+        load4(cls + c, v);
+    } else {
+        const int goal = t > GG, p = t - 1 - (goal ? GG : 0);
+        float p4[4];
+        load4(pe + (((goal ? (size_t)nb : 0) + b) * GG + p) * D + c, v);
+        load4(pos + (size_t)p * D + c, p4);
+        v[0] += p4[0]; v[1] += p4[1]; v[2] += p4[2]; v[3] += p4[3];
+    }
+    store4(x + i, v[0], v[1], v[2], v[3]);
+}
+int launch_assemble_gc(hipStream_t stream, const float* pe, const float* cls, const float* pos, float* x, int nb, int GG, int D) {
+    const size_t tot = (size_t)nb * (2 * GG + 1) * D;
+    hipLaunchKernelGGL(enc_assemble_gc_kernel, dim3((unsigned)((tot / 4 + 255) / 256)), dim3(256), 0, stream, pe, cls, pos, x, nb, GG, D);
+    ARP_HIP_OK(hipGetLastError());
+    return 0;
+}
+
 // ARP_MODE_F16X3: f32 [rows, K] -> binary16 [rows, 3K] = [hi | lo | hi], hi = rn16(x), lo = rn16(x - hi): the A operand of a K-concatenated product against
 // [W_hi | W_hi | W_lo] -- x.W to ~2^-22 on three 16-bit MFMAs (hi.hi is exact in the f32 accumulator; lo.lo, ~2^-24, is dropped).  Values whose lo falls below
 // binary16's normal range keep an absolute error <= 3e-8 (subnormals are not flushed on this path).  8 elements per thread.
@@ -176,6 +207,7 @@ struct arp_enc {
     Profiler prof;
     int gemm_force = 0;
     int tokens() const { return (cfg.img_res / cfg.patch) * (cfg.img_res / cfg.patch) + 1; }
+    int gc_tokens() const { return 2 * (tokens() - 1) + 1; }  // a (frame, goal) pair: class token + both frames' patches
     size_t esz() const { return (cfg.mode == ARP_MODE_F32 || cfg.mode == ARP_MODE_F16X3) ? 4 : 2; }  // element size of the ACTIVATION buffers
     size_t wsz() const { return cfg.mode == ARP_MODE_F32 ? 4 : 2; }
 };
@@ -286,9 +318,11 @@ int ensure_ws(arp_enc* c, arp_enc::Ws& w, int frames) {
     return 0;
 }
 
-template <typename T> int forward_chunk(arp_enc* c, arp_enc::Ws& w, hipStream_t stream, const float* img_dev, int nb, float* out_dev) {
+// goal_dev != null (here and in forward_chunk_x3): nb (frame, goal) pairs -- both frame sets through patchify and ONE patch-embedding product of 2 nb GG rows,
+// the goal-conditioned assembly, then the blocks over 2 GG + 1 tokens per sample.  goal_dev == null is the plain pass, launch for launch what it always was.
+template <typename T> int forward_chunk(arp_enc* c, arp_enc::Ws& w, hipStream_t stream, const float* img_dev, int nb, float* out_dev, const float* goal_dev) {
     const arp_enc_cfg& k = c->cfg;
-    const int G = k.img_res / k.patch, N = c->tokens(), D = k.width, KP = k.patch * k.patch * 3;
+    const int G = k.img_res / k.patch, N = goal_dev ? c->gc_tokens() : c->tokens(), D = k.width, KP = k.patch * k.patch * 3;
     TowerCtx t;
     t.stream = stream; t.prof = &c->prof; t.attn_impl = k.attn_impl; t.gemm_force = c->gemm_force; t.shared_chip = c->shared_chip;
     if (sizeof(T) == 2 && c->lat_now) {  // (the patch embedding below then goes through tower_gemm's skinny route where skinny_supported holds)
@@ -300,10 +334,18 @@ template <typename T> int forward_chunk(arp_enc* c, arp_enc::Ws& w, hipStream_t 
         hipLaunchKernelGGL((patchify_kernel<T>), dim3((unsigned)((tot / 4 + 255) / 256)), dim3(256), 0, stream, img_dev, w.patches.as<T>(), nb,
                            k.img_res, k.patch);
         ARP_HIP_OK(hipGetLastError());
+        if (goal_dev) {
+            hipLaunchKernelGGL((patchify_kernel<T>), dim3((unsigned)((tot / 4 + 255) / 256)), dim3(256), 0, stream, goal_dev, w.patches.as<T>() + tot, nb,
+                               k.img_res, k.patch);
+            ARP_HIP_OK(hipGetLastError());
+        }
     }
     ARP_TRY((tower_gemm<T, float, ACT_NONE, false, 8 + SITE_PATCH>(t, "m3ae.image_embedding", w.patches.p, c->w_emb, c->b_emb, nullptr, w.pe.p,
-                                                                   nb * G * G, D, KP)));
-    {
+                                                                   (goal_dev ? 2 : 1) * nb * G * G, D, KP)));
+    if (goal_dev) {
+        ProfScope ps(c->prof, stream, "m3ae.assemble");
+        ARP_TRY(launch_assemble_gc(stream, w.pe.as<float>(), c->cls, c->pos, w.x.as<float>(), nb, G * G, D));
+    } else {
         ProfScope ps(c->prof, stream, "m3ae.assemble");
         const size_t tot = (size_t)nb * N * D;
         hipLaunchKernelGGL(enc_assemble_kernel, dim3((unsigned)((tot / 4 + 255) / 256)), dim3(256), 0, stream, w.pe.as<float>(), c->cls, c->pos,
@@ -319,9 +361,9 @@ template <typename T> int forward_chunk(arp_enc* c, arp_enc::Ws& w, hipStream_t 
 // ARP_MODE_F16X3: the same network with every GEMM as a K-concatenated (hi, lo) product on the f16 kernels and everything between the GEMMs in f32
 // (LayerNorm outputs, the exact-f32 attention kernel, the tanh-GELU'd hidden activation): 12 x (ln -> split -> in_proj -> attention -> split -> out_proj -> ln ->
 // split -> fc1 -> split -> fc2).  Three MFMAs per product plus the split passes: ~4x the plain f16 step, ~2x faster than the f32-MFMA mode, f32-level error.
-int forward_chunk_x3(arp_enc* c, arp_enc::Ws& w, hipStream_t stream, const float* img_dev, int nb, float* out_dev) {
+int forward_chunk_x3(arp_enc* c, arp_enc::Ws& w, hipStream_t stream, const float* img_dev, int nb, float* out_dev, const float* goal_dev) {
     const arp_enc_cfg& k = c->cfg;
-    const int G = k.img_res / k.patch, N = c->tokens(), D = k.width, KP = k.patch * k.patch * 3, H = k.mlp_ratio * D, M = nb * N;
+    const int G = k.img_res / k.patch, N = goal_dev ? c->gc_tokens() : c->tokens(), D = k.width, KP = k.patch * k.patch * 3, H = k.mlp_ratio * D, M = nb * N;
     TowerCtx t;
     t.stream = stream; t.prof = &c->prof; t.attn_impl = k.attn_impl; t.gemm_force = c->gemm_force; t.shared_chip = c->shared_chip;
     f16_t* a3 = w.a3.as<f16_t>();
@@ -334,9 +376,17 @@ int forward_chunk_x3(arp_enc* c, arp_enc::Ws& w, hipStream_t stream, const float
         const size_t tot = (size_t)nb * G * G * KP;
         hipLaunchKernelGGL(patchify_split3_kernel, dim3((unsigned)((tot / 4 + 255) / 256)), dim3(256), 0, stream, img_dev, a3, nb, k.img_res, k.patch);
         ARP_HIP_OK(hipGetLastError());
+        if (goal_dev) {
+            hipLaunchKernelGGL(patchify_split3_kernel, dim3((unsigned)((tot / 4 + 255) / 256)), dim3(256), 0, stream, goal_dev, a3 + 3 * tot, nb, k.img_res, k.patch);
+            ARP_HIP_OK(hipGetLastError());
+        }
     }
-    ARP_TRY((tower_gemm<f16_t, float, ACT_NONE, false, 8 + SITE_PATCH>(t, "m3ae.image_embedding", a3, c->w_emb, c->b_emb, nullptr, w.pe.p, nb * G * G, D, 3 * KP)));
-    {
+    ARP_TRY((tower_gemm<f16_t, float, ACT_NONE, false, 8 + SITE_PATCH>(t, "m3ae.image_embedding", a3, c->w_emb, c->b_emb, nullptr, w.pe.p,
+                                                                       (goal_dev ? 2 : 1) * nb * G * G, D, 3 * KP)));
+    if (goal_dev) {
+        ProfScope ps(c->prof, stream, "m3ae.assemble");
+        ARP_TRY(launch_assemble_gc(stream, w.pe.as<float>(), c->cls, c->pos, w.x.as<float>(), nb, G * G, D));
+    } else {
         ProfScope ps(c->prof, stream, "m3ae.assemble");
         const size_t tot = (size_t)nb * N * D;
         hipLaunchKernelGGL(enc_assemble_kernel, dim3((unsigned)((tot / 4 + 255) / 256)), dim3(256), 0, stream, w.pe.as<float>(), c->cls, c->pos, w.x.as<float>(), nb * N, N, D);
@@ -442,13 +492,16 @@ int forward_chunk_c(arp_enc* c, arp_enc::Ws& w, hipStream_t stream, const float*
 
 namespace arp {
 
-static int forward_part(arp_enc* c, arp_enc::Ws& w, hipStream_t stream, const float* img, int nb, float* out) {
-    ARP_TRY(ensure_ws(c, w, nb));
-    if (c->cfg.mode == ARP_MODE_F16X3) return forward_chunk_x3(c, w, stream, img, nb, out);
+// goal != null: nb (frame, goal) pairs.  A pair is 2 GG + 1 token rows and 2 GG patch rows: every workspace buffer of 2 nb plain frames holds it.
+static int forward_part(arp_enc* c, arp_enc::Ws& w, hipStream_t stream, const float* img, int nb, float* out, const float* goal = nullptr) {
+    if (goal && c->cfg.mode == ARP_MODE_F16C)
+        return fail("f16c: no goal-conditioned pass (its [hi | x4 | dx4] attention rows exist on the LDS-resident kernel only, <= 288 tokens)");
+    ARP_TRY(ensure_ws(c, w, goal ? 2 * nb : nb));
+    if (c->cfg.mode == ARP_MODE_F16X3) return forward_chunk_x3(c, w, stream, img, nb, out, goal);
     if (c->cfg.mode == ARP_MODE_F16C) return forward_chunk_c(c, w, stream, img, nb, out);
-    if (c->cfg.mode == ARP_MODE_BF16) return forward_chunk<bf16_t>(c, w, stream, img, nb, out);
-    if (c->cfg.mode == ARP_MODE_F16) return forward_chunk<f16_t>(c, w, stream, img, nb, out);
-    return forward_chunk<float>(c, w, stream, img, nb, out);
+    if (c->cfg.mode == ARP_MODE_BF16) return forward_chunk<bf16_t>(c, w, stream, img, nb, out, goal);
+    if (c->cfg.mode == ARP_MODE_F16) return forward_chunk<f16_t>(c, w, stream, img, nb, out, goal);
+    return forward_chunk<float>(c, w, stream, img, nb, out, goal);
 }
 
 // the encoder's GEMM instances (forward_chunk / forward_chunk_x3 / forward_chunk_c above), by name
@@ -483,13 +536,14 @@ int enc_op_gemm_site(const arp_gemm_site& d) {
 // Enqueues the encoder of `n` device-resident frames behind everything already on `stream`; `stream` continues behind the last part.  Safe under a
 // stream capture of `stream` (the part streams join the capture through the fork event and leave it through the join events), but every buffer must
 // exist beforehand: the first call of a geometry allocates and must run eagerly (arp_dt.hip runs two eager steps before it captures).
-int enc_forward_on(arp_enc* c, hipStream_t stream, const float* images_dev, int n, float* out_dev, bool latency) {
+// goals_dev != null: the goal-conditioned pass of n (frame, goal) pairs (enc_forward_gc_on); max_frames and the part sizes then count pairs
+static int enc_forward_any(arp_enc* c, hipStream_t stream, const float* images_dev, const float* goals_dev, int n, float* out_dev, bool latency) {
     if (!c || !c->finalized) return fail("encoder weights not finalized");
     if (n <= 0) return 0;
     const int mb = c->cfg.max_frames;
-    const size_t fi = (size_t)c->cfg.img_res * c->cfg.img_res * 3, fo = (size_t)c->tokens() * c->cfg.width;
+    const size_t fi = (size_t)c->cfg.img_res * c->cfg.img_res * 3, fo = (size_t)(goals_dev ? c->gc_tokens() : c->tokens()) * c->cfg.width;
     // the latency path: decided on the call's TOTAL rows (never per part or per chunk: a frame's bits must not depend on how a call is cut), one part
-    if (latency && (c->cfg.mode == ARP_MODE_F16 || c->cfg.mode == ARP_MODE_BF16) && n <= mb && (long)n * c->tokens() <= c->lat_rows) {
+    if (latency && !goals_dev && (c->cfg.mode == ARP_MODE_F16 || c->cfg.mode == ARP_MODE_BF16) && n <= mb && (long)n * c->tokens() <= c->lat_rows) {
         ARP_TRY(c->lat_part.ensure((size_t)4 * n * c->tokens() * c->cfg.width * 4));
         c->lat_now = true;
         const int rc = forward_part(c, c->ws[0], stream, images_dev, n, out_dev);
@@ -500,10 +554,11 @@ int enc_forward_on(arp_enc* c, hipStream_t stream, const float* images_dev, int 
         const int nb = std::min(mb, n - off);
         const float* img = images_dev + off * fi;
         float* out = out_dev + off * fo;
+        const float* goal = goals_dev ? goals_dev + off * fi : nullptr;
         int parts = std::min(c->n_parts, (int)arp_enc::MAX_PARTS);
         while (parts > 1 && nb / parts < c->min_part_frames) --parts;
         if (parts < 2) {
-            ARP_TRY(forward_part(c, c->ws[0], stream, img, nb, out));
+            ARP_TRY(forward_part(c, c->ws[0], stream, img, nb, out, goal));
             continue;
         }
         // contiguous parts: part 0 on the caller's stream, part k on its own
@@ -523,7 +578,7 @@ int enc_forward_on(arp_enc* c, hipStream_t stream, const float* images_dev, int 
         for (int i = 0; i < parts && !rc; ++i) {
             hipStream_t st = i == 0 ? stream : c->ws[i].stream;
             if (i > 0 && hipStreamWaitEvent(st, c->ev_fork, 0) != hipSuccess) rc = fail("hipStreamWaitEvent(fork) failed");
-            if (!rc) rc = forward_part(c, c->ws[i], st, img + (size_t)cut[i] * fi, cut[i + 1] - cut[i], out + (size_t)cut[i] * fo);
+            if (!rc) rc = forward_part(c, c->ws[i], st, img + (size_t)cut[i] * fi, cut[i + 1] - cut[i], out + (size_t)cut[i] * fo, goal ? goal + (size_t)cut[i] * fi : nullptr);
         }
         c->shared_chip = false;
         // join even after a failure: a part stream that entered a capture must leave it before the capture ends
@@ -533,6 +588,21 @@ int enc_forward_on(arp_enc* c, hipStream_t stream, const float* images_dev, int 
         }
         if (rc) return rc;
     }
+    return 0;
+}
+int enc_forward_on(arp_enc* c, hipStream_t stream, const float* images_dev, int n, float* out_dev, bool latency) {
+    return enc_forward_any(c, stream, images_dev, nullptr, n, out_dev, latency);
+}
+// n (frame, goal) pairs, both device-resident [n, res, res, 3] f32 -> out_dev [n, 2 GG + 1, width] f32.  Chunks of max_frames PAIRS, part streams as above, never
+// the latency path.  Stream and capture rules as enc_forward_on.
+int enc_forward_gc_on(arp_enc* c, hipStream_t stream, const float* images_dev, const float* goals_dev, int n, float* out_dev) {
+    if (!goals_dev) return fail("forward_gc: null goal frames");
+    if (c && c->cfg.mode == ARP_MODE_F16C) return fail("f16c: no goal-conditioned pass (its [hi | x4 | dx4] attention rows exist on the LDS-resident kernel only, <= 288 tokens)");
+    return enc_forward_any(c, stream, images_dev, goals_dev, n, out_dev, false);
+}
+int enc_gc_tokens(arp_enc* c, int* tokens) {
+    if (!c) return fail("null encoder");
+    *tokens = c->gc_tokens();
     return 0;
 }
 int enc_geometry(arp_enc* c, int* tokens, int* width, int* img_res, int* device) {
@@ -710,6 +780,31 @@ int arp_enc_forward(arp_enc* c, const float* images, int n, float* out) {
     }
     return 0;
 }
+
+int arp_enc_forward_gc(arp_enc* c, const float* images, const float* goals, int n, float* out) {
+    if (!c || !c->finalized) return fail("encoder weights not finalized");
+    if (n < 0) return fail("negative pair count");
+    if (n == 0) return 0;
+    if (!images || !goals || !out) return fail("null buffer");
+    if (c->cfg.mode == ARP_MODE_F16C) return fail("f16c: no goal-conditioned pass (its [hi | x4 | dx4] attention rows exist on the LDS-resident kernel only, <= 288 tokens)");
+    ARP_HIP_OK(hipSetDevice(c->cfg.device));
+    const size_t fi = (size_t)c->cfg.img_res * c->cfg.img_res * 3, fo = (size_t)c->gc_tokens() * c->cfg.width;
+    const int mb = c->cfg.max_frames;
+    if (!c->stream) ARP_TRY(c->stream.create());
+    ARP_TRY(c->img_in.ensure((size_t)2 * std::min(n, mb) * fi * 4));  // the chunk's frames, then its goals
+    ARP_TRY(c->out.ensure((size_t)std::min(n, mb) * fo * 4));
+    for (int off = 0; off < n; off += mb) {
+        const int nb = std::min(mb, n - off);
+        float* gdev = c->img_in.as<float>() + (size_t)nb * fi;
+        ARP_HIP_OK(hipMemcpyAsync(c->img_in.p, images + off * fi, nb * fi * 4, hipMemcpyHostToDevice, c->stream));
+        ARP_HIP_OK(hipMemcpyAsync(gdev, goals + off * fi, nb * fi * 4, hipMemcpyHostToDevice, c->stream));
+        ARP_TRY(enc_forward_gc_on(c, c->stream, c->img_in.as<float>(), gdev, nb, c->out.as<float>()));
+        ARP_HIP_OK(hipMemcpyAsync(out + off * fo, c->out.p, nb * fo * 4, hipMemcpyDeviceToHost, c->stream));
+        ARP_HIP_OK(hipStreamSynchronize(c->stream));
+    }
+    return 0;
+}
+int arp_enc_gc_tokens(arp_enc* c) { return c ? c->gc_tokens() : fail("null handle"); }
 
 // Part streams of a call (see arp_enc::Ws).  n_streams 1 = everything on the caller's stream (rounds 1-5); first_part_frames > 0: that many frames in part 0 of two, 0: the default cut (15/32), < 0: equal parts;
 // min_part_frames <= 0 keeps the default (a part of fewer frames runs with fewer parts).  Takes effect from the next call.

@@ -171,6 +171,7 @@ static int rollout_create(arp_dt* policy, arp_enc* encoder, arp_clip* reward, ar
     if (!(scale != 0.f)) return fail("rollout: scale must not be zero");
     auto s = std::make_unique<arp_rollout>();
     ARP_TRY(dt_rollout_info(policy, &s->pi));
+    if (s->pi.gcbc) return fail("rollout: model GCBC needs a goal frame per episode, which a session does not carry");
     // Model BC refuses arp_dt_attach_encoder (its reference encoder reads the instruction's text tokens too): the session is then LENT an encoder for its own
     // passes (arp_rollout_create_with_encoder); the handle's refusal stands.  BC.encode reads no return-to-go: no ring, no reward source.
     if (encoder) s->pi.enc = encoder;

@@ -7,7 +7,7 @@ struct arp_dt;
 struct arp_enc;
 namespace arp {
 struct DtRolloutInfo {
-    int window, enc_tokens, enc_dim, n_actions, device, bc;
+    int window, enc_tokens, enc_dim, n_actions, device, bc, gcbc;
     arp_enc* enc;         // the attached frozen encoder, or null
     hipStream_t stream;   // the handle's compute stream: everything the session enqueues for the policy goes here
 };

@@ -10,6 +10,10 @@ namespace arp {
 // 16-bit modes then runs on tower.h's latency path.  The training paths leave it false and keep their kernels at every size.
 int enc_forward_on(arp_enc* e, hipStream_t stream, const float* images_dev, int n, float* out_dev, bool latency = false);
 int enc_geometry(arp_enc* e, int* tokens, int* width, int* img_res, int* device);
+// The goal-conditioned pass: n (frame, goal) pairs, both f32 NHWC [n, res, res, 3] in HBM -> out_dev f32 [n * (2 P + 1), width], P = (res / patch)^2: per pair the
+// class token, the frame's patches, the goal frame's patches.  max_frames counts pairs here; part streams as in enc_forward_on; never the latency path.
+int enc_forward_gc_on(arp_enc* e, hipStream_t stream, const float* images_dev, const float* goals_dev, int n, float* out_dev);
+int enc_gc_tokens(arp_enc* e, int* tokens);  // 2 P + 1
 // arp_op_gemm_site's "m3ae.*" instances (the encoder's own, in this unit)
 int enc_op_gemm_site(const arp_gemm_site& d);
 }  // namespace arp

@@ -5,6 +5,7 @@
 #include <vector>
 
 #include "attention.h"
+#include "attention_long.h"
 #include "common.h"
 #include "gemm.h"
 #include "gemm256.h"
@@ -257,6 +258,9 @@ static int tower_layernorm(TowerCtx& c, const char* site, const float* in, size_
     return 0;
 }
 
+// the key-blocked kernels (attention_long.h) take this sequence length: head_dim 64, past the LDS-resident instances, up to 1024 keys
+static inline bool attn_long_has(int N, int hd) { return hd == 64 && N >= ATTN_LONG_MIN && N <= ATTN_LONG_MAX; }
+
 template <typename T>
 static int launch_attention(hipStream_t stream, int impl, const T* qkv, T* out, int B, int N, int D, int heads, int causal, int nq = 0, float out8 = 0.f,
                             f16_t* out3 = nullptr, int outc = 0) {  // out3 (T = float, the f32-MFMA kernel only): (hi, lo, hi) binary16 rows instead of f32
@@ -288,6 +292,17 @@ static int launch_attention(hipStream_t stream, int impl, const T* qkv, T* out, 
                 default: break;  // fall through to the VALU kernel
             }
 #undef ARP_ATTN_CASE
+            // past 288 keys: the key-blocked kernel (attention_long.h), plain output only -- the other forms take the refusals below.  The query tiles (64 rows)
+            // are dealt over gridDim.y when B * heads alone would leave most of the chip idle (one goal pair: 12 workgroups), as qsplit_ above does.
+            if (attn_long_has(N, hd) && out8 == 0.f && !outc) {
+                auto kern = attn_long_kernel<T>;
+                ARP_HIP_OK(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, ATTN_LONG_LDS));
+                const int ntiles = ((nq + 15) / 16 + 3) / 4;
+                const int qsplit = B * heads < 128 ? ntiles : 1;
+                hipLaunchKernelGGL(kern, dim3(B * heads, qsplit), dim3(256), ATTN_LONG_LDS, stream, qkv, out, N, D, heads, scale, causal, nq);
+                ARP_HIP_OK(hipGetLastError());
+                return 0;
+            }
         }
     }
     if (out8 != 0.f || outc) return fail("attention: the e4m3 / [hi | x4 | dx4] outputs exist on the MFMA kernel only");
@@ -333,6 +348,15 @@ static int launch_attention(hipStream_t stream, int impl, const T* qkv, T* out, 
             ARP_ATTN32_CASE(17)
             ARP_ATTN32_CASE(18)
 #undef ARP_ATTN32_CASE
+        }
+        // past 288 keys: the key-blocked exact-f32 kernel (attention_long.h), f32 rows only
+        if (impl == 0 && attn_long_has(N, hd) && (D & 3) == 0 && !out3) {
+            auto kern = attn_long_f32_kernel<ATTN_LONG_F32_Q>;
+            ARP_HIP_OK(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, ATTN_LONG_F32_LDS));
+            hipLaunchKernelGGL(kern, dim3(B * heads, (nq + ATTN_LONG_F32_Q - 1) / ATTN_LONG_F32_Q), dim3(ATTN_LONG_F32_Q), ATTN_LONG_F32_LDS, stream, qkv, out, N, D,
+                               heads, scale, causal, nq);
+            ARP_HIP_OK(hipGetLastError());
+            return 0;
         }
     }
     if (out3) return fail("attention: the (hi, lo, hi) output exists on the f32-MFMA kernel only (head_dim 64, <= 288 tokens)");

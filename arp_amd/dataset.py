@@ -71,7 +71,9 @@ class ProcgenDataset:
     """The reference class's deterministic core over an :class:`arp_amd.h5store.H5Store`, a path to one, or a plain dict of arrays."""
 
     def __init__(self, store_or_path, window_size, image_key="ob", vl_type="clip", *, env_name=None, use_vl=True, use_normalize=False,
-                 start_index=0, max_length=int(1e9), num_subset=-1, split="train", num_frames=None, reward_key=None):
+                 start_index=0, max_length=int(1e9), num_subset=-1, split="train", num_frames=None, reward_key=None, goal_rng=None):
+        # goal_rng: a numpy.random.RandomState -> items carry the hindsight goal of data_procgen.py:186-189 under "goal" (GCBC's batch dict)
+        self.goal_rng = goal_rng
         self._own = False
         if isinstance(store_or_path, (str, os.PathLike)):
             from . import h5store
@@ -187,6 +189,17 @@ class ProcgenDataset:
             return out
         return np.stack([np.asarray(ob[int(j)][-1]) for j in rows])
 
+    # -- data_procgen.py:186-189 ---------------------------------------------------------------------------------------------------
+    def goal_row(self, i):
+        """The hindsight goal of (processed) row i: one draw of ``goal_rng.choice`` over the rows from i to the end of i's trajectory -- the reference's own
+        call, so a RandomState seeded like its global generator gives its sequence -- clamped to the last row.  The goal frames are that row's window."""
+        if self.goal_rng is None:
+            raise ValueError("no goal_rng: construct the dataset with goal_rng=numpy.random.RandomState(seed)")
+        b = self.h5_file_traj_idx
+        t = int(self.idx_to_traj[i])
+        end = b[t + 1] if t + 1 < len(b) and b[t] <= i < b[t + 1] else self.n_rows  # (rows behind the last done flag: their unfinished trajectory)
+        return min(self.goal_rng.choice(list(range(i, end)), 1).item(), self.n_rows - 1)
+
     def _labels(self, index, j):
         res = {"image": {}, "rtg": {}}
         if self.use_vl:
@@ -199,6 +212,8 @@ class ProcgenDataset:
         j = self.window_rows(i)
         res = self._labels(i, j)
         res["image"][self.image_key] = self.last_frames(j)
+        if self.goal_rng is not None:
+            res["goal"] = {self.image_key: self.last_frames(self.window_rows(self.goal_row(i)))}
         return res
 
     def literal_item(self, index):

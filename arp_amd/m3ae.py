@@ -30,6 +30,11 @@ class EncoderConfig:
     def tokens(self):
         return (self.img_res // self.patch) ** 2 + 1
 
+    @property
+    def gc_tokens(self):
+        """tokens of one (frame, goal) pair in :meth:`M3AEEncoder.forward_gc_representations`: class token + both frames' patches"""
+        return 2 * (self.img_res // self.patch) ** 2 + 1
+
 
 def flops_per_frame(cfg):
     n, d = cfg.tokens, cfg.width
@@ -64,6 +69,18 @@ class M3AEEncoder:
             raise ValueError(f"images must be float [n, {self.cfg.img_res}, {self.cfg.img_res}, 3]")
         out = np.empty((x.shape[0], self.cfg.tokens, self.cfg.width), np.float32)
         check(lib.arp_enc_forward(self._h, _ffi.as_ptr(x, C.c_float), x.shape[0], _ffi.as_ptr(out, C.c_float)))
+        return out
+
+    def forward_gc_representations(self, images, goals):
+        """``forward_gc_representations`` (m3ae/model.py:498-525, GCBC's encoder call): float frames and goal frames ``[n, res, res, 3]`` ->
+        ``[n, gc_tokens, width]``; row 0 the class token, rows ``1..P`` the frame's patches, rows ``P+1..2P`` the goal's.  ``max_frames`` counts pairs.
+        Modes f32 / f16 / bf16 / f16x3; f16c raises."""
+        x = np.require(np.asarray(images, dtype=np.float32), requirements="C")
+        g = np.require(np.asarray(goals, dtype=np.float32), requirements="C")
+        if x.ndim != 4 or x.shape[1:] != (self.cfg.img_res, self.cfg.img_res, 3) or g.shape != x.shape:
+            raise ValueError(f"images and goals must both be float [n, {self.cfg.img_res}, {self.cfg.img_res}, 3]")
+        out = np.empty((x.shape[0], self.cfg.gc_tokens, self.cfg.width), np.float32)
+        check(lib.arp_enc_forward_gc(self._h, _ffi.as_ptr(x, C.c_float), _ffi.as_ptr(g, C.c_float), x.shape[0], _ffi.as_ptr(out, C.c_float)))
         return out
 
     def set_streams(self, n_streams=2, first_part_frames=0, min_part_frames=0):

@@ -9,7 +9,7 @@ import numpy as np
 def policy_param_shapes(cfg):
     """cfg.model "BC" (the InstructRL baseline, arp_dt/BC.py:87-100): the same tree without rtg_input and the return head."""
     E, D, H = cfg.emb, cfg.enc_dim, cfg.mlp_ratio * cfg.emb
-    bc = getattr(cfg, "model", "ARPDT") == "BC"
+    bc = getattr(cfg, "model", "ARPDT") in ("BC", "GCBC")  # GCBC.py's tree is BC.py's
     s = {}
     if cfg.use_adapter:
         for i in (0, 1):

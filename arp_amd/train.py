@@ -15,7 +15,8 @@ stands in).  ``state`` is a :class:`TrainState` wrapping the device-resident par
 step counter; like the reference's donated state it is consumed by the call and the returned one must be
 used.  ``batch`` keeps the reference's keys: ``batch["image"]`` holds, per image key, the frozen encoder
 output ``[B, T, tokens, dim]`` (the boundary of this round: BASELINE.json configs[3] feeds pre-computed
-encodings), ``batch["action"]`` int ``[B, T]``, ``batch["rtg"]`` per key ``[B, T, 1]`` (none for ``PolicyConfig(model="BC")``).
+encodings), ``batch["action"]`` int ``[B, T]``, ``batch["rtg"]`` per key ``[B, T, 1]`` (none for ``PolicyConfig(model="BC")``);
+``PolicyConfig(model="GCBC")`` with the frozen encoder attached reads ``batch["image"]`` and ``batch["goal"]`` frames and no rtg.
 All compute is in libarp_hip.so; there is no CPU fallback.
 """
 import ctypes as C
@@ -52,12 +53,22 @@ class PolicyConfig:
     b2: float = 0.999
     eps: float = 1e-8
     # main_procgen.py:406-427: "ARPDT" (use_vl=True), or "BC" -- the InstructRL baseline (use_vl=False, vl_type="BC": arp_dt/BC.py), the same transformer
-    # on two tokens per time step [image, action], no return-to-go input, no return head, the cross-entropy alone
+    # on two tokens per time step [image, action], no return-to-go input, no return head, the cross-entropy alone; or "GCBC" -- the goal-conditioned
+    # baseline (main_procgen.py:413-414, arp_dt/GCBC.py): BC's policy behind the frozen encoder's goal-conditioned call on (frame, goal) pairs
+    # (enc_tokens = EncoderConfig.gc_tokens).  Unlike BC it accepts attach_encoder, and then takes batch["image"] + batch["goal"] frames.
     model: str = "ARPDT"
 
     def __post_init__(self):
         if self.model not in _ffi.DT_MODELS:
             raise ValueError(f"PolicyConfig.model must be one of {sorted(_ffi.DT_MODELS)}, not {self.model!r}")
+        if self.model == "GCBC":
+            # forward_gc_representations emits class token + the frame's P patches + the goal's P patches, P a square patch grid (513 at 256 x 256, patch 16).
+            # The default enc_tokens (257: ARP-DT's P + 1) is not such a count: a GCBC configuration has to name its own (EncoderConfig.gc_tokens).
+            p2 = self.enc_tokens - 1
+            g = int(round((p2 // 2) ** 0.5)) if p2 > 0 else 0
+            if p2 <= 0 or p2 % 2 or g * g != p2 // 2:
+                raise ValueError(f"PolicyConfig(model='GCBC'): enc_tokens must be 2 P + 1 with P a square patch grid (EncoderConfig.gc_tokens, 513 at 256 x 256), "
+                                 f"not {self.enc_tokens}")
 
 
 def _dt_cfg(cfg, mode, device):
@@ -78,7 +89,8 @@ class PolicyTrainer:
         _ffi.require_gpu()
         self.cfg = cfg
         c = _dt_cfg(cfg, {"bf16": MODE_BF16, "f16": MODE_F16, "f32": MODE_F32}[mode], device)
-        self.bc = getattr(cfg, "model", "ARPDT") == "BC"
+        self.bc = getattr(cfg, "model", "ARPDT") in ("BC", "GCBC")  # GCBC is BC everywhere inside the step
+        self.gcbc = getattr(cfg, "model", "ARPDT") == "GCBC"
         h = C.c_void_p()
         check(lib.arp_dt_create(C.byref(c), C.byref(h)))
         self._h = h
@@ -165,9 +177,12 @@ class PolicyTrainer:
         self._B = B
 
     # -- two device-resident batch slots: the reference's prefetch_to_device(..., 2) (main_procgen.py:703) ----------------------
-    def upload_async(self, slot, enc, action, rtg=None, images=False):
+    def upload_async(self, slot, enc, action, rtg=None, images=False, goals=None):
         """Enqueue the host -> device copy of a batch into slot 0 / 1 on the handle's copy stream.  Safe to call from another
-        thread while :meth:`train_step` runs on the other slot.  The arrays must stay alive until :meth:`select` (kept here)."""
+        thread while :meth:`train_step` runs on the other slot.  The arrays must stay alive until :meth:`select` (kept here).
+        ``goals``: refused -- goal batches (model GCBC) exist in the synchronous slot only (:meth:`set_batch_images`)."""
+        if goals is not None:
+            raise _ffi.ArpError("goal batches exist in the synchronous slot only: set_batch_images(images, action, goals=goals) (no prefetch slot, no encode_ahead)")
         enc = np.require(np.asarray(enc, dtype=np.float32), requirements="C")
         action = np.require(np.asarray(action, dtype=np.int32), requirements="C")
         B, T = action.shape
@@ -198,7 +213,8 @@ class PolicyTrainer:
     def attach_encoder(self, encoder):
         """Put the frozen M3AE encoder (arp_amd.m3ae.M3AEEncoder) inside the step: the boundary then is the
         reference's own -- batch["image"] holds frames, not encodings (ARPDT.py:413-462).  Refused for model BC: the reference's InstructRL
-        encoder reads the instruction's text tokens beside the frame (BC.py:286-321), this one is image-only."""
+        encoder reads the instruction's text tokens beside the frame (BC.py:286-321), this one is image-only.  Accepted for model GCBC, whose encoder call
+        reads frames and goal frames alone (GCBC.py:462-468): ``cfg.enc_tokens`` must be the encoder's ``gc_tokens``."""
         check(lib.arp_dt_attach_encoder(self._h, encoder._h))
         self._encoder = encoder
 
@@ -237,9 +253,23 @@ class PolicyTrainer:
         self._inflight[int(slot)] = (None, None, None, len(idx))
         return not self._ds_use_enc
 
-    def set_batch_images(self, images, action, rtg):
+    def set_batch_images(self, images, action, rtg=None, goals=None):
+        """Frames ``[B, T, H, W, 3]`` in front of the attached encoder.  ``goals`` (model GCBC): the hindsight goal frames, same shape; the step then encodes
+        (frame, goal) pairs (``arp_dt_set_batch_images_goal``) and reads no return-to-go."""
         images = np.require(np.asarray(images, dtype=np.float32), requirements="C")
         action = np.require(np.asarray(action, dtype=np.int32), requirements="C")
+        if goals is not None:
+            goals = np.require(np.asarray(goals, dtype=np.float32), requirements="C")
+            B, T = action.shape
+            if images.ndim != 5 or images.shape[:2] != (B, T) or goals.shape != images.shape or T != self.cfg.window:
+                raise ValueError(f"batch shapes: images {images.shape}, goals {goals.shape}, action {action.shape}")
+            check(lib.arp_dt_set_batch_images_goal(self._h, _ffi.as_ptr(images, C.c_float), _ffi.as_ptr(goals, C.c_float), _ffi.as_ptr(action, C.c_int32), B))
+            self._B = B
+            return
+        if self.gcbc:
+            raise _ffi.ArpError("model GCBC encodes (frame, goal) pairs: set_batch_images needs goals=")
+        if rtg is None:
+            raise ValueError("rtg is None (only a goal batch of model GCBC takes no return-to-go)")
         rtg = np.require(np.asarray(rtg, dtype=np.float32), requirements="C")
         B, T = action.shape
         if images.shape[:2] != (B, T) or rtg.size != B * T or T != self.cfg.window:
@@ -264,13 +294,17 @@ class PolicyTrainer:
     def backward(self):
         check(lib.arp_dt_backward(self._h))
 
-    def _set_batch_any(self, enc, action, rtg):
+    def _set_batch_any(self, enc, action, rtg, goals=None):
         """encodings [B, T, tokens, dim], or -- with a frozen encoder attached -- normalised frames [B, T, H, W, 3] (row N1: what the rollout loop has),
-        or -- with a dataset attached -- a batch dict whose only key is ``"index"``"""
+        or -- with a dataset attached -- a batch dict whose only key is ``"index"``, or -- model GCBC -- the reference's batch dict with
+        ``"image"``, ``"goal"`` and ``"action"`` (or frames with ``goals``)"""
+        if isinstance(enc, dict) and "goal" in enc:
+            goals = _first_view(enc["goal"]) if self.gcbc else None  # (the reference's dataset puts "goal" in every batch; only GCBC reads it)
+            enc, action, rtg = _batch_arrays(enc, self.cfg.use_symlog)
         if is_index_batch(enc):
             self.set_batch_indices(enc["index"])
         elif getattr(self, "_encoder", None) is not None and np.ndim(enc) == 5 and np.shape(enc)[-1] == 3:
-            self.set_batch_images(enc, action, rtg)
+            self.set_batch_images(enc, action, rtg, goals=goals)
         else:
             self.set_batch(enc, action, rtg)
 
@@ -375,6 +409,11 @@ def symlog(x):
 def is_index_batch(batch):
     """A batch that names rows of an attached device-resident dataset: a dict whose only key is ``"index"``."""
     return isinstance(batch, dict) and set(batch) == {"index"}
+
+
+def _first_view(v):
+    """the array of a per-image-key dict (one image key here), or the array itself"""
+    return np.asarray(next(iter(v.values())) if isinstance(v, dict) else v)
 
 
 def _batch_arrays(batch, use_symlog=False):
@@ -643,6 +682,9 @@ def _stage(tr, batch, rank, world, device_axis):
         tr.set_batch_indices(part["index"])
         return None
     enc, act, rtg = _batch_arrays(part, tr.cfg.use_symlog)
+    if part.get("goal") is not None and getattr(tr, "gcbc", False):  # the reference's GCBC batch dict: image, goal, action
+        tr._set_batch_any(enc, act, None, goals=_first_view(part["goal"]))
+        return None
     tr._set_batch_any(enc, act, rtg) if hasattr(tr, "_set_batch_any") else tr.set_batch(enc, act, rtg)  # frames in with a frozen encoder attached (row N1): set_batch_images
     return None
 

@@ -190,9 +190,14 @@ typedef struct arp_dt_cfg {
                             with use_vl=False, vl_type="BC") -- two tokens per time step [image, action], the action head on the image-token rows
                             0::2, no rtg_input, no return head, no return loss.  A BC handle takes rtg == NULL (and ignores a non-NULL one), wants
                             return_pred == NULL in arp_dt_forward, reports trans_loss = return_loss = 0 (the model outputs neither:
-                            main_procgen.py:118-124,153-157 read them with output.get(..., 0.0)) and refuses arp_dt_attach_encoder. */
+                            main_procgen.py:118-124,153-157 read them with output.get(..., 0.0)) and refuses arp_dt_attach_encoder.
+                            ARP_DT_MODEL_GCBC (2): the goal-conditioned baseline, arp_dt/GCBC.py (main_procgen.py:413-414).  Its policy is BC's line for line
+                            -- same parameter tree, same step, same aux; with encodings in, a GCBC and a BC handle give the same bits -- and what it
+                            changes is the frozen encoder call: forward_gc_representations on a (frame, goal) pair (GCBC.py:462-468), which reads no
+                            text.  So a GCBC handle ACCEPTS arp_dt_attach_encoder, with enc_tokens == 2 P + 1 (arp_enc_gc_tokens) and enc_dim == width,
+                            and takes frames + goal frames through arp_dt_set_batch_images_goal. */
 } arp_dt_cfg;
-enum { ARP_DT_MODEL_ARPDT = 0, ARP_DT_MODEL_BC = 1 };
+enum { ARP_DT_MODEL_ARPDT = 0, ARP_DT_MODEL_BC = 1, ARP_DT_MODEL_GCBC = 2 };
 
 int arp_dt_create(const arp_dt_cfg* cfg, arp_dt** out);
 int arp_dt_destroy(arp_dt* h);
@@ -413,6 +418,14 @@ int arp_enc_load_weight(arp_enc* h, const char* name, const float* data, const i
 int arp_enc_finalize_weights(arp_enc* h);
 /* images f32 NHWC [n,res,res,3] (already normalised, as the training pipeline delivers them) -> f32 [n,tokens,width] */
 int arp_enc_forward(arp_enc* h, const float* images_host, int n, float* out_host);
+/* The goal-conditioned call (forward_gc_representations, arp_dt/models/m3ae/model.py:498-525; GCBC's encoder call, arp_dt/GCBC.py:462-468): n (frame, goal)
+ * pairs, both f32 NHWC [n,res,res,3] -> f32 [n, 2 P + 1, width] with P = (img_res / patch)^2.  One sequence per pair: class token, the frame's P patches, the goal
+ * frame's P patches; both patch blocks carry the same 2-D sincos position and image type embedding.  Both frame sets share one patch-embedding product; at
+ * 256 x 256 the blocks run over 513 tokens, on the key-blocked attention kernels (csrc/attention_long.h).  max_frames counts pairs in this call; part streams
+ * apply as in arp_enc_forward; the latency path is never taken.  Modes f32, f16, bf16, f16x3; ARP_MODE_F16C returns an error (its attention output form
+ * exists up to 288 tokens only).  arp_enc_gc_tokens: 2 P + 1. */
+int arp_enc_forward_gc(arp_enc* h, const float* images_host, const float* goals_host, int n, float* out_host);
+int arp_enc_gc_tokens(arp_enc* h);
 /* Part streams (round 6): a call's frames are encoded as `n_streams` contiguous parts (1..4, default 2), part 0 on the caller's stream and the others on
  * streams of their own, so that one part's memory-bound kernels and GEMM grid tails run beside another part's GEMMs -- as arp_clip_cfg.n_streams does
  * for the labelling pass.  first_part_frames > 0: that many frames in part 0 of two; 0: the default cut (15/32 of the frames: parts that end at different times
@@ -431,6 +444,12 @@ int arp_enc_profile_json(arp_enc* h, char* buf, int buf_len);
  * [B,T,res,res,3] f32 and every forward / train step runs the encoder first (on the step's stream). */
 int arp_dt_attach_encoder(arp_dt* h, arp_enc* enc);
 int arp_dt_set_batch_images(arp_dt* h, const float* images, const int32_t* action, const float* rtg, int B);
+/* Model GCBC's staging slot (synchronous, like arp_dt_set_batch_images): frames and goal frames, both [B,T,res,res,3] f32, and the actions; every forward /
+ * train step then runs the goal-conditioned encoder pass (arp_enc_forward_gc's) first.  The goal row is drawn per sample (data_procgen.py:186-189), so the
+ * encoding depends on the pair and cannot come from a per-frame cache: for this model the encoder is inside the step.  Not offered, each with an error
+ * string: goal batches in the two prefetch slots (arp_dt_upload_batch_images_async) and arp_dt_encode_ahead, a goal gather from a device-resident dataset
+ * (arp_dt_*_batch_indices with frames), a rollout session on a GCBC handle, and arp_dt_set_batch_images (no goals) on a GCBC handle. */
+int arp_dt_set_batch_images_goal(arp_dt* h, const float* images, const float* goals, const int32_t* action, int B);
 /* The encoder is frozen: batch i + 1's encodings depend on nothing step i computes.  arp_dt_encode_ahead(slot) enqueues the encoder pass of the frames in
  * batch slot `slot` (0 / 1: uploaded with arp_dt_upload_batch_images_async; 2: staged by arp_dt_set_batch_images) on the encoder's own stream NOW -- behind the
  * slot's upload and the last step that read the slot -- so that it runs beside the current step's policy part; the step that then reads the slot waits for it
