@@ -116,6 +116,7 @@ SIGNATURES = {
     "arp_clip_sync": (_i, [_vp]),
     "arp_clip_set_streams": (_i, [_vp, _i]),
     "arp_clip_encode_image": (_i, [_vp, _u8p, _i, _i, _i, _i, _i, _fp]),
+    "arp_clip_encode_image_dev_async": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _vp]),
     "arp_preprocess": (_i, [_u8p, _i, _i, _i, _i, _i, _fp]),
     "arp_bicubic_coeffs": (_i, [_i, _i, _i32p, _i32p, _i32p, _i]),
     "arp_clip_clock_probe": (_i, [_vp, _i]),
@@ -227,6 +228,8 @@ SIGNATURES = {
     "arp_rollout_create": (_i, [_vp, _vp, _i, _i, _i, _f, C.POINTER(_vp)]),
     "arp_rollout_create_with_encoder": (_i, [_vp, _vp, _vp, _i, _i, _i, _f, C.POINTER(_vp)]),
     "arp_rollout_create_ft": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _f, C.POINTER(_vp)]),
+    "arp_rollout_create_gc": (_i, [_vp, _vp, _vp, _i, _i, _i, _f, C.POINTER(_vp)]),
+    "arp_rollout_reset_goal": (_i, [_vp, _i32p, _i, _fp, _u8p]),
     "arp_rollout_destroy": (_i, [_vp]),
     "arp_rollout_reset": (_i, [_vp, _i32p, _i, _fp]),
     "arp_rollout_set_lut": (_i, [_vp, _fp]),

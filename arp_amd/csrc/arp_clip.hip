@@ -1061,6 +1061,25 @@ int arp_clip_encode_image(arp_clip* c, const uint8_t* frames, int n, int H, int 
     return 0;
 }
 
+// arp_clip_encode_image for frames that never left the device: preprocess + vision tower on the handle's stream, the features copied device to device behind
+// them.  Enqueued, not waited for (the workspace may grow on the first call of a size, which synchronises the stream as in label_dev_single).
+int arp_clip_encode_image_dev_async(arp_clip* c, const uint8_t* frames_dev, int n, int H, int W, int use_crop, int normalize, float* feats_dev) {
+    ARP_TRY(check_ready(c, false));
+    if (c->primary) return fail("a part stream's sibling is not a handle of its own");
+    if (n < 0) return fail("negative frame count");
+    if (n == 0) return 0;
+    if (!frames_dev || !feats_dev) return fail("null buffer");
+    if (n > c->cfg.max_batch) return fail("arp_clip_encode_image_dev_async: at most max_batch frames per call");
+    ARP_HIP_OK(hipSetDevice(c->cfg.device));
+    ResizePlan* plan;
+    ARP_TRY(get_plan(c, H, W, use_crop, &plan, (long)n * c->ntok() <= c->lat_rows));
+    ARP_TRY(ensure_workspace(c, n));
+    ARP_TRY(forward_chunk_dispatch(c, frames_dev, n, plan));
+    if (normalize) ARP_TRY(launch_l2_normalize(c->stream, c->feat.as<float>(), n, c->cfg.embed));
+    ARP_HIP_OK(hipMemcpyAsync(feats_dev, c->feat.p, (size_t)n * c->cfg.embed * 4, hipMemcpyDeviceToDevice, c->stream));
+    return 0;
+}
+
 // Frozen-tower outputs for the fine-tune head (row N2): per-block CLS features [n, layers*width] and the un-normalised
 // CLIP image feature [n, embed], through the fine-tune transform (bilinear; clip_multiscale_adapter.py:120-149).
 // pil_crop < 0: the fine-tune transform; 0 / 1: the LABEL transform instead (Pillow bicubic + normalise, use_crop = pil_crop) -- what the rollout

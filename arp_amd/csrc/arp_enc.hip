@@ -186,7 +186,9 @@ struct arp_enc {
     // Latency path (the rollout session's per-step pass of its E new frames): a call of at most lat_rows token rows IN TOTAL, in the plain 16-bit
     // modes, runs as ONE part on tower.h's latency path -- the W-tiled skinny GEMMs (patch embedding, in_proj, c_fc), out_proj / c_proj as split-K slabs whose
     // reduction kernel adds bias + residual and applies the next LayerNorm.  Only callers that ask for it (enc_forward_on's `latency`: the rollout session, and
-    // arp_enc_forward once arp_enc_set_latency turned lat_host on) take it; the training paths never do, whatever their row count.
+    // arp_enc_forward once arp_enc_set_latency turned lat_host on) take it; the training paths never do, whatever their row count.  A goal-conditioned call
+    // (enc_forward_gc_on, arp_enc_forward_gc) follows the same rule on pairs x (2 P + 1) rows: one real pair is 513 rows, measured 1.224 against 1.474 ms per
+    // GCBC session step with the path on / off (profiles/gc_rollout_timing.txt); two pairs are over SKINNY_MAX_M.
     // Default 514 = two frames at 257 tokens, the largest row count at which the path was measured faster inside a rollout step (ViT-B/16, f16 / bf16:
     // 257 rows 1.10 against 1.56 ms per step, 514 rows 1.39 against 1.69, 771 rows 1.80 against 1.69 -- slower; profiles/rollout_step_timing.txt).
     int lat_rows = 514;  // arp_enc_set_latency / ARP_ENC_LAT_ROWS (up to SKINNY_MAX_M); 0 = the throughput kernels at every size
@@ -543,10 +545,12 @@ static int enc_forward_any(arp_enc* c, hipStream_t stream, const float* images_d
     const int mb = c->cfg.max_frames;
     const size_t fi = (size_t)c->cfg.img_res * c->cfg.img_res * 3, fo = (size_t)(goals_dev ? c->gc_tokens() : c->tokens()) * c->cfg.width;
     // the latency path: decided on the call's TOTAL rows (never per part or per chunk: a frame's bits must not depend on how a call is cut), one part
-    if (latency && !goals_dev && (c->cfg.mode == ARP_MODE_F16 || c->cfg.mode == ARP_MODE_BF16) && n <= mb && (long)n * c->tokens() <= c->lat_rows) {
-        ARP_TRY(c->lat_part.ensure((size_t)4 * n * c->tokens() * c->cfg.width * 4));
+    // (a goal-conditioned call counts its pairs' rows, 2 P + 1 each: one real pair is 513 rows, two pairs are over SKINNY_MAX_M)
+    const long rows = (long)n * (goals_dev ? c->gc_tokens() : c->tokens());
+    if (latency && (c->cfg.mode == ARP_MODE_F16 || c->cfg.mode == ARP_MODE_BF16) && n <= mb && rows <= c->lat_rows) {
+        ARP_TRY(c->lat_part.ensure((size_t)4 * rows * c->cfg.width * 4));
         c->lat_now = true;
-        const int rc = forward_part(c, c->ws[0], stream, images_dev, n, out_dev);
+        const int rc = forward_part(c, c->ws[0], stream, images_dev, n, out_dev, goals_dev);
         c->lat_now = false;
         return rc;
     }
@@ -593,12 +597,12 @@ static int enc_forward_any(arp_enc* c, hipStream_t stream, const float* images_d
 int enc_forward_on(arp_enc* c, hipStream_t stream, const float* images_dev, int n, float* out_dev, bool latency) {
     return enc_forward_any(c, stream, images_dev, nullptr, n, out_dev, latency);
 }
-// n (frame, goal) pairs, both device-resident [n, res, res, 3] f32 -> out_dev [n, 2 GG + 1, width] f32.  Chunks of max_frames PAIRS, part streams as above, never
-// the latency path.  Stream and capture rules as enc_forward_on.
-int enc_forward_gc_on(arp_enc* c, hipStream_t stream, const float* images_dev, const float* goals_dev, int n, float* out_dev) {
+// n (frame, goal) pairs, both device-resident [n, res, res, 3] f32 -> out_dev [n, 2 GG + 1, width] f32.  Chunks of max_frames PAIRS, part streams as above;
+// latency as in enc_forward_on, on the pairs' rows.  Stream and capture rules as enc_forward_on.
+int enc_forward_gc_on(arp_enc* c, hipStream_t stream, const float* images_dev, const float* goals_dev, int n, float* out_dev, bool latency) {
     if (!goals_dev) return fail("forward_gc: null goal frames");
     if (c && c->cfg.mode == ARP_MODE_F16C) return fail("f16c: no goal-conditioned pass (its [hi | x4 | dx4] attention rows exist on the LDS-resident kernel only, <= 288 tokens)");
-    return enc_forward_any(c, stream, images_dev, goals_dev, n, out_dev, false);
+    return enc_forward_any(c, stream, images_dev, goals_dev, n, out_dev, latency);
 }
 int enc_gc_tokens(arp_enc* c, int* tokens) {
     if (!c) return fail("null encoder");
@@ -798,7 +802,7 @@ int arp_enc_forward_gc(arp_enc* c, const float* images, const float* goals, int 
         float* gdev = c->img_in.as<float>() + (size_t)nb * fi;
         ARP_HIP_OK(hipMemcpyAsync(c->img_in.p, images + off * fi, nb * fi * 4, hipMemcpyHostToDevice, c->stream));
         ARP_HIP_OK(hipMemcpyAsync(gdev, goals + off * fi, nb * fi * 4, hipMemcpyHostToDevice, c->stream));
-        ARP_TRY(enc_forward_gc_on(c, c->stream, c->img_in.as<float>(), gdev, nb, c->out.as<float>()));
+        ARP_TRY(enc_forward_gc_on(c, c->stream, c->img_in.as<float>(), gdev, nb, c->out.as<float>(), c->lat_host && n <= mb));
         ARP_HIP_OK(hipMemcpyAsync(out + off * fo, c->out.p, nb * fo * 4, hipMemcpyDeviceToHost, c->stream));
         ARP_HIP_OK(hipStreamSynchronize(c->stream));
     }

@@ -8,6 +8,11 @@
 // The reward pass (arp_clip_label_dev_async on the device copy of the same uint8 frames) runs on the CLIP handle's stream beside all that; a kernel
 // behind it takes the reward off the return-to-go.  The two streams are ordered by events only (ev_up: frames landed; ev_win: this step's window
 // kernel has read the return-to-go; ev_rtg: the return-to-go is updated and the frames are free): the host waits once, for the actions.
+//
+// A session made by arp_rollout_create_gc also holds one GOAL frame per environment (the reference fixes it per episode, :94, and re-attaches it to every
+// observation, :108,130).  Model GCBC: the encoder pass above becomes the goal-conditioned one on the E new (frame, goal) pairs, everything else is the BC step.
+// An ARP-DT policy with a plain labelling handle: the reward pass becomes the features of the E new frames and a kernel that writes -||f - g||_2 against the
+// goals' features, which were computed at arp_rollout_reset_goal (clip_goal_conditioned, envs/vl_reward.py:26-41).
 #include <algorithm>
 #include <cstring>
 #include <memory>
@@ -112,6 +117,23 @@ __global__ __launch_bounds__(64) void rollout_rtg_kernel(float* __restrict__ rtg
     if (e < E) rtg[e] -= (reward[e] - sub) / scale;
 }
 
+// The goal reward (get_torch_clip_goal_conditioned_reward, envs/vl_reward.py:26-41): reward[e] = -|| f[e] - g[e] ||_2 on un-normalised image features.  One wave
+// per environment, f32; lane l sums elements l, l + 64, ... in index order and the lanes are folded by a fixed xor butterfly, so a value depends on its two rows
+// and on nothing else (not on E, not on the other environments).
+__global__ __launch_bounds__(64) void rollout_goal_reward_kernel(const float* __restrict__ f, const float* __restrict__ g, int D, float* __restrict__ reward) {
+    const int e = blockIdx.x, lane = threadIdx.x;
+    const float* fr = f + (size_t)e * D;
+    const float* gr = g + (size_t)e * D;
+    float acc = 0.f;
+    for (int i = lane; i < D; i += 64) {
+        const float d = fr[i] - gr[i];
+        acc += d * d;
+    }
+#pragma unroll
+    for (int o = 32; o >= 1; o >>= 1) acc += __shfl_xor(acc, o, 64);
+    if (lane == 0) reward[e] = -sqrtf(acc);
+}
+
 // reset of the listed environments: return-to-go, episode length
 __global__ __launch_bounds__(64) void rollout_reset_kernel(const int32_t* __restrict__ ids, const float* __restrict__ rtg0, int n, float* rtg, int32_t* len) {
     const int i = blockIdx.x * 64 + threadIdx.x;
@@ -144,6 +166,13 @@ struct arp_rollout {
     int head = 0;  // the ring slot the NEXT step writes
     float tail = 0.f;
     int32_t tail_action = 0;
+    // A session made by arp_rollout_create_gc carries one goal frame per environment: uint8 as it came; for a GCBC policy also f32 through the byte -> float table
+    // (the encoder's second input); for an ARP-DT policy with a labelling handle the goals' un-normalised CLIP image features (the goal reward).
+    bool gc = false;
+    int embed = 0;                  // the reward handle's feature width (goal reward)
+    DevBuf goals_u8, goal32, goal_feat, frame_feat;
+    std::vector<char> has_goal;     // [E]
+    bool goal_reward() const { return gc && clip; }
     const float* logits = nullptr;  // the policy's logits buffer as of the last step
     float* slot_enc = nullptr;
     int32_t* slot_action = nullptr;
@@ -165,13 +194,17 @@ int quiesce(arp_rollout* s) {
 
 extern "C" {
 
-static int rollout_create(arp_dt* policy, arp_enc* encoder, arp_clip* reward, arp_ft* head, int n_envs, int H, int W, float scale, arp_rollout** out) {
+static int rollout_create(arp_dt* policy, arp_enc* encoder, arp_clip* reward, arp_ft* head, int n_envs, int H, int W, float scale, arp_rollout** out,
+                          bool gc = false) {
     if (!policy || !out) return fail("null argument");
     if (n_envs <= 0) return fail("rollout: n_envs must be positive");
     if (!(scale != 0.f)) return fail("rollout: scale must not be zero");
     auto s = std::make_unique<arp_rollout>();
     ARP_TRY(dt_rollout_info(policy, &s->pi));
-    if (s->pi.gcbc) return fail("rollout: model GCBC needs a goal frame per episode, which a session does not carry");
+    if (s->pi.gcbc && !gc) return fail("rollout: model GCBC needs a goal frame per episode, which a session does not carry");
+    if (gc && head) return fail("rollout: create_gc takes a plain labelling handle: the fine-tuned goal reward stays with the host function");
+    if (gc && s->pi.bc && !s->pi.gcbc) return fail("rollout: create_gc: model BC reads no goal frame (model GCBC does)");
+    if (gc && !s->pi.bc && !reward) return fail("rollout: create_gc: an ARP-DT policy carries goal frames for the goal reward only: pass a labelling handle");
     // Model BC refuses arp_dt_attach_encoder (its reference encoder reads the instruction's text tokens too): the session is then LENT an encoder for its own
     // passes (arp_rollout_create_with_encoder); the handle's refusal stands.  BC.encode reads no return-to-go: no ring, no reward source.
     if (encoder) s->pi.enc = encoder;
@@ -181,6 +214,7 @@ static int rollout_create(arp_dt* policy, arp_enc* encoder, arp_clip* reward, ar
     if (s->pi.bc && reward) return fail("rollout: model BC reads no return-to-go: a reward handle is refused");
     int tokens = 0, width = 0, res = 0, dev = 0;
     ARP_TRY(enc_geometry(s->pi.enc, &tokens, &width, &res, &dev));
+    if (s->pi.gcbc) ARP_TRY(enc_gc_tokens(s->pi.enc, &tokens));  // a (frame, goal) pair per ring entry
     if (H != res || W != res) return fail("rollout: frames are " + std::to_string(H) + " x " + std::to_string(W) + ", the attached encoder reads " + std::to_string(res) + " x " + std::to_string(res));
     if (tokens != s->pi.enc_tokens || width != s->pi.enc_dim) return fail("rollout: encoder geometry does not match the policy's enc_tokens / enc_dim");
     if (dev != s->pi.device) return fail("rollout: the encoder lives on another device");
@@ -191,6 +225,13 @@ static int rollout_create(arp_dt* policy, arp_enc* encoder, arp_clip* reward, ar
         ARP_TRY(clip_ms_info(reward, &ci));
         if (ci.device != s->pi.device) return fail("rollout: the reward handles live on another device");
         s->clip_stream = ci.stream;
+    } else if (reward && gc) {  // the goal reward reads image features only: no prompt set is asked for
+        ClipMsInfo ci;
+        ARP_TRY(clip_ms_info(reward, &ci));
+        if (ci.device != s->pi.device) return fail("rollout: the reward handle lives on another device");
+        if (n_envs > ci.max_batch) return fail("rollout: the goal reward encodes n_envs frames per call: n_envs exceeds the reward handle's max_batch");
+        s->clip_stream = ci.stream;
+        s->embed = ci.embed;
     } else if (reward) {
         int cdev = 0;
         ARP_TRY(clip_stream_of(reward, &s->clip_stream, &cdev));
@@ -198,7 +239,7 @@ static int rollout_create(arp_dt* policy, arp_enc* encoder, arp_clip* reward, ar
     }
     ARP_HIP_OK(hipSetDevice(s->pi.device));
     s->dt = policy; s->clip = reward; s->ft = head; s->enc = s->pi.enc;
-    s->E = n_envs; s->H = H; s->W = W; s->scale = scale;
+    s->E = n_envs; s->H = H; s->W = W; s->scale = scale; s->gc = gc;
     s->F = (size_t)tokens * width;
     const size_t E = n_envs, T = s->pi.window, fb = (size_t)H * W * 3;
     ARP_TRY(s->frames_u8.ensure(E * fb)); ARP_TRY(s->enc_in.ensure(E * fb * 4));
@@ -207,8 +248,14 @@ static int rollout_create(arp_dt* policy, arp_enc* encoder, arp_clip* reward, ar
     ARP_TRY(s->rtg_cur.ensure(E * 4)); ARP_TRY(s->len.ensure(E * 4)); ARP_TRY(s->reward.ensure(E * 4)); ARP_TRY(s->actions.ensure(E * 4));
     ARP_TRY(s->lut.ensure(3 * 256 * 4)); ARP_TRY(s->reset_ids.ensure(E * 4)); ARP_TRY(s->reset_rtg.ensure(E * 4));
     ARP_TRY(s->pin_frames.ensure(E * fb)); ARP_TRY(s->pin_small.ensure(4 * E * 4));
+    if (gc) {
+        s->has_goal.assign(E, 0);
+        ARP_TRY(s->goals_u8.ensure(E * fb));
+        if (s->pi.gcbc) ARP_TRY(s->goal32.ensure(E * fb * 4));
+        if (reward) { ARP_TRY(s->goal_feat.ensure(E * s->embed * 4)); ARP_TRY(s->frame_feat.ensure(E * s->embed * 4)); }
+    }
     ARP_TRY(s->ev_up.create()); ARP_TRY(s->ev_win.create()); ARP_TRY(s->ev_rtg.create());
-    for (DevBuf* b : {&s->ring, &s->act_ring, &s->rtg_ring, &s->rtg_cur, &s->len, &s->reward, &s->actions})
+    for (DevBuf* b : {&s->ring, &s->act_ring, &s->rtg_ring, &s->rtg_cur, &s->len, &s->reward, &s->actions, &s->goals_u8, &s->goal32, &s->goal_feat, &s->frame_feat})
         if (b->p) ARP_HIP_OK(hipMemset(b->p, 0, b->bytes));
     *out = s.release();
     return 0;
@@ -226,10 +273,29 @@ int arp_rollout_create_ft(arp_dt* policy, arp_enc* encoder_or_null, arp_clip* to
     return rollout_create(policy, encoder_or_null, towers, head, n_envs, H, W, scale, out);
 }
 
+int arp_rollout_create_gc(arp_dt* policy, arp_enc* encoder_or_null, arp_clip* reward_or_null, int n_envs, int H, int W, float scale, arp_rollout** out) {
+    return rollout_create(policy, encoder_or_null, reward_or_null, nullptr, n_envs, H, W, scale, out, true);
+}
+
 int arp_rollout_destroy(arp_rollout* s) {
     if (!s) return 0;
     (void)quiesce(s);
     delete s;
+    return 0;
+}
+
+// uint8 -> f32 through the session's table, `frames` frames on the policy's stream
+static int launch_ingest(arp_rollout* s, const uint8_t* src, float* dst, size_t frames) {
+    const size_t n4 = frames * s->H * s->W / 4;
+    hipLaunchKernelGGL(rollout_ingest_kernel, dim3((unsigned)std::min<size_t>((n4 + 255) / 256, 2048)), dim3(256), 0, s->pi.stream, src, s->lut.as<float>(), dst, n4);
+    ARP_HIP_OK(hipGetLastError());
+    return 0;
+}
+// a GCBC session's goals as the encoder reads them: all E at once (an environment without a goal yet holds zeros, and no step runs before it has one)
+static int ingest_goals(arp_rollout* s) {
+    if (!s->gc || !s->pi.gcbc || !s->has_lut) return 0;
+    ARP_TRY(launch_ingest(s, s->goals_u8.as<uint8_t>(), s->goal32.as<float>(), (size_t)s->E));
+    ARP_HIP_OK(hipStreamSynchronize(s->pi.stream));
     return 0;
 }
 
@@ -238,7 +304,7 @@ int arp_rollout_set_lut(arp_rollout* s, const float* lut768) {
     ARP_TRY(quiesce(s));
     ARP_HIP_OK(hipMemcpy(s->lut.p, lut768, 3 * 256 * 4, hipMemcpyHostToDevice));
     s->has_lut = true;
-    return 0;
+    return ingest_goals(s);  // (a GCBC session's f32 goals are table values: a new table, new goals)
 }
 
 int arp_rollout_set_reward_norm(arp_rollout* s, int use_normalize, float reward_min) {
@@ -259,8 +325,18 @@ int arp_rollout_debug_set_tail(arp_rollout* s, float value, int action) {
     return 0;
 }
 
+static int rollout_reset(arp_rollout* s, const int32_t* env_ids, int n, const float* rtg0, const uint8_t* goals_u8);
 int arp_rollout_reset(arp_rollout* s, const int32_t* env_ids, int n, const float* rtg0) {
     if (!s || !env_ids || !rtg0) return fail("null argument");
+    return rollout_reset(s, env_ids, n, rtg0, nullptr);
+}
+int arp_rollout_reset_goal(arp_rollout* s, const int32_t* env_ids, int n, const float* rtg0, const uint8_t* goals_u8) {
+    if (!s || !env_ids || !goals_u8) return fail("null argument");
+    if (!s->gc) return fail("rollout: reset_goal needs a session that carries goal frames (arp_rollout_create_gc)");
+    if (!rtg0 && !s->pi.bc) return fail("rollout: reset_goal: the first return-to-go is required (only model GCBC reads none)");
+    return rollout_reset(s, env_ids, n, rtg0, goals_u8);
+}
+static int rollout_reset(arp_rollout* s, const int32_t* env_ids, int n, const float* rtg0, const uint8_t* goals_u8) {
     if (n <= 0 || n > s->E) return fail("rollout: reset names 1 .. n_envs environments");
     for (int i = 0; i < n; ++i) {
         if (env_ids[i] < 0 || env_ids[i] >= s->E) return fail("rollout: env_id " + std::to_string(env_ids[i]) + " out of range [0, " + std::to_string(s->E) + ")");
@@ -269,12 +345,27 @@ int arp_rollout_reset(arp_rollout* s, const int32_t* env_ids, int n, const float
     }
     ARP_TRY(quiesce(s));  // (a reset is rare: behind everything in flight, the return-to-go kernel of the last step included)
     ARP_HIP_OK(hipMemcpy(s->reset_ids.p, env_ids, (size_t)n * 4, hipMemcpyHostToDevice));
-    ARP_HIP_OK(hipMemcpy(s->reset_rtg.p, rtg0, (size_t)n * 4, hipMemcpyHostToDevice));
+    if (rtg0) ARP_HIP_OK(hipMemcpy(s->reset_rtg.p, rtg0, (size_t)n * 4, hipMemcpyHostToDevice));
+    else ARP_HIP_OK(hipMemset(s->reset_rtg.p, 0, (size_t)n * 4));
     hipLaunchKernelGGL(rollout_reset_kernel, dim3((n + 63) / 64), dim3(64), 0, s->pi.stream, s->reset_ids.as<int32_t>(), s->reset_rtg.as<float>(), n,
                        s->rtg_cur.as<float>(), s->len.as<int32_t>());
     ARP_HIP_OK(hipGetLastError());
     ARP_HIP_OK(hipStreamSynchronize(s->pi.stream));
     s->any_reset = true;
+    if (goals_u8) {  // the listed environments' goals, then everything derived from them (both streams are idle: quiesce above)
+        const size_t fb = (size_t)s->H * s->W * 3;
+        for (int i = 0; i < n; ++i) {
+            ARP_HIP_OK(hipMemcpy(s->goals_u8.as<uint8_t>() + (size_t)env_ids[i] * fb, goals_u8 + (size_t)i * fb, fb, hipMemcpyHostToDevice));
+            s->has_goal[env_ids[i]] = 1;
+        }
+        ARP_TRY(ingest_goals(s));
+        if (s->goal_reward()) {
+            // All E goals in ONE call, as a step encodes its E frames in one call (the towers choose their kernels by the call's rows); an environment
+            // whose goal did not change gets the bits it had.  Label transform, no crop, un-normalised.
+            ARP_TRY(arp_clip_encode_image_dev_async(s->clip, s->goals_u8.as<uint8_t>(), s->E, s->H, s->W, 0, 0, s->goal_feat.as<float>()));
+            ARP_HIP_OK(hipStreamSynchronize(s->clip_stream));
+        }
+    }
     return 0;
 }
 
@@ -297,6 +388,11 @@ static int rollout_step(arp_rollout* s, const uint8_t* frames_host, const float*
     if (!s->has_lut) return fail("rollout: no byte -> float table (arp_rollout_set_lut)");
     if (rewards && s->clip) return fail("rollout: rewards were passed to a session that owns a reward handle");
     if (rewards && s->pi.bc) return fail("rollout: model BC reads no return-to-go: rewards are refused");
+    if (s->gc) {
+        for (int e = 0; e < s->E; ++e)
+            if (!s->has_goal[e]) return fail("rollout: environment " + std::to_string(e) + " has no goal frame yet (arp_rollout_reset_goal)");
+        if (s->clip && use_crop) return fail("rollout: use_crop with the device goal reward is refused (the reference crops the goal's crop again: that stays with the host function)");
+    }
     ARP_HIP_OK(hipSetDevice(s->pi.device));
     const int E = s->E, T = s->pi.window, NA = s->pi.n_actions;
     const size_t fb = (size_t)s->H * s->W * 3;
@@ -321,18 +417,20 @@ static int rollout_step(arp_rollout* s, const uint8_t* frames_host, const float*
     if (s->clip) {  // 7. the reward pass, beside steps 2-6 on the labelling handle's own stream
         ARP_HIP_OK(hipEventRecord(s->ev_up, S));
         ARP_HIP_OK(hipStreamWaitEvent(s->clip_stream, s->ev_up, 0));
-        if (s->ft) ARP_TRY(arp_ft_reward_dev_async(s->ft, s->clip, s->frames_u8.as<uint8_t>(), E, s->H, s->W, use_crop, 1 /* label transform */, s->reward.as<float>()));
+        if (s->gc) {
+            ARP_TRY(arp_clip_encode_image_dev_async(s->clip, s->frames_u8.as<uint8_t>(), E, s->H, s->W, 0, 0, s->frame_feat.as<float>()));
+            hipLaunchKernelGGL(rollout_goal_reward_kernel, dim3(E), dim3(64), 0, s->clip_stream, s->frame_feat.as<float>(), s->goal_feat.as<float>(), s->embed,
+                               s->reward.as<float>());
+            ARP_HIP_OK(hipGetLastError());
+        } else if (s->ft) ARP_TRY(arp_ft_reward_dev_async(s->ft, s->clip, s->frames_u8.as<uint8_t>(), E, s->H, s->W, use_crop, 1 /* label transform */, s->reward.as<float>()));
         else ARP_TRY(arp_clip_label_dev_async(s->clip, s->frames_u8.as<uint8_t>(), E, s->H, s->W, use_crop, s->reward.as<float>()));
     }
     // 2. ingest
-    {
-        const size_t n4 = (size_t)E * s->H * s->W / 4;
-        hipLaunchKernelGGL(rollout_ingest_kernel, dim3((unsigned)std::min<size_t>((n4 + 255) / 256, 2048)), dim3(256), 0, S, s->frames_u8.as<uint8_t>(),
-                           s->lut.as<float>(), s->enc_in.as<float>(), n4);
-        ARP_HIP_OK(hipGetLastError());
-    }
-    // 3. the encoder on the E new frames, straight into ring slot `head`
-    ARP_TRY(enc_forward_on(s->enc, S, s->enc_in.as<float>(), E, s->ring.as<float>() + (size_t)s->head * E * s->F, true));
+    ARP_TRY(launch_ingest(s, s->frames_u8.as<uint8_t>(), s->enc_in.as<float>(), (size_t)E));
+    // 3. the encoder on the E new frames (model GCBC: on the E new (frame, goal) pairs), straight into ring slot `head`
+    float* slot = s->ring.as<float>() + (size_t)s->head * E * s->F;
+    if (s->pi.gcbc) ARP_TRY(enc_forward_gc_on(s->enc, S, s->enc_in.as<float>(), s->goal32.as<float>(), E, slot, true));
+    else ARP_TRY(enc_forward_on(s->enc, S, s->enc_in.as<float>(), E, slot, true));
     // 4. window
     {
         WindowArgs a;
@@ -387,6 +485,14 @@ int arp_rollout_read(arp_rollout* s, const char* what, void* out, int64_t bytes)
     else if (w == "reward") { src = s->reward.p; n = E * 4; }
     else if (w == "logits") { src = s->logits; n = E * T * s->pi.n_actions * 4; }
     else if (w == "enc_ring") { src = s->ring.p; n = T * E * s->F * 4; }
+    else if (w == "goal") {
+        if (!s->gc) return fail("rollout read: goal exists on a session that carries goal frames (arp_rollout_create_gc)");
+        src = s->goals_u8.p; n = E * s->H * s->W * 3;
+    }
+    else if (w == "goal_feat") {
+        if (!s->goal_reward()) return fail("rollout read: goal_feat exists on a session with the device goal reward");
+        src = s->goal_feat.p; n = E * s->embed * 4;
+    }
     else if (w == "head") {
         if (bytes != 4) return fail("rollout read: head is one int32");
         *static_cast<int32_t*>(out) = s->head;

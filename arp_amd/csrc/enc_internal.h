@@ -11,8 +11,9 @@ namespace arp {
 int enc_forward_on(arp_enc* e, hipStream_t stream, const float* images_dev, int n, float* out_dev, bool latency = false);
 int enc_geometry(arp_enc* e, int* tokens, int* width, int* img_res, int* device);
 // The goal-conditioned pass: n (frame, goal) pairs, both f32 NHWC [n, res, res, 3] in HBM -> out_dev f32 [n * (2 P + 1), width], P = (res / patch)^2: per pair the
-// class token, the frame's patches, the goal frame's patches.  max_frames counts pairs here; part streams as in enc_forward_on; never the latency path.
-int enc_forward_gc_on(arp_enc* e, hipStream_t stream, const float* images_dev, const float* goals_dev, int n, float* out_dev);
+// class token, the frame's patches, the goal frame's patches.  max_frames counts pairs here; part streams as in enc_forward_on; latency: as there, counted on
+// the call's n * (2 P + 1) rows (the rollout session's pass of its E new pairs; the GCBC train step leaves it false).
+int enc_forward_gc_on(arp_enc* e, hipStream_t stream, const float* images_dev, const float* goals_dev, int n, float* out_dev, bool latency = false);
 int enc_gc_tokens(arp_enc* e, int* tokens);  // 2 P + 1
 // arp_op_gemm_site's "m3ae.*" instances (the encoder's own, in this unit)
 int enc_op_gemm_site(const arp_gemm_site& d);

@@ -90,7 +90,8 @@ class M3AEEncoder:
     def set_latency_rows(self, rows, host_calls=None):
         """The latency path's row limit (``arp_enc_set_latency``): a call of at most ``rows`` token rows in total (frames x tokens; f16 / bf16) runs the skinny
         GEMMs instead of the throughput tiles.  A rollout session's per-step pass takes the path by default; ``host_calls=True`` makes
-        :meth:`forward_representation` take it too.  ``rows=0`` turns it off for every caller."""
+        :meth:`forward_representation` and :meth:`forward_gc_representations` take it too.  A goal-conditioned call counts ``pairs x gc_tokens`` rows.
+        ``rows=0`` turns it off for every caller."""
         check(lib.arp_enc_set_latency(self._h, int(rows), -1 if host_calls is None else int(bool(host_calls))))
 
     def profile(self, on=True):

@@ -37,9 +37,14 @@ class RolloutSession:
     ``encoder``: the encoder to use instead of the trainer's attached one.  Model BC (``PolicyConfig(model="BC")``) runs this way -- it refuses
     ``attach_encoder`` and keeps refusing it, the session borrows the encoder for its own passes: two tokens per step, no return-to-go ring, and a reward
     model, ``use_normalize`` / ``reward_min`` and ``rewards=`` are refused by the library.
+    ``goal_conditioned=True`` (``arp_rollout_create_gc``): the session keeps one goal frame per environment in HBM, handed over with ``reset(goals=...)``
+    (the reference fixes it per episode, rollout_procgen.py:94).  With a GCBC trainer a step encodes the new (frame, goal) pairs; with an ARP-DT trainer and a
+    plain :class:`arp_amd.clip.ClipLabeller` (no prompts needed) the reward is ``clip_goal_conditioned``, ``-||f(frame) - f(goal)||`` on the device, the goal's
+    feature computed once per reset; ``use_crop`` is then refused.  Without the flag a GCBC trainer is refused, as ever.
     """
 
-    def __init__(self, trainer, reward_model=None, n_envs=1, return_to_go=100.0, scale=100.0, reward_min=0.0, use_normalize=False, lut=None, encoder=None):
+    def __init__(self, trainer, reward_model=None, n_envs=1, return_to_go=100.0, scale=100.0, reward_min=0.0, use_normalize=False, lut=None, encoder=None,
+                 goal_conditioned=False):
         from . import _ffi, dataset
         from .finetune import FinetunedClip
         self._ffi = _ffi
@@ -52,7 +57,12 @@ class RolloutSession:
         res = enc.cfg.img_res if enc is not None else 0
         h = C.c_void_p()
         rm = reward_model._h if reward_model is not None and not finetuned else None
-        if finetuned:  # the fine-tuned reward: its towers and its head (both kept alive through reward_model below)
+        self.goal_conditioned = bool(goal_conditioned)
+        if goal_conditioned:
+            if finetuned:
+                raise _ffi.ArpError("rollout: create_gc takes a plain labelling handle: the fine-tuned goal reward stays with the host function")
+            _ffi.check(_ffi.lib.arp_rollout_create_gc(trainer._h, encoder._h if encoder is not None else None, rm, int(n_envs), res, res, float(scale), C.byref(h)))
+        elif finetuned:  # the fine-tuned reward: its towers and its head (both kept alive through reward_model below)
             if reward_model._resident_text_error:
                 raise _ffi.ArpError(reward_model._resident_text_error)
             _ffi.check(_ffi.lib.arp_rollout_create_ft(trainer._h, encoder._h if encoder is not None else None, reward_model.towers._h,
@@ -81,13 +91,24 @@ class RolloutSession:
     def set_reward_norm(self, use_normalize, reward_min):
         self._ffi.check(self._ffi.lib.arp_rollout_set_reward_norm(self._h, int(bool(use_normalize)), float(reward_min)))
 
-    def reset(self, env_ids=None, rtg=None):
+    def reset(self, env_ids=None, rtg=None, goals=None):
         """Start an episode in ``env_ids`` (default: all).  ``rtg``: the first return-to-go, already divided by ``scale`` (scalar or one per listed
-        environment; default ``return_to_go / scale``)."""
+        environment; default ``return_to_go / scale``).  ``goals`` (a ``goal_conditioned`` session): the listed environments' goal frames, uint8
+        ``[n, H, W, 3]`` (``[H, W, 3]`` for one); without it an environment keeps the goal it has."""
         ids = np.arange(self.n_envs, dtype=np.int32) if env_ids is None else np.require(np.asarray(env_ids, np.int32).reshape(-1), requirements="C")
         r = np.full(len(ids), self.return_to_go / self.scale if rtg is None else 0.0, np.float32)
         if rtg is not None:
             r[:] = np.asarray(rtg, np.float32).reshape(-1)
+        if goals is not None:
+            g = np.asarray(goals)
+            if g.dtype != np.uint8:
+                raise ValueError("goals must be uint8")
+            g = np.require(g.reshape(-1, *g.shape[-3:]), requirements="C")
+            if g.shape != (len(ids), self.res, self.res, 3):
+                raise ValueError(f"goals {g.shape}, expected {(len(ids), self.res, self.res, 3)}")
+            self._ffi.check(self._ffi.lib.arp_rollout_reset_goal(self._h, self._ffi.as_ptr(ids, C.c_int32), len(ids), self._ffi.as_ptr(r, C.c_float),
+                                                                 self._ffi.as_ptr(g, C.c_uint8)))
+            return
         self._ffi.check(self._ffi.lib.arp_rollout_reset(self._h, self._ffi.as_ptr(ids, C.c_int32), len(ids), self._ffi.as_ptr(r, C.c_float)))
 
     def step(self, frames_u8, rewards=None, use_crop=False):
@@ -113,7 +134,8 @@ class RolloutSession:
         E, T = self.n_envs, self.window
         shape, dt = {"enc_window": ((E, T, self.tokens, self.dim), np.float32), "action_window": ((E, T), np.int32), "rtg_window": ((E, T), np.float32),
                      "len": ((E,), np.int32), "rtg": ((E,), np.float32), "reward": ((E,), np.float32), "logits": ((E, T, self.n_actions), np.float32),
-                     "enc_ring": ((T, E, self.tokens, self.dim), np.float32), "head": ((1,), np.int32)}[what]
+                     "enc_ring": ((T, E, self.tokens, self.dim), np.float32), "head": ((1,), np.int32), "goal": ((E, self.res, self.res, 3), np.uint8),
+                     "goal_feat": ((E, getattr(getattr(self.reward_model, "cfg", None), "embed", 0)), np.float32)}[what]
         out = np.empty(shape, dt)
         self._ffi.check(self._ffi.lib.arp_rollout_read(self._h, what.encode(), out.ctypes.data_as(C.c_void_p), out.nbytes))
         return out
@@ -133,7 +155,7 @@ class RolloutSession:
             pass
 
 
-def batch_rollout(env, session, episode_length, num_episodes, transform_action_fn=None, log_interval=None):
+def batch_rollout(env, session, episode_length, num_episodes, transform_action_fn=None, log_interval=None, goals=None):
     """The reference loop (rollout_procgen.py:84-182) around a one-environment session; returns its ``metric`` dict
     (``return``, ``episode_length``; :178-181).  numpy only.
 
@@ -146,7 +168,11 @@ def batch_rollout(env, session, episode_length, num_episodes, transform_action_f
     action ring keeps the greedy action itself and only ``env.step`` sees ``transform_action_fn(action)``.  The two agree for the identity transform the
     reference runs with, and for no other.
 
-    Out of scope (no Procgen in this project): ``eval_data_path`` replay with saved states and goal images, videos, state recording, several
+    ``goals`` (a goal-conditioned session): a sequence indexed by episode or a callable ``goals(ep)`` giving episode ``ep``'s goal frame, uint8 ``[H, W, 3]``;
+    it is handed to ``session.reset(goals=...)`` at that episode's reset and nowhere else, where the reference reads
+    ``eval_hdf5["ob"][eval_traj_idx[ep + 1] - 1, -1]`` (:94) and re-attaches it to every observation (:108,130).
+
+    Out of scope (no Procgen in this project): ``eval_data_path`` replay with saved states, videos, state recording, several
     image keys.  The vision-language reward and the return-to-go are the session's business (:class:`RolloutSession`).
     """
     import logging
@@ -154,7 +180,10 @@ def batch_rollout(env, session, episode_length, num_episodes, transform_action_f
     reward, ep_lens = np.zeros(1, np.float32), np.zeros(1, np.float32)
     info = {}
     for ep in range(num_episodes):
-        session.reset()
+        if goals is None:
+            session.reset()
+        else:
+            session.reset(goals=np.asarray(goals(ep) if callable(goals) else goals[ep], np.uint8)[None])
         done = np.zeros(1, np.int32)
         next_obs = None
         for t in range(episode_length):

@@ -129,6 +129,10 @@ int arp_clip_set_streams(arp_clip* h, int n_streams); /* change the stream count
 /* model.encode_image (label_reward.py:156, clip_goal_conditioned variant) */
 int arp_clip_encode_image(arp_clip* h, const uint8_t* frames_host, int n, int H, int W, int use_crop, int normalize,
                           float* out /* [n, embed] */);
+/* The same with frames and features in device memory: enqueued on the handle's stream (ordered against other streams by the caller's events), no copy out, no
+ * wait.  At most max_batch frames per call; no prompt set needed.  The rollout session's goal reward (arp_rollout_create_gc) runs on it. */
+int arp_clip_encode_image_dev_async(arp_clip* h, const uint8_t* frames_dev, int n, int H, int W, int use_crop, int normalize,
+                                    float* feats_dev /* [n, embed] */);
 
 /* The torchvision/PIL transform alone (label_reward.py:109-121 / :92-102), for PIL-parity tests:
  * uint8 NHWC -> f32 NCHW [n,3,res,res]. */
@@ -422,7 +426,7 @@ int arp_enc_forward(arp_enc* h, const float* images_host, int n, float* out_host
  * pairs, both f32 NHWC [n,res,res,3] -> f32 [n, 2 P + 1, width] with P = (img_res / patch)^2.  One sequence per pair: class token, the frame's P patches, the goal
  * frame's P patches; both patch blocks carry the same 2-D sincos position and image type embedding.  Both frame sets share one patch-embedding product; at
  * 256 x 256 the blocks run over 513 tokens, on the key-blocked attention kernels (csrc/attention_long.h).  max_frames counts pairs in this call; part streams
- * apply as in arp_enc_forward; the latency path is never taken.  Modes f32, f16, bf16, f16x3; ARP_MODE_F16C returns an error (its attention output form
+ * apply as in arp_enc_forward, and so does the latency path (arp_enc_set_latency: off for this call unless host_calls = 1; counted on n (2 P + 1) rows).  Modes f32, f16, bf16, f16x3; ARP_MODE_F16C returns an error (its attention output form
  * exists up to 288 tokens only).  arp_enc_gc_tokens: 2 P + 1. */
 int arp_enc_forward_gc(arp_enc* h, const float* images_host, const float* goals_host, int n, float* out_host);
 int arp_enc_gc_tokens(arp_enc* h);
@@ -435,7 +439,7 @@ int arp_enc_set_streams(arp_enc* h, int n_streams, int first_part_frames, int mi
  * measured slower; capped at 1024), in ARP_MODE_F16 / ARP_MODE_BF16,
  * runs the W-tiled skinny GEMMs with split-K out_proj / c_proj whose reduction applies the next LayerNorm (csrc/tower.h::run_blocks) instead of the throughput
  * tiles: same operands, same accumulation type, another summation order.  Only a rollout session's per-step pass takes it by default; host_calls = 1 makes
- * arp_enc_forward take it too (0: not; < 0: unchanged).  rows = 0 turns the path off for every caller.  The training paths never take it.
+ * arp_enc_forward and arp_enc_forward_gc take it too (0: not; < 0: unchanged); a goal-conditioned call counts pairs x (2 P + 1) rows.  rows = 0 turns the path off for every caller.  The training paths never take it.
  * Environment: ARP_ENC_LAT_ROWS sets `rows` at create. */
 int arp_enc_set_latency(arp_enc* h, int rows, int host_calls);
 int arp_enc_profile_enable(arp_enc* h, int on);
@@ -507,6 +511,19 @@ int arp_rollout_create_with_encoder(arp_dt* policy, arp_enc* encoder, arp_clip* 
  * constructors above.  The head's prompts (arp_ft_reward_set_text, arp_ft_reward_set_reduce) may be set before or after creation, and must be current at
  * every step.  Refused at creation: towers and head on different devices or of different geometry, a goal_conditioned head. */
 int arp_rollout_create_ft(arp_dt* policy, arp_enc* encoder_or_null, arp_clip* towers, arp_ft* head, int n_envs, int H, int W, float scale, arp_rollout** out);
+/* A session that carries ONE GOAL FRAME PER ENVIRONMENT in HBM (the reference fixes it per episode and re-attaches it to every observation,
+ * envs/rollout_procgen.py:94,108,130).  The three constructors above keep refusing a GCBC policy; this one accepts
+ *   - a GCBC policy (no reward handle, as for BC; the encoder attached to it or a lent one): a step encodes the E new (frame, goal) pairs, F = (2 P + 1) x width
+ *     per ring entry, and is otherwise the BC step;
+ *   - an ARP-DT policy with a plain labelling handle: the reward is clip_goal_conditioned (get_torch_clip_goal_conditioned_reward, envs/vl_reward.py:26-41),
+ *     reward[e] = -|| f(frame_e) - f(goal_e) ||_2 on un-normalised image features through the label transform, computed on the reward handle's stream; the
+ *     goals' features are computed once, at arp_rollout_reset_goal.  No prompt set is needed; use_crop = 1 in arp_rollout_step is refused.
+ * Refused: model BC, an ARP-DT policy without a reward handle, a fine-tuned head (there is no argument for one).
+ * arp_rollout_reset_goal is arp_rollout_reset (rtg0_or_null: NULL for a GCBC policy, required otherwise) plus the goal frames of the listed environments, uint8
+ * [n, H, W, 3] in host memory; a plain arp_rollout_reset keeps an environment's goal.  arp_rollout_step is refused until every environment has a goal.
+ * arp_rollout_read gains "goal" uint8 [E, H, W, 3] and, with the goal reward, "goal_feat" f32 [E, embed]. */
+int arp_rollout_create_gc(arp_dt* policy, arp_enc* encoder_or_null, arp_clip* reward_or_null, int n_envs, int H, int W, float scale, arp_rollout** out);
+int arp_rollout_reset_goal(arp_rollout* h, const int32_t* env_ids, int n, const float* rtg0_or_null, const uint8_t* goals_u8 /* [n, H, W, 3] */);
 int arp_rollout_destroy(arp_rollout* h);
 /* start an episode in the n listed environments: return-to-go rtg0[i] (already divided by scale, as :90), episode length 0 */
 int arp_rollout_reset(arp_rollout* h, const int32_t* env_ids, int n, const float* rtg0);
