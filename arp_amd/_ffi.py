@@ -225,6 +225,9 @@ SIGNATURES = {
     "arp_ds_nbytes": (C.c_int64, [_vp]),
     "arp_dt_upload_batch_indices_async": (_i, [_vp, _i, _vp, _i64p, _i, _i]),
     "arp_dt_set_batch_indices": (_i, [_vp, _vp, _i64p, _i, _i]),
+    "arp_dt_upload_batch_index_pairs_async": (_i, [_vp, _i, _vp, _i64p, _i64p, _i]),
+    "arp_dt_set_batch_index_pairs": (_i, [_vp, _vp, _i64p, _i64p, _i]),
+    "arp_ds_gather_pairs_debug": (_i, [_vp, _i64p, _i64p, _i, _i, _fp, _fp, _i32p]),
     "arp_rollout_create": (_i, [_vp, _vp, _i, _i, _i, _f, C.POINTER(_vp)]),
     "arp_rollout_create_with_encoder": (_i, [_vp, _vp, _vp, _i, _i, _i, _f, C.POINTER(_vp)]),
     "arp_rollout_create_ft": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _f, C.POINTER(_vp)]),

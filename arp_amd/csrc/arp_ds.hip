@@ -43,9 +43,8 @@ __device__ __forceinline__ int ds_source_row(const int32_t* __restrict__ idx, co
 // out[f] = lut[c][frames[j(f)]]: uint8 NHWC frames -> the f32 frames the encoder reads.  One block walks `iters` tiles of 256 x 16 bytes of ONE frame:
 // every lane loads 16 bytes (1 KiB per wave instruction), the tile is turned through LDS so that lane l of store s holds the dword (s * 256 + l) of the tile,
 // and every store instruction writes 16 bytes per lane, 1 KiB contiguous per wave.  The table sits in LDS (3 KB); the written value is exactly lut[c][u].
-__global__ __launch_bounds__(DS_THREADS) void ds_frame_gather_kernel(const uint8_t* __restrict__ frames, const int32_t* __restrict__ idx,
-                                                                      const int32_t* __restrict__ start, const float* __restrict__ lut,
-                                                                      float* __restrict__ out, int T, uint32_t chunks, int iters) {
+__device__ __forceinline__ void ds_frame_gather_body(const uint8_t* __restrict__ frames, const int32_t* __restrict__ idx, const int32_t* __restrict__ start,
+                                                     const float* __restrict__ lut, float* __restrict__ out, int T, uint32_t chunks, int iters) {
     __shared__ float s_lut[3 * 256];
     __shared__ uint4 s_tile[2][DS_THREADS];
     const int tid = threadIdx.x, f = blockIdx.y;
@@ -71,6 +70,23 @@ __global__ __launch_bounds__(DS_THREADS) void ds_frame_gather_kernel(const uint8
             }
         }
     }
+}
+
+__global__ __launch_bounds__(DS_THREADS) void ds_frame_gather_kernel(const uint8_t* __restrict__ frames, const int32_t* __restrict__ idx,
+                                                                      const int32_t* __restrict__ start, const float* __restrict__ lut,
+                                                                      float* __restrict__ out, int T, uint32_t chunks, int iters) {
+    ds_frame_gather_body(frames, idx, start, lut, out, T, chunks, iters);
+}
+
+// A (frame, goal) pair slot in ONE launch (model GCBC): grid z = 0 fills `out` with the windows of idx, z = 1 fills `goals` with the windows of gidx -- the
+// goal frames of sample b are the window of its goal row under the same rule (data_procgen.py:189 reads ob[g][-T:]).  z and not a doubled y: B * T alone may
+// reach grid y's 65 535.  Same block shape, same loads, same LDS turn, same stores as the kernel above (its body).
+__global__ __launch_bounds__(DS_THREADS) void ds_frame_gather_pairs_kernel(const uint8_t* __restrict__ frames, const int32_t* __restrict__ idx,
+                                                                            const int32_t* __restrict__ gidx, const int32_t* __restrict__ start,
+                                                                            const float* __restrict__ lut, float* __restrict__ out, float* __restrict__ goals,
+                                                                            int T, uint32_t chunks, int iters) {
+    const bool g = blockIdx.z != 0;  // (uniform)
+    ds_frame_gather_body(frames, g ? gidx : idx, start, lut, g ? goals : out, T, chunks, iters);
 }
 
 // out[f] = cache[j(f)]: row copies of `vec` 16-byte vectors
@@ -155,6 +171,34 @@ static int gather_impl(arp_ds* d, hipStream_t st, const int32_t* idx_dev, const 
 int ds_gather_on(arp_ds* d, hipStream_t st, const int32_t* idx_dev, int B, int T, float* frames_out, float* enc_out, int32_t* action_out, float* rtg_out) {
     if (!d->labels) return fail("the dataset's labels are not set (arp_ds_set_labels)");
     return gather_impl(d, st, idx_dev, d->start.as<int32_t>(), B, T, frames_out, enc_out, action_out, rtg_out);
+}
+
+int ds_check_goals(arp_ds* d, const int64_t* gidx, int B) {
+    if (!d || !gidx || B <= 0) return fail("bad argument");
+    for (int b = 0; b < B; ++b)
+        if (gidx[b] < 0 || gidx[b] >= d->n_rows)
+            return fail("goal index " + std::to_string((long long)gidx[b]) + " (batch position " + std::to_string(b) + ") is outside [0, " + std::to_string(d->n_rows) + ")");
+    return 0;
+}
+
+int ds_gather_pairs_on(arp_ds* d, hipStream_t st, const int32_t* idx_dev, const int32_t* gidx_dev, int B, int T, float* frames_out, float* goals_out,
+                       int32_t* action_out) {
+    if (!d->labels) return fail("the dataset's labels are not set (arp_ds_set_labels)");
+    if (!frames_out != !goals_out) return fail("a pair gather writes frames and goals together (or the labels alone)");
+    const int n = B * T;
+    if (frames_out) {  // the grid of gather_impl's frame launch, twice along z
+        const uint32_t chunks = (uint32_t)(d->fb / 16);
+        const size_t tiles = (chunks + DS_THREADS - 1) / DS_THREADS;
+        const int iters = (int)((tiles + row_blocks(tiles, n) - 1) / row_blocks(tiles, n));
+        const int gx = (int)((tiles + iters - 1) / iters);
+        hipLaunchKernelGGL(ds_frame_gather_pairs_kernel, dim3(gx, n, 2), dim3(DS_THREADS), 0, st, d->frames.as<uint8_t>(), idx_dev, gidx_dev, d->start.as<int32_t>(),
+                           d->lut.as<float>(), frames_out, goals_out, T, chunks, iters);
+    }
+    if (action_out)  // GCBC reads no return-to-go
+        hipLaunchKernelGGL(ds_label_gather_kernel, dim3((n + 63) / 64), dim3(64), 0, st, d->action.as<int32_t>(), (const float*)nullptr, idx_dev,
+                           d->start.as<int32_t>(), action_out, (float*)nullptr, T, n);
+    ARP_HIP_OK(hipGetLastError());
+    return 0;
 }
 
 }  // namespace arp
@@ -315,6 +359,30 @@ int arp_ds_gather_debug(arp_ds* d, const int64_t* idx, int B, int window, float*
     if (frames_out) ARP_HIP_OK(hipMemcpy(frames_out, df.p, n * d->fb * 4, hipMemcpyDeviceToHost));
     if (action_out) ARP_HIP_OK(hipMemcpy(action_out, da.p, n * 4, hipMemcpyDeviceToHost));
     if (rtg_out) ARP_HIP_OK(hipMemcpy(rtg_out, dr.p, n * 4, hipMemcpyDeviceToHost));
+    return 0;
+}
+
+// arp_ds_gather_debug for (frame, goal) pairs: goals_out f32 [B, window, res, res, 3] holds the windows of the goal rows.  Frames and goals come from the
+// one pair launch (both are gathered whenever either is asked for); each output may be NULL.  Synchronous, on the null stream.
+int arp_ds_gather_pairs_debug(arp_ds* d, const int64_t* idx, const int64_t* goal_idx, int B, int window, float* frames_out, float* goals_out, int32_t* action_out) {
+    if (!d) return fail("null handle");
+    const bool fr = frames_out || goals_out;
+    ARP_TRY(ds_check_batch(d, idx, B, window, d->device, 0, false, fr ? 0 : -1, d->res, 0, 0));
+    ARP_TRY(ds_check_goals(d, goal_idx, B));
+    ARP_HIP_OK(hipSetDevice(d->device));
+    const size_t n = (size_t)B * window;
+    std::vector<int32_t> h(idx, idx + B);
+    h.insert(h.end(), goal_idx, goal_idx + B);
+    DevBuf di, df, dg, da;  // (freed on every return; hipFree waits for the gather)
+    ARP_TRY(di.ensure((size_t)B * 8));
+    if (fr) ARP_TRY(df.ensure(n * d->fb * 4));
+    if (fr) ARP_TRY(dg.ensure(n * d->fb * 4));
+    if (action_out) ARP_TRY(da.ensure(n * 4));
+    ARP_HIP_OK(hipMemcpy(di.p, h.data(), (size_t)B * 8, hipMemcpyHostToDevice));
+    ARP_TRY(ds_gather_pairs_on(d, nullptr, di.as<int32_t>(), di.as<int32_t>() + B, B, window, df.as<float>(), dg.as<float>(), da.as<int32_t>()));
+    if (frames_out) ARP_HIP_OK(hipMemcpy(frames_out, df.p, n * d->fb * 4, hipMemcpyDeviceToHost));
+    if (goals_out) ARP_HIP_OK(hipMemcpy(goals_out, dg.p, n * d->fb * 4, hipMemcpyDeviceToHost));
+    if (action_out) ARP_HIP_OK(hipMemcpy(action_out, da.p, n * 4, hipMemcpyDeviceToHost));
     return 0;
 }
 

@@ -79,7 +79,7 @@ struct arp_dt {
     struct BatchSlot {
         DevBuf enc32, action, rtg;
         DevBuf img32;             // raw frames [B*T, res, res, 3] f32 when the encoder is attached
-        DevBuf goal32;            // model GCBC: the goal frames, same shape (arp_dt_set_batch_images_goal; the synchronous slot only)
+        DevBuf goal32;            // model GCBC: the goal frames, same shape (arp_dt_set_batch_images_goal on the synchronous slot; arp_dt_*_index_pairs* on any)
         bool goals = false;       // the frames in img32 come with goals in goal32: the encoder pass is the goal-conditioned one
         int B = 0;
         bool images = false;
@@ -90,7 +90,7 @@ struct arp_dt {
         bool up_recorded = false;       // `up` has been recorded at least once (a slot the prefetcher has used)
         bool enc_ahead = false;         // enc32 holds (or will hold, behind enc_done) the encodings of the frames now in img32: the step does not encode again
         // a batch named by row indices of a device-resident dataset (arp_dt_upload_batch_indices_async): the indices go through idx_pin, a small pinned
-        // staging buffer of the handle's, into idx, and gather kernels on the upload's stream fill the buffers above
+        // staging buffer of the handle's, into idx, and gather kernels on the upload's stream fill the buffers above ((row, goal row) pairs: [idx | goal idx])
         DevBuf idx;
         PinBuf idx_pin;
     } bt[3];  // 0 / 1: the prefetcher's slots (arp_dt_upload_batch*_async); 2: the synchronous arp_dt_set_batch* calls -- a validation
@@ -1689,7 +1689,9 @@ static int stage_slot_indices(arp_dt* c, int si, hipStream_t st, arp_ds* ds, con
     int tokens = k.enc_tokens, width = k.enc_dim, res = 0, dev = k.device;
     if (!use_encodings) {
         if (!c->enc) return fail("no encoder attached: index batches of frames need arp_dt_attach_encoder first (or use_encodings with cached encodings)");
-        if (c->gcbc()) return fail("model GCBC: the device-resident dataset gathers no goal frames (stage frames and goals with arp_dt_set_batch_images_goal)");
+        if (c->gcbc())
+            return fail("model GCBC: a plain index batch names no goal rows (name them with arp_dt_set_batch_index_pairs / arp_dt_upload_batch_index_pairs_async, "
+                        "or stage frames and goals with arp_dt_set_batch_images_goal)");
         ARP_TRY(enc_geometry(c->enc, &tokens, &width, &res, &dev));
     }
     const bool with_rtg = !c->bc();
@@ -1748,6 +1750,72 @@ int arp_dt_set_batch_indices(arp_dt* c, arp_ds* ds, const int64_t* idx, int B, i
     return 0;
 }
 
+// Model GCBC from the device-resident set: B (row, goal row) pairs into slot `si`.  stage_slot_indices with a second index array: both go through the slot's
+// pinned staging ([idx | goal_idx], one copy) into b.idx, ONE frame-gather launch fills img32 and goal32 (ds_gather_pairs_on), the actions follow idx.
+// Every check runs on the host before anything is enqueued.
+static int stage_slot_index_pairs(arp_dt* c, int si, hipStream_t st, arp_ds* ds, const int64_t* idx, const int64_t* gidx, int B) {
+    const arp_dt_cfg& k = c->cfg;
+    if (!c->gcbc()) return fail("goal indices belong to model GCBC (ARP_DT_MODEL_GCBC)");
+    if (!c->enc) return fail("no encoder attached: index pairs gather frames and goal frames, which need arp_dt_attach_encoder first");
+    int tokens = 0, width = 0, res = 0, dev = k.device;
+    ARP_TRY(enc_geometry(c->enc, &tokens, &width, &res, &dev));
+    ARP_TRY(ds_check_batch(ds, idx, B, k.window, k.device, k.n_actions, false, 0, res, k.enc_tokens, k.enc_dim));
+    ARP_TRY(ds_check_goals(ds, gidx, B));
+    arp_dt::BatchSlot& b = c->bt[si];
+    const size_t R = (size_t)B * k.window, fb = (size_t)res * res * 3 * 4;
+    ARP_TRY(b.action.ensure(R * 4));
+    ARP_TRY(b.enc32.ensure(R * k.enc_tokens * k.enc_dim * 4));  // the encoder's output buffer
+    ARP_TRY(b.img32.ensure(R * fb));
+    ARP_TRY(b.goal32.ensure(R * fb));
+    ARP_TRY(b.idx.ensure((size_t)B * 8));
+    ARP_TRY(b.idx_pin.ensure((size_t)B * 8));
+    for (int i = 0; i < B; ++i) {
+        b.idx_pin.as<int32_t>()[i] = (int32_t)idx[i];
+        b.idx_pin.as<int32_t>()[B + i] = (int32_t)gidx[i];
+    }
+    ARP_HIP_OK(hipMemcpyAsync(b.idx.p, b.idx_pin.p, (size_t)B * 8, hipMemcpyHostToDevice, st));
+    hipEvent_t t0 = si == 2 && c->prof.on ? c->prof.begin(st) : nullptr;  // (the synchronous slot only, as stage_slot_indices)
+    ARP_TRY(ds_gather_pairs_on(ds, st, b.idx.as<int32_t>(), b.idx.as<int32_t>() + B, B, k.window, b.img32.as<float>(), b.goal32.as<float>(), b.action.as<int32_t>()));
+    if (t0) c->prof.end("ds.gather_pairs", t0, st);
+    b.B = B;
+    b.images = true;
+    b.goals = true;
+    return 0;
+}
+
+// arp_dt_upload_batch_indices_async for (row, goal row) pairs: same slots, same copy stream, same protocol.  The encode-ahead pass nobody consumed reads
+// goal32 too, so the same host wait on enc_done covers it.
+int arp_dt_upload_batch_index_pairs_async(arp_dt* c, int slot, arp_ds* ds, const int64_t* idx, const int64_t* goal_idx, int B) {
+    if (!c || !ds || !idx || !goal_idx || B <= 0 || slot < 0 || slot > 1) return fail("bad argument");
+    ARP_HIP_OK(hipSetDevice(c->cfg.device));
+    arp_dt::BatchSlot& b = c->bt[slot];
+    std::lock_guard<std::mutex> capture_lock(c->capture_mu);
+    if (b.used) ARP_HIP_OK(hipEventSynchronize(b.use));
+    if (b.up_recorded) ARP_HIP_OK(hipEventSynchronize(b.up));
+    if (b.enc_ahead && b.enc_done) ARP_HIP_OK(hipEventSynchronize(b.enc_done));
+    if (!c->copy_stream) ARP_TRY(c->copy_stream.create());
+    ARP_TRY(stage_slot_index_pairs(c, slot, c->copy_stream, ds, idx, goal_idx, B));
+    ARP_HIP_OK(hipEventRecord(b.up, c->copy_stream));
+    b.up_pending = true;
+    b.up_recorded = true;
+    b.enc_ahead = false;
+    return 0;
+}
+
+// The synchronous form (slot 2, the compute stream), as arp_dt_set_batch_indices.
+int arp_dt_set_batch_index_pairs(arp_dt* c, arp_ds* ds, const int64_t* idx, const int64_t* goal_idx, int B) {
+    if (!c || !ds || !idx || !goal_idx || B <= 0) return fail("bad argument");
+    ARP_HIP_OK(hipSetDevice(c->cfg.device));
+    if (c->bt[2].enc_ahead && c->enc_stream) ARP_HIP_OK(hipStreamSynchronize(c->enc_stream));
+    ARP_TRY(stage_slot_index_pairs(c, 2, c->stream, ds, idx, goal_idx, B));  // (a refused batch leaves the staged one selected)
+    c->cur = 2;
+    c->bt[2].enc_ahead = false;
+    ARP_TRY(ensure_buffers(c, B));
+    ARP_HIP_OK(hipStreamSynchronize(c->stream));
+    c->use_images = true;
+    return 0;
+}
+
 int arp_dt_attach_encoder(arp_dt* c, arp_enc* enc) {
     if (!c || !enc) return fail("null argument");
     // The reference's InstructRL encoder sees the BERT-tokenized instruction beside the frame (BC.py:286-321: 1 + 256 + 77 tokens); this encoder is
@@ -1800,7 +1868,9 @@ static int set_batch_frames(arp_dt* c, const float* images, const float* goals, 
 int arp_dt_encode_ahead(arp_dt* c, int slot) {
     if (!c || slot < 0 || slot > 2) return fail("bad argument");
     if (!c->enc) return fail("no encoder attached: call arp_dt_attach_encoder first");
-    if (c->gcbc()) return fail("model GCBC: no encode-ahead (goal batches exist in the synchronous slot only, and their step encodes them)");
+    // model GCBC: slots 0 / 1 hold goals once arp_dt_upload_batch_index_pairs_async has filled them (enqueue_encode runs the goal-conditioned pass on b.goals);
+    // the synchronous slot's step encodes its own batch
+    if (c->gcbc() && slot == 2) return fail("model GCBC: no encode-ahead (goal batches exist in the synchronous slot only, and their step encodes them)");
     if (!c->enc_eager) return fail("arp_dt_encode_ahead needs the eager encoder path (ARP_DT_ENC_EAGER=0 captures the encoder inside the step's graph)");
     ARP_HIP_OK(hipSetDevice(c->cfg.device));
     std::lock_guard<std::mutex> lock(c->capture_mu);

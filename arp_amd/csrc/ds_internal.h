@@ -13,4 +13,11 @@ int ds_check_batch(arp_ds* d, const int64_t* idx, int B, int window, int device,
 // The gathers of one batch, enqueued on `st`.  idx_dev: int32[B] in HBM.  Row of (b, t): j = max(idx[b] - (T - 1 - t), traj_start[idx[b]]).
 // frames_out f32 [B*T, res, res, 3] (= lut[c][u]) or enc_out f32 [B*T, tokens*dim], whichever is non-null; action_out int32 [B*T]; rtg_out f32 [B*T] or null.
 int ds_gather_on(arp_ds* d, hipStream_t st, const int32_t* idx_dev, int B, int T, float* frames_out, float* enc_out, int32_t* action_out, float* rtg_out);
+// Model GCBC's (frame, goal) pairs.  ds_check_goals: every gidx in [0, n_rows), on the host, naming the batch position -- bounds only, not the hindsight rule
+// (a caller may name goals from elsewhere; traj_start[g] <= g keeps the gather inside the buffer).  ds_gather_pairs_on: ONE frame-gather launch whose grid z
+// selects the half -- z = 0 reads idx_dev and writes frames_out, z = 1 reads gidx_dev and writes goals_out (the window of the goal row under the same rule);
+// both non-null or both null.  action_out int32 [B*T] follows idx_dev; no return-to-go.
+int ds_check_goals(arp_ds* d, const int64_t* gidx, int B);
+int ds_gather_pairs_on(arp_ds* d, hipStream_t st, const int32_t* idx_dev, const int32_t* gidx_dev, int B, int T, float* frames_out, float* goals_out,
+                       int32_t* action_out);
 }  // namespace arp

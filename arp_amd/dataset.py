@@ -15,8 +15,14 @@ The window rule.  The recorder builds every row with ``stack_frames`` (data/PPG/
 (likewise ``act`` and the stacked returns-to-go).  ``__getitem__`` is built from the per-row values by that rule; ``literal_item`` reads the
 stacked rows themselves and ``verify`` compares the two on sampled rows -- ``DeviceDataset.load`` refuses a file that fails it.
 
-Not here: goal frames (hindsight relabelling draws from an RNG), ``use_task_reward``, ``state``, several image keys, the BERT tokenizer,
-``random_start``.  There is no CPU fallback for the device side: the gathers are in libarp_hip.so.
+Goal frames (model GCBC).  The hindsight goal of row ``i`` is one RNG draw over the rows from ``i`` to the end of its trajectory
+(``ProcgenDataset.goal_row``, data_procgen.py:186-189) and its frames are ``ob[g][-T:]``: the window of row ``g`` under the same rule.  The draw stays on
+the host -- ``DeviceDataset.index_batches(goal_rng=...)`` yields ``{"index", "goal_index"}`` pair batches, drawn in the order a sequential host loader
+draws -- and one gather launch fills a slot's frames and goal frames from the set in HBM (``PolicyTrainer.set_batch_index_pairs`` /
+``upload_index_pairs_async``).  A pair's encoding is not a per-row quantity: there is no encodings cache for it.
+
+Not here: ``use_task_reward``, ``state``, several image keys, the BERT tokenizer, ``random_start``.  There is no CPU fallback for the device side:
+the gathers are in libarp_hip.so.
 """
 import ctypes as C
 import os
@@ -190,15 +196,17 @@ class ProcgenDataset:
         return np.stack([np.asarray(ob[int(j)][-1]) for j in rows])
 
     # -- data_procgen.py:186-189 ---------------------------------------------------------------------------------------------------
-    def goal_row(self, i):
+    def goal_row(self, i, rng=None):
         """The hindsight goal of (processed) row i: one draw of ``goal_rng.choice`` over the rows from i to the end of i's trajectory -- the reference's own
-        call, so a RandomState seeded like its global generator gives its sequence -- clamped to the last row.  The goal frames are that row's window."""
-        if self.goal_rng is None:
+        call, so a RandomState seeded like its global generator gives its sequence -- clamped to the last row.  The goal frames are that row's window.
+        ``rng``: draw from this generator instead of the dataset's own (``DeviceDataset.index_batches(goal_rng=...)``)."""
+        rng = self.goal_rng if rng is None else rng
+        if rng is None:
             raise ValueError("no goal_rng: construct the dataset with goal_rng=numpy.random.RandomState(seed)")
         b = self.h5_file_traj_idx
         t = int(self.idx_to_traj[i])
         end = b[t + 1] if t + 1 < len(b) and b[t] <= i < b[t + 1] else self.n_rows  # (rows behind the last done flag: their unfinished trajectory)
-        return min(self.goal_rng.choice(list(range(i, end)), 1).item(), self.n_rows - 1)
+        return min(rng.choice(list(range(i, end)), 1).item(), self.n_rows - 1)
 
     def _labels(self, index, j):
         res = {"image": {}, "rtg": {}}
@@ -355,9 +363,10 @@ class DeviceDataset:
         if row0 != self.n_rows:
             raise ArpError(f"set_encodings: {row0} rows given, the dataset has {self.n_rows}")
 
-    def gather(self, idx, window=None, frames=True):
+    def gather(self, idx, window=None, frames=True, goal_index=None):
         """Debug read-back: ``{"image": f32 [B, T, res, res, 3], "action": int32 [B, T], "rtg": f32 [B, T, 1] (if the set holds one)}`` of the batch
-        the row indices name."""
+        the row indices name.  ``goal_index`` (model GCBC's pair batch): ``"goal"`` beside ``"image"`` -- the windows of the goal rows, through the pair
+        gather -- and no ``"rtg"`` (GCBC reads none)."""
         idx = np.require(np.asarray(idx, dtype=np.int64).reshape(-1), requirements="C")
         T = int(self.window_size if window is None else window)
         B = len(idx)
@@ -365,6 +374,15 @@ class DeviceDataset:
             raise ArpError("gather: window must be positive and idx non-empty")
         img = np.empty((B, T, self.res, self.res, 3), np.float32) if frames else None
         act = np.empty((B, T), np.int32)
+        if goal_index is not None:
+            gidx = np.require(np.asarray(goal_index, dtype=np.int64).reshape(-1), requirements="C")
+            if len(gidx) != B:
+                raise ArpError(f"gather: {B} indices, {len(gidx)} goal indices")
+            goal = np.empty((B, T, self.res, self.res, 3), np.float32) if frames else None
+            check(lib.arp_ds_gather_pairs_debug(self._h, _ffi.as_ptr(idx, C.c_int64), _ffi.as_ptr(gidx, C.c_int64), B, T,
+                                                None if img is None else _ffi.as_ptr(img, C.c_float), None if goal is None else _ffi.as_ptr(goal, C.c_float),
+                                                _ffi.as_ptr(act, C.c_int32)))
+            return {"action": act, "image": img, "goal": goal} if frames else {"action": act}
         has_rtg = self.dataset is None or self.dataset.use_vl
         rtg = np.empty((B, T, 1), np.float32) if has_rtg else None
         check(lib.arp_ds_gather_debug(self._h, _ffi.as_ptr(idx, C.c_int64), B, T, None if img is None else _ffi.as_ptr(img, C.c_float),
@@ -380,13 +398,22 @@ class DeviceDataset:
     def nbytes(self):
         return int(lib.arp_ds_nbytes(self._h)) if self._h else 0
 
-    def index_batches(self, batch_size, seed, epochs=None, drop_last=True, rank=0, world=1):
+    def index_batches(self, batch_size, seed, epochs=None, drop_last=True, rank=0, world=1, goal_rng=None):
         """Yields ``{"index": int64[B_global]}``: per epoch one fresh ``numpy.random.default_rng`` permutation of ``range(len(dataset))``, mapped through
         ``process_index``, cut into global batches.  NOT torch's ``DataLoader`` stream: same distribution (a uniform shuffle without replacement per
         epoch), other numbers.  ``rank`` / ``world`` only check divisibility: every rank draws the same global batch and ``shard_batch`` (what the step
-        functions and ``prefetch_to_device`` apply) cuts this rank's contiguous part, exactly as for a host batch."""
+        functions and ``prefetch_to_device`` apply) cuts this rank's contiguous part, exactly as for a host batch.
+
+        ``goal_rng`` (a ``numpy.random.RandomState``; model GCBC): yields ``{"index": int64[B], "goal_index": int64[B]}`` -- one ``dataset.goal_row`` draw
+        per batch position, in batch order, which is the order in which a sequential ``[dataset[i] for i in index]`` consumes the same generator: the same
+        seed names the same goals on both feeds.  The index stream itself is the one without ``goal_rng``."""
+        goal_row = None
+        if goal_rng is not None:
+            if self.dataset is None:
+                raise ArpError("index_batches(goal_rng=...): the hindsight draw needs the trajectory bounds of a loaded ProcgenDataset (DeviceDataset.load)")
+            goal_row = lambda i: self.dataset.goal_row(i, goal_rng)  # noqa: E731
         return index_batches(len(self.dataset) if self.dataset is not None else self.n_rows, batch_size, seed, epochs=epochs, drop_last=drop_last,
-                             rank=rank, world=world, process_index=self.dataset.process_index if self.dataset is not None else None)
+                             rank=rank, world=world, process_index=self.dataset.process_index if self.dataset is not None else None, goal_row=goal_row)
 
     def close(self):
         if getattr(self, "_h", None):
@@ -400,8 +427,9 @@ class DeviceDataset:
             pass
 
 
-def index_batches(n, batch_size, seed, epochs=None, drop_last=True, rank=0, world=1, process_index=None):
-    """The index stream of :meth:`DeviceDataset.index_batches` (needs no GPU)."""
+def index_batches(n, batch_size, seed, epochs=None, drop_last=True, rank=0, world=1, process_index=None, goal_row=None):
+    """The index stream of :meth:`DeviceDataset.index_batches` (needs no GPU).  ``goal_row``: a callable (processed row -> goal row), called once per batch
+    position in batch order as each batch is drawn; its rows go out under ``"goal_index"``."""
     B = int(batch_size)
     if B <= 0 or B % int(world) or not (0 <= int(rank) < int(world)):
         raise ValueError(f"global batch of {B} does not divide over {world} ranks (rank {rank})")
@@ -415,5 +443,8 @@ def index_batches(n, batch_size, seed, epochs=None, drop_last=True, rank=0, worl
             perm = np.asarray([process_index(int(i)) for i in perm], np.int64)
         stop = n - n % B if drop_last else n
         for lo in range(0, stop, B):
-            yield {"index": perm[lo : lo + B]}
+            if goal_row is None:
+                yield {"index": perm[lo : lo + B]}
+            else:
+                yield {"index": perm[lo : lo + B], "goal_index": np.asarray([goal_row(int(i)) for i in perm[lo : lo + B]], np.int64)}
         epoch += 1

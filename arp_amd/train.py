@@ -16,7 +16,8 @@ step counter; like the reference's donated state it is consumed by the call and 
 used.  ``batch`` keeps the reference's keys: ``batch["image"]`` holds, per image key, the frozen encoder
 output ``[B, T, tokens, dim]`` (the boundary of this round: BASELINE.json configs[3] feeds pre-computed
 encodings), ``batch["action"]`` int ``[B, T]``, ``batch["rtg"]`` per key ``[B, T, 1]`` (none for ``PolicyConfig(model="BC")``);
-``PolicyConfig(model="GCBC")`` with the frozen encoder attached reads ``batch["image"]`` and ``batch["goal"]`` frames and no rtg.
+``PolicyConfig(model="GCBC")`` with the frozen encoder attached reads ``batch["image"]`` and ``batch["goal"]`` frames and no rtg
+(or, with a device-resident dataset attached, ``{"index", "goal_index"}``: rows and goal rows, gathered on the GPU).
 All compute is in libarp_hip.so; there is no CPU fallback.
 """
 import ctypes as C
@@ -223,11 +224,17 @@ class PolicyTrainer:
         """After this call ``_stage``, ``prefetch_to_device``, ``create_train_step`` / ``create_val_step``'s step functions, ``greedy_action`` and
         ``greedy_return`` accept a batch dict whose only key is ``"index"`` (int64 row indices): HIP gather kernels build the window batch in the batch slot
         from the set in HBM.  ``use_encodings=False``: frames, through the attached encoder inside the step; ``True``: the set's cached encodings -- the
-        encodings-in step (the only way model BC trains from a file: it takes encodings)."""
+        encodings-in step (the only way model BC trains from a file: it takes encodings).  Model GCBC attaches frames only, and its batch dict has the
+        keys ``"index"`` and ``"goal_index"`` (:func:`is_index_pair_batch`): frames and goal frames are gathered by one launch, and ``prefetch_to_device``
+        runs the goal-conditioned encoder pass of the next batch beside the current step."""
         if getattr(ds, "window_size", None) is not None and ds.window_size != self.cfg.window:
             raise _ffi.ArpError(f"the dataset's window is {ds.window_size}, the handle's is {self.cfg.window}")
         if self.cfg.use_symlog:
             raise _ffi.ArpError("use_symlog: the set holds rtg / scale, not its symlog (load the set with symlog'd returns through set_labels instead)")
+        if self.gcbc and use_encodings:
+            raise _ffi.ArpError("model GCBC: attach_dataset(use_encodings=True) has nothing to gather -- the encoder reads (frame, goal) pairs and the goal is "
+                                "drawn per sample, so a pair's encoding is not a per-row quantity and there is nothing to cache; attach the frames "
+                                '(use_encodings=False) and feed {"index", "goal_index"} batches')
         if not use_encodings and getattr(self, "_encoder", None) is None:
             raise _ffi.ArpError("attach_dataset(use_encodings=False) gathers frames: attach the frozen encoder first (attach_encoder)")
         self._dataset, self._ds_use_enc = ds, bool(use_encodings)
@@ -252,6 +259,30 @@ class PolicyTrainer:
         self._inflight = getattr(self, "_inflight", {})
         self._inflight[int(slot)] = (None, None, None, len(idx))
         return not self._ds_use_enc
+
+    # -- model GCBC: (row, goal row) pairs of the attached dataset ---------------------------------------------------------------------
+    def _index_pair_args(self, index, goal_index):
+        ds, idx = self._index_args(index)
+        gidx = np.require(np.asarray(goal_index, dtype=np.int64).reshape(-1), requirements="C")
+        if len(gidx) != len(idx):
+            raise _ffi.ArpError(f"a pair batch names one goal row per row: {len(idx)} indices, {len(gidx)} goal indices")
+        return ds, idx, gidx
+
+    def set_batch_index_pairs(self, index, goal_index):
+        """Frames of the windows of ``index`` and goal frames of the windows of ``goal_index``, gathered on the GPU into the synchronous slot
+        (``arp_dt_set_batch_index_pairs``); the step then encodes the pairs at its head, as after ``set_batch_images(..., goals=)``."""
+        ds, idx, gidx = self._index_pair_args(index, goal_index)
+        check(lib.arp_dt_set_batch_index_pairs(self._h, ds._h, _ffi.as_ptr(idx, C.c_int64), _ffi.as_ptr(gidx, C.c_int64), len(idx)))
+        self._B = len(idx)
+
+    def upload_index_pairs_async(self, slot, index, goal_index):
+        """:meth:`upload_indices_async` for a pair batch: one gather launch on the handle's copy stream fills the slot's frames and goal frames.  Returns
+        True (the slot holds frames: :meth:`encode_ahead` may follow)."""
+        ds, idx, gidx = self._index_pair_args(index, goal_index)
+        check(lib.arp_dt_upload_batch_index_pairs_async(self._h, int(slot), ds._h, _ffi.as_ptr(idx, C.c_int64), _ffi.as_ptr(gidx, C.c_int64), len(idx)))
+        self._inflight = getattr(self, "_inflight", {})
+        self._inflight[int(slot)] = (None, None, None, len(idx))
+        return True
 
     def set_batch_images(self, images, action, rtg=None, goals=None):
         """Frames ``[B, T, H, W, 3]`` in front of the attached encoder.  ``goals`` (model GCBC): the hindsight goal frames, same shape; the step then encodes
@@ -301,7 +332,9 @@ class PolicyTrainer:
         if isinstance(enc, dict) and "goal" in enc:
             goals = _first_view(enc["goal"]) if self.gcbc else None  # (the reference's dataset puts "goal" in every batch; only GCBC reads it)
             enc, action, rtg = _batch_arrays(enc, self.cfg.use_symlog)
-        if is_index_batch(enc):
+        if is_index_pair_batch(enc):
+            self.set_batch_index_pairs(enc["index"], enc["goal_index"])
+        elif is_index_batch(enc):
             self.set_batch_indices(enc["index"])
         elif getattr(self, "_encoder", None) is not None and np.ndim(enc) == 5 and np.shape(enc)[-1] == 3:
             self.set_batch_images(enc, action, rtg, goals=goals)
@@ -409,6 +442,12 @@ def symlog(x):
 def is_index_batch(batch):
     """A batch that names rows of an attached device-resident dataset: a dict whose only key is ``"index"``."""
     return isinstance(batch, dict) and set(batch) == {"index"}
+
+
+def is_index_pair_batch(batch):
+    """Model GCBC's batch from the device-resident dataset: a dict with the keys ``"index"`` and ``"goal_index"`` exactly
+    (``DeviceDataset.index_batches(goal_rng=...)``)."""
+    return isinstance(batch, dict) and set(batch) == {"index", "goal_index"}
 
 
 def _first_view(v):
@@ -619,7 +658,9 @@ def prefetch_to_device(iterator, size, trainer, *, rank=0, world=1, device_axis=
                 if stop.is_set():
                     return
                 part = shard_batch(batch, rank, world, device_axis)
-                if is_index_batch(part):  # rows of the attached dataset: gathered on the GPU into the slot
+                if is_index_pair_batch(part):  # model GCBC: rows and goal rows of the attached dataset, one gather launch for both
+                    images = trainer.upload_index_pairs_async(slot, part["index"], part["goal_index"])
+                elif is_index_batch(part):  # rows of the attached dataset: gathered on the GPU into the slot
                     images = trainer.upload_indices_async(slot, part["index"])
                 else:
                     enc, act, rtg = _batch_arrays(part, trainer.cfg.use_symlog)
@@ -678,6 +719,9 @@ def _stage(tr, batch, rank, world, device_axis):
         tr.select(batch.slot)
         return batch
     part = shard_batch(batch, rank, world, device_axis)
+    if is_index_pair_batch(part):
+        tr.set_batch_index_pairs(part["index"], part["goal_index"])
+        return None
     if is_index_batch(part):
         tr.set_batch_indices(part["index"])
         return None

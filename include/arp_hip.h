@@ -450,14 +450,17 @@ int arp_dt_attach_encoder(arp_dt* h, arp_enc* enc);
 int arp_dt_set_batch_images(arp_dt* h, const float* images, const int32_t* action, const float* rtg, int B);
 /* Model GCBC's staging slot (synchronous, like arp_dt_set_batch_images): frames and goal frames, both [B,T,res,res,3] f32, and the actions; every forward /
  * train step then runs the goal-conditioned encoder pass (arp_enc_forward_gc's) first.  The goal row is drawn per sample (data_procgen.py:186-189), so the
- * encoding depends on the pair and cannot come from a per-frame cache: for this model the encoder is inside the step.  Not offered, each with an error
- * string: goal batches in the two prefetch slots (arp_dt_upload_batch_images_async) and arp_dt_encode_ahead, a goal gather from a device-resident dataset
- * (arp_dt_*_batch_indices with frames), a rollout session on a GCBC handle, and arp_dt_set_batch_images (no goals) on a GCBC handle. */
+ * encoding depends on the pair and cannot come from a per-frame cache: for this model the encoder is inside the step.  The feed that keeps frames off PCIe
+ * is the device-resident set's: arp_dt_set_batch_index_pairs / arp_dt_upload_batch_index_pairs_async (below) gather frames and goal frames into any slot, and
+ * arp_dt_encode_ahead accepts slots 0 / 1 of a GCBC handle once they hold such a batch.  Not offered, each with an error string: HOST-built goal batches in
+ * the two prefetch slots (arp_dt_upload_batch_images_async), arp_dt_encode_ahead on the synchronous slot (its step encodes it), a plain index batch
+ * (arp_dt_*_batch_indices: it names no goal rows), a GCBC encodings cache, and arp_dt_set_batch_images (no goals) on a GCBC handle. */
 int arp_dt_set_batch_images_goal(arp_dt* h, const float* images, const float* goals, const int32_t* action, int B);
 /* The encoder is frozen: batch i + 1's encodings depend on nothing step i computes.  arp_dt_encode_ahead(slot) enqueues the encoder pass of the frames in
  * batch slot `slot` (0 / 1: uploaded with arp_dt_upload_batch_images_async; 2: staged by arp_dt_set_batch_images) on the encoder's own stream NOW -- behind the
  * slot's upload and the last step that read the slot -- so that it runs beside the current step's policy part; the step that then reads the slot waits for it
- * instead of encoding.  Callable from the uploader thread.  Without it a step encodes its own batch at its head (same stream of work, same encodings). */
+ * instead of encoding.  Callable from the uploader thread.  Without it a step encodes its own batch at its head (same stream of work, same encodings).
+ * Model GCBC: slots 0 / 1 once arp_dt_upload_batch_index_pairs_async has filled them (the goal-conditioned pass); slot 2 is refused, its step encodes it. */
 int arp_dt_encode_ahead(arp_dt* h, int slot);
 
 /* ---- a demonstration set resident in HBM: policy batches from row indices -------------------------
@@ -485,6 +488,14 @@ int64_t arp_ds_nbytes(arp_ds* ds); /* HBM the handle holds */
  * [enc_tokens, enc_dim] per row) and its labels.  Every index and every geometry is checked on the host first; idx need not outlive the call. */
 int arp_dt_upload_batch_indices_async(arp_dt* h, int slot, arp_ds* ds, const int64_t* idx, int B, int use_encodings);
 int arp_dt_set_batch_indices(arp_dt* h, arp_ds* ds, const int64_t* idx, int B, int use_encodings);
+/* Model GCBC: B (row, goal row) pairs.  The goal frames of sample b are the window of row goal_idx[b] under the same rule (data_procgen.py:189: ob[g][-T:]);
+ * ONE frame-gather launch (grid z = 0 / 1) fills the slot's frames and goal frames, the actions follow idx, no return-to-go is read.  Same slots, copy stream
+ * and protocol as the two calls above.  Checked on the host before anything is enqueued: everything arp_dt_set_batch_indices checks for frames, every
+ * goal_idx[b] in [0, n_rows) (bounds only, not the hindsight rule: evaluation names goals from elsewhere), model GCBC, an attached encoder. */
+int arp_dt_upload_batch_index_pairs_async(arp_dt* h, int slot, arp_ds* ds, const int64_t* idx, const int64_t* goal_idx, int B);
+int arp_dt_set_batch_index_pairs(arp_dt* h, arp_ds* ds, const int64_t* idx, const int64_t* goal_idx, int B);
+/* Debug read-back of a pair batch: frames_out and goals_out f32 [B, window, res, res, 3], action_out int32 [B, window]; each output may be NULL. */
+int arp_ds_gather_pairs_debug(arp_ds* ds, const int64_t* idx, const int64_t* goal_idx, int B, int window, float* frames_out, float* goals_out, int32_t* action_out);
 
 /* ---- row N4: a device-resident rollout session ------------------------------------------------------
  * batch_rollout's inner loop (arp_dt/envs/rollout_procgen.py:96-166, driven by create_test_step, main_procgen.py:171-229) for n_envs independent
