@@ -1422,6 +1422,138 @@ template <typename T> int step_impl(arp_dt* c, float lr, float* aux) {
     return 0;
 }
 
+// ---- batch staging: every arp_dt_set_batch* / arp_dt_upload_batch*_async entry describes its batch as a BatchSrc and goes through stage_sync / stage_async ----
+// Where a batch of B windows comes from: host arrays, or rows of a device-resident dataset (arp_ds.hip).
+struct BatchSrc {
+    int B = 0;
+    // host arrays: encodings, or frames (the encoder-in-front boundary, row N1) with model GCBC's goal frames beside them; rtg is NULL for model BC
+    const float *enc = nullptr, *frames = nullptr, *goals = nullptr;
+    const int32_t* action = nullptr;
+    const float* rtg = nullptr;
+    // rows idx of ds: frames (img32 = lut[c][u]) or, use_encodings, the set's cached encodings, and the labels; gidx (model GCBC): the goal row of every row
+    arp_ds* ds = nullptr;
+    const int64_t *idx = nullptr, *gidx = nullptr;
+    int use_encodings = 0;
+};
+
+// The slot's buffers for B windows: frame_bytes per frame (0: encodings in, no frames), goal frames beside them, n_idx staged row indices.  A buffer that has
+// to GROW frees the old one (hipFree synchronises the device): size them once, with the largest batch.
+int size_slot(arp_dt* c, arp_dt::BatchSlot& b, int B, size_t frame_bytes, bool goals, int n_idx) {
+    const size_t R = (size_t)B * c->cfg.window;
+    ARP_TRY(b.action.ensure(R * 4));
+    if (!c->bc()) ARP_TRY(b.rtg.ensure(R * 4));  // BC.encode reads no rtg
+    ARP_TRY(b.enc32.ensure(R * c->cfg.enc_tokens * c->cfg.enc_dim * 4));  // with frames in: the encoder's output buffer
+    if (frame_bytes) ARP_TRY(b.img32.ensure(R * frame_bytes));
+    if (frame_bytes && goals) ARP_TRY(b.goal32.ensure(R * frame_bytes));
+    if (n_idx) {
+        ARP_TRY(b.idx.ensure((size_t)n_idx * 4));
+        ARP_TRY(b.idx_pin.ensure((size_t)n_idx * 4));
+    }
+    return 0;
+}
+
+// One batch into slot `si` on stream `st`: host -> device copies, or gathers from the dataset.  Every check runs on the host before anything is enqueued or
+// any slot state is touched, so a refused batch leaves the slot as it was.  Touches only the slot's own buffers (the caller may be a prefetch thread working
+// beside a running step on the other slot); the caller's idx / gidx are copied into the slot's pinned staging buffer and need not outlive the call.
+int stage_slot(arp_dt* c, int si, hipStream_t st, const BatchSrc& s) {
+    const arp_dt_cfg& k = c->cfg;
+    const int B = s.B;
+    const bool images = s.ds ? !s.use_encodings : s.frames != nullptr, goals = images && (s.ds ? s.gidx != nullptr : s.goals != nullptr);
+    const bool with_rtg = !c->bc();  // BC.encode reads no rtg (a non-NULL one is ignored)
+    if (!s.ds && !s.rtg && with_rtg) return fail("rtg is NULL (only model BC takes no return-to-go)");
+    if (s.ds && goals && !c->gcbc()) return fail("goal indices belong to model GCBC (ARP_DT_MODEL_GCBC)");
+    if (images && !c->enc)  // (never the case for model BC: arp_dt_attach_encoder refuses it)
+        return fail(!s.ds   ? "no encoder attached: call arp_dt_attach_encoder first"
+                    : goals ? "no encoder attached: index pairs gather frames and goal frames, which need arp_dt_attach_encoder first"
+                            : "no encoder attached: index batches of frames need arp_dt_attach_encoder first (or use_encodings with cached encodings)");
+    if (images && !goals && c->gcbc())  // (host frames: the synchronous entry has refused them in its own words, so this is a prefetch slot)
+        return fail(s.ds ? "model GCBC: a plain index batch names no goal rows (name them with arp_dt_set_batch_index_pairs / arp_dt_upload_batch_index_pairs_async, "
+                           "or stage frames and goals with arp_dt_set_batch_images_goal)"
+                         : "model GCBC: frames need their goal frames, and goal batches exist in the synchronous slot only (arp_dt_set_batch_images_goal)");
+    int tokens = 0, width = 0, res = 0, dev = 0;
+    if (images) ARP_TRY(enc_geometry(c->enc, &tokens, &width, &res, &dev));
+    if (s.ds) {
+        ARP_TRY(ds_check_batch(s.ds, s.idx, B, k.window, k.device, k.n_actions, with_rtg, images ? 0 : 1, res, k.enc_tokens, k.enc_dim));
+        if (goals) ARP_TRY(ds_check_goals(s.ds, s.gidx, B));
+    } else {
+        for (int i = 0; i < B * k.window; ++i)
+            if (s.action[i] < 0 || s.action[i] >= k.n_actions) return fail("action id out of range");
+    }
+    arp_dt::BatchSlot& b = c->bt[si];
+    const size_t R = (size_t)B * k.window, fb = (size_t)res * res * 3 * 4;
+    const int n_idx = s.ds ? (goals ? 2 * B : B) : 0;  // (row, goal row) pairs: [idx | goal idx], one copy
+    ARP_TRY(size_slot(c, b, B, images ? fb : 0, goals, n_idx));
+    if (s.ds) {
+        int32_t* pin = b.idx_pin.as<int32_t>();
+        for (int i = 0; i < B; ++i) {
+            pin[i] = (int32_t)s.idx[i];
+            if (goals) pin[B + i] = (int32_t)s.gidx[i];
+        }
+        ARP_HIP_OK(hipMemcpyAsync(b.idx.p, pin, (size_t)n_idx * 4, hipMemcpyHostToDevice, st));
+        // (profiled on the synchronous slot only: the profiler belongs to the compute thread, the uploader thread must not touch it)
+        hipEvent_t t0 = si == 2 && c->prof.on ? c->prof.begin(st) : nullptr;
+        const int32_t* idx = b.idx.as<int32_t>();
+        if (goals)  // ONE frame-gather launch fills img32 and goal32; the actions follow idx
+            ARP_TRY(ds_gather_pairs_on(s.ds, st, idx, idx + B, B, k.window, b.img32.as<float>(), b.goal32.as<float>(), b.action.as<int32_t>()));
+        else
+            ARP_TRY(ds_gather_on(s.ds, st, idx, B, k.window, images ? b.img32.as<float>() : nullptr, images ? nullptr : b.enc32.as<float>(), b.action.as<int32_t>(),
+                                 with_rtg ? b.rtg.as<float>() : nullptr));
+        if (t0) c->prof.end(goals ? "ds.gather_pairs" : images ? "ds.gather_frames" : "ds.gather_encodings", t0, st);
+    } else {
+        if (images) ARP_HIP_OK(hipMemcpyAsync(b.img32.p, s.frames, R * fb, hipMemcpyHostToDevice, st));
+        if (goals) ARP_HIP_OK(hipMemcpyAsync(b.goal32.p, s.goals, R * fb, hipMemcpyHostToDevice, st));
+        if (!images) ARP_HIP_OK(hipMemcpyAsync(b.enc32.p, s.enc, R * k.enc_tokens * k.enc_dim * 4, hipMemcpyHostToDevice, st));
+        ARP_HIP_OK(hipMemcpyAsync(b.action.p, s.action, R * 4, hipMemcpyHostToDevice, st));
+        if (with_rtg) ARP_HIP_OK(hipMemcpyAsync(b.rtg.p, s.rtg, R * 4, hipMemcpyHostToDevice, st));
+    }
+    b.B = B;
+    b.images = images;
+    b.goals = goals;
+    return 0;
+}
+
+// The synchronous protocol: slot 2, on the compute stream.  A refused batch leaves the slot that was selected selected, and its contents usable.
+int stage_sync(arp_dt* c, const BatchSrc& s) {
+    ARP_HIP_OK(hipSetDevice(c->cfg.device));
+    arp_dt::BatchSlot& b = c->bt[2];
+    if (b.enc_ahead && c->enc_stream) ARP_HIP_OK(hipStreamSynchronize(c->enc_stream));  // (an encode-ahead pass still reading / writing the buffers about to be filled)
+    ARP_TRY(stage_slot(c, 2, c->stream, s));
+    c->cur = 2;
+    b.enc_ahead = false;
+    ARP_TRY(ensure_buffers(c, s.B));
+    ARP_HIP_OK(hipStreamSynchronize(c->stream));
+    c->use_images = b.images;
+    return 0;
+}
+
+// The asynchronous protocol: slot 0 / 1 on the handle's COPY stream -- main_procgen.py:703's prefetch_to_device(..., 2).  Returns once the copies or gathers
+// are enqueued (from pageable host memory: once they are staged); never touches the slot a running step reads, so it may be called from another host thread
+// while arp_dt_train_step runs.  arp_dt_select_batch / arp_dt_encode_ahead order the step and the encoder behind `up`.
+int stage_async(arp_dt* c, int slot, const BatchSrc& s) {
+    ARP_HIP_OK(hipSetDevice(c->cfg.device));
+    arp_dt::BatchSlot& b = c->bt[slot];
+    // Behind the slot's last reader: a HOST-side wait on the event that step recorded (already complete when the caller follows
+    // prefetch_to_device's protocol: a slot is handed back after its step's aux was read).  Not a stream-side wait: from this thread
+    // hipStreamWaitEvent on an event of a stream that is being captured is refused, and a pageable upload queued behind a pending
+    // stream wait ran 4x slower (7.8 ms instead of 1.8 ms per 101 MB).
+    // Never beside a graph capture on the compute thread (fwd_bwd_graphed): HIP refuses hipEventSynchronize on an event whose stream is
+    // capturing at that moment -- even one recorded long before the capture began -- and that refusal also invalidates the capture.
+    std::lock_guard<std::mutex> capture_lock(c->capture_mu);
+    if (b.used) ARP_HIP_OK(hipEventSynchronize(b.use));
+    if (b.up_recorded) ARP_HIP_OK(hipEventSynchronize(b.up));  // (the copy that last read this slot's pinned staging buffer)
+    if (b.enc_ahead && b.enc_done) ARP_HIP_OK(hipEventSynchronize(b.enc_done));  // (an encode-ahead pass nobody consumed still writes enc32 / reads img32, goal32)
+    // ONE copy stream for both slots (round 6; two until then): the uploads share the PCIe link anyway, and every stream of a process is a hardware queue -- with
+    // the two copy streams the encoder-inside step held five (compute, 2 x copy, encoder, encoder part) and ran 10.3 -> 11.9 ms per step when the fifth queue came
+    // to share a dispatch pipe with a busy one (profiles/r6_n1_flow.txt: same box, GPU_MAX_HW_QUEUES 4 / 8 / 16 and creation orders); four is what the chip runs side by side
+    if (!c->copy_stream) ARP_TRY(c->copy_stream.create());
+    ARP_TRY(stage_slot(c, slot, c->copy_stream, s));
+    ARP_HIP_OK(hipEventRecord(b.up, c->copy_stream));
+    b.up_pending = true;
+    b.up_recorded = true;
+    b.enc_ahead = false;  // (new frames: whatever enc32 holds belongs to the batch before)
+    return 0;
+}
+
 }  // namespace
 
 // =================================== C ABI ===============================================================
@@ -1579,90 +1711,54 @@ int arp_dt_get_step(arp_dt* c, int64_t* step) {
     return 0;
 }
 
-// Host -> device copy of one batch into slot `si` on stream `st`.  Touches only the slot's own buffers (the caller may be a
-// prefetch thread working beside a running step on the other slot); frames != nullptr: the encoder-in-front boundary (row N1).
-static int stage_slot(arp_dt* c, int si, hipStream_t st, const float* enc, const float* frames, const int32_t* action, const float* rtg, int B,
-                      const float* goals = nullptr) {
-    const int R = B * c->cfg.window;
-    for (int i = 0; i < R; ++i)
-        if (action[i] < 0 || action[i] >= c->cfg.n_actions) return fail("action id out of range");
-    arp_dt::BatchSlot& b = c->bt[si];
-    ARP_TRY(b.action.ensure((size_t)R * 4));
-    const bool with_rtg = !c->bc();  // BC.encode reads no rtg (a non-NULL one is ignored)
-    if (with_rtg) ARP_TRY(b.rtg.ensure((size_t)R * 4));
-    const size_t Mx = (size_t)R * c->cfg.enc_tokens;
-    ARP_TRY(b.enc32.ensure(Mx * c->cfg.enc_dim * 4));  // with frames in: the encoder's output buffer
-    if (frames) {
-        int tokens = 0, width = 0, res = 0, dev = 0;
-        ARP_TRY(enc_geometry(c->enc, &tokens, &width, &res, &dev));
-        const size_t fb = (size_t)res * res * 3 * 4;
-        ARP_TRY(b.img32.ensure((size_t)R * fb));
-        ARP_HIP_OK(hipMemcpyAsync(b.img32.p, frames, (size_t)R * fb, hipMemcpyHostToDevice, st));
-        if (goals) {
-            ARP_TRY(b.goal32.ensure((size_t)R * fb));
-            ARP_HIP_OK(hipMemcpyAsync(b.goal32.p, goals, (size_t)R * fb, hipMemcpyHostToDevice, st));
-        }
-    } else {
-        ARP_HIP_OK(hipMemcpyAsync(b.enc32.p, enc, Mx * c->cfg.enc_dim * 4, hipMemcpyHostToDevice, st));
-    }
-    ARP_HIP_OK(hipMemcpyAsync(b.action.p, action, (size_t)R * 4, hipMemcpyHostToDevice, st));
-    if (with_rtg) ARP_HIP_OK(hipMemcpyAsync(b.rtg.p, rtg, (size_t)R * 4, hipMemcpyHostToDevice, st));
-    b.B = B;
-    b.images = frames != nullptr;
-    b.goals = frames != nullptr && goals != nullptr;
-    return 0;
-}
-
+// The eight batch entries: their own argument checks, then the one synchronous (slot 2) or asynchronous (slot 0 / 1) protocol -- stage_sync / stage_async.
 int arp_dt_set_batch(arp_dt* c, const float* enc, const int32_t* action, const float* rtg, int B) {
     if (!c || !enc || !action || B <= 0) return fail("bad argument");
-    if (!rtg && !c->bc()) return fail("rtg is NULL (only model BC takes no return-to-go)");
-    ARP_HIP_OK(hipSetDevice(c->cfg.device));
-    c->cur = 2;  // the synchronous slot
-    if (c->bt[2].enc_ahead && c->enc_stream) ARP_HIP_OK(hipStreamSynchronize(c->enc_stream));  // (an encode-ahead pass still writing the buffer about to be filled)
-    c->bt[2].enc_ahead = false;
-    ARP_TRY(stage_slot(c, 2, c->stream, enc, nullptr, action, rtg, B));
-    ARP_TRY(ensure_buffers(c, B));
-    c->use_images = false;
-    ARP_HIP_OK(hipStreamSynchronize(c->stream));
-    return 0;
+    return stage_sync(c, {.B = B, .enc = enc, .action = action, .rtg = rtg});
 }
 
-// Asynchronous upload of a batch into slot 0 / 1 on the handle's COPY stream -- main_procgen.py:703's prefetch_to_device(..., 2).
-// Returns once the copies are enqueued (from pageable host memory: once they are staged); never touches the slot a running step
-// reads, so it may be called from another host thread while arp_dt_train_step runs.  The copy waits (on the GPU) for the last
-// step that read this slot; arp_dt_select_batch makes the compute stream wait for the copy.
-static int upload_async(arp_dt* c, int slot, const float* enc, const float* frames, const int32_t* action, const float* rtg, int B) {
-    if (!c || (!enc && !frames) || !action || B <= 0 || slot < 0 || slot > 1) return fail("bad argument");
-    if (!rtg && !c->bc()) return fail("rtg is NULL (only model BC takes no return-to-go)");
-    if (frames && !c->enc) return fail("no encoder attached: call arp_dt_attach_encoder first");
-    if (frames && c->gcbc()) return fail("model GCBC: frames need their goal frames, and goal batches exist in the synchronous slot only (arp_dt_set_batch_images_goal)");
-    ARP_HIP_OK(hipSetDevice(c->cfg.device));
-    arp_dt::BatchSlot& b = c->bt[slot];
-    // Behind the slot's last reader: a HOST-side wait on the event that step recorded (already complete when the caller follows
-    // prefetch_to_device's protocol: a slot is handed back after its step's aux was read).  Not a stream-side wait: from this thread
-    // hipStreamWaitEvent on an event of a stream that is being captured is refused, and a pageable upload queued behind a pending
-    // stream wait ran 4x slower (7.8 ms instead of 1.8 ms per 101 MB).
-    // Never beside a graph capture on the compute thread (fwd_bwd_graphed): HIP refuses hipEventSynchronize on an event whose stream is
-    // capturing at that moment -- even one recorded long before the capture began -- and that refusal also invalidates the capture.
-    std::lock_guard<std::mutex> capture_lock(c->capture_mu);
-    if (b.used) ARP_HIP_OK(hipEventSynchronize(b.use));
-    // a slot that has to GROW frees its old buffers (hipFree synchronises the device): size them once, with the largest batch
-    // ONE copy stream for both slots (round 6; two until then): the uploads share the PCIe link anyway, and every stream of a process is a hardware queue -- with
-    // the two copy streams the encoder-inside step held five (compute, 2 x copy, encoder, encoder part) and ran 10.3 -> 11.9 ms per step when the fifth queue came
-    // to share a dispatch pipe with a busy one (profiles/r6_n1_flow.txt: same box, GPU_MAX_HW_QUEUES 4 / 8 / 16 and creation orders); four is what the chip runs side by side
-    if (!c->copy_stream) ARP_TRY(c->copy_stream.create());
-    ARP_TRY(stage_slot(c, slot, c->copy_stream, enc, frames, action, rtg, B));
-    ARP_HIP_OK(hipEventRecord(b.up, c->copy_stream));
-    b.up_pending = true;
-    b.up_recorded = true;
-    b.enc_ahead = false;  // (new frames: whatever enc32 holds belongs to the batch before)
-    return 0;
+int arp_dt_set_batch_images(arp_dt* c, const float* images, const int32_t* action, const float* rtg, int B) {
+    if (c && c->gcbc()) return fail("model GCBC encodes (frame, goal) pairs: stage frames and goals with arp_dt_set_batch_images_goal");
+    if (!c || !images || !action || !rtg || B <= 0) return fail("bad argument");
+    return stage_sync(c, {.B = B, .frames = images, .action = action, .rtg = rtg});
 }
+
+// Model GCBC: frames and goal frames, both [B, T, res, res, 3] f32, and the actions; the step then runs the goal-conditioned encoder pass
+// (enc_forward_gc_on) where an ARP-DT step runs enc_forward_on.
+int arp_dt_set_batch_images_goal(arp_dt* c, const float* images, const float* goals, const int32_t* action, int B) {
+    if (!c || !images || !goals || !action || B <= 0) return fail("bad argument");
+    if (!c->gcbc()) return fail("goal frames belong to model GCBC (ARP_DT_MODEL_GCBC)");
+    return stage_sync(c, {.B = B, .frames = images, .goals = goals, .action = action});
+}
+
+int arp_dt_set_batch_indices(arp_dt* c, arp_ds* ds, const int64_t* idx, int B, int use_encodings) {
+    if (!c || !ds || !idx || B <= 0) return fail("bad argument");
+    return stage_sync(c, {.B = B, .ds = ds, .idx = idx, .use_encodings = use_encodings});
+}
+
+int arp_dt_set_batch_index_pairs(arp_dt* c, arp_ds* ds, const int64_t* idx, const int64_t* goal_idx, int B) {
+    if (!c || !ds || !idx || !goal_idx || B <= 0) return fail("bad argument");
+    return stage_sync(c, {.B = B, .ds = ds, .idx = idx, .gidx = goal_idx});
+}
+
 int arp_dt_upload_batch_async(arp_dt* c, int slot, const float* enc, const int32_t* action, const float* rtg, int B) {
-    return upload_async(c, slot, enc, nullptr, action, rtg, B);
+    if (!c || !enc || !action || B <= 0 || slot < 0 || slot > 1) return fail("bad argument");
+    return stage_async(c, slot, {.B = B, .enc = enc, .action = action, .rtg = rtg});
 }
+
 int arp_dt_upload_batch_images_async(arp_dt* c, int slot, const float* images, const int32_t* action, const float* rtg, int B) {
-    return upload_async(c, slot, nullptr, images, action, rtg, B);
+    if (!c || !images || !action || B <= 0 || slot < 0 || slot > 1) return fail("bad argument");
+    return stage_async(c, slot, {.B = B, .frames = images, .action = action, .rtg = rtg});
+}
+
+int arp_dt_upload_batch_indices_async(arp_dt* c, int slot, arp_ds* ds, const int64_t* idx, int B, int use_encodings) {
+    if (!c || !ds || !idx || B <= 0 || slot < 0 || slot > 1) return fail("bad argument");
+    return stage_async(c, slot, {.B = B, .ds = ds, .idx = idx, .use_encodings = use_encodings});
+}
+
+int arp_dt_upload_batch_index_pairs_async(arp_dt* c, int slot, arp_ds* ds, const int64_t* idx, const int64_t* goal_idx, int B) {
+    if (!c || !ds || !idx || !goal_idx || B <= 0 || slot < 0 || slot > 1) return fail("bad argument");
+    return stage_async(c, slot, {.B = B, .ds = ds, .idx = idx, .gidx = goal_idx});
 }
 
 // The next forward / step reads slot `slot` (compute stream ordered behind the slot's upload).
@@ -1681,141 +1777,6 @@ int arp_dt_select_batch(arp_dt* c, int slot) {
     return 0;
 }
 
-// A batch named by B row indices of a device-resident dataset (arp_ds.hip) into slot `si`, gathered on stream `st`: frames (use_encodings == 0: the encoder-inside
-// boundary, img32 = lut[c][u]) or cached encodings (enc32), and the labels.  Every check runs on the host before anything is enqueued; the caller's idx is
-// copied into the slot's pinned staging buffer and need not outlive the call.
-static int stage_slot_indices(arp_dt* c, int si, hipStream_t st, arp_ds* ds, const int64_t* idx, int B, int use_encodings) {
-    const arp_dt_cfg& k = c->cfg;
-    int tokens = k.enc_tokens, width = k.enc_dim, res = 0, dev = k.device;
-    if (!use_encodings) {
-        if (!c->enc) return fail("no encoder attached: index batches of frames need arp_dt_attach_encoder first (or use_encodings with cached encodings)");
-        if (c->gcbc())
-            return fail("model GCBC: a plain index batch names no goal rows (name them with arp_dt_set_batch_index_pairs / arp_dt_upload_batch_index_pairs_async, "
-                        "or stage frames and goals with arp_dt_set_batch_images_goal)");
-        ARP_TRY(enc_geometry(c->enc, &tokens, &width, &res, &dev));
-    }
-    const bool with_rtg = !c->bc();
-    ARP_TRY(ds_check_batch(ds, idx, B, k.window, k.device, k.n_actions, with_rtg, use_encodings ? 1 : 0, res, k.enc_tokens, k.enc_dim));
-    arp_dt::BatchSlot& b = c->bt[si];
-    const size_t R = (size_t)B * k.window;
-    ARP_TRY(b.action.ensure(R * 4));
-    if (with_rtg) ARP_TRY(b.rtg.ensure(R * 4));
-    ARP_TRY(b.enc32.ensure(R * k.enc_tokens * k.enc_dim * 4));  // with frames in: the encoder's output buffer
-    if (!use_encodings) ARP_TRY(b.img32.ensure(R * res * res * 3 * 4));
-    ARP_TRY(b.idx.ensure((size_t)B * 4));
-    ARP_TRY(b.idx_pin.ensure((size_t)B * 4));
-    for (int i = 0; i < B; ++i) b.idx_pin.as<int32_t>()[i] = (int32_t)idx[i];
-    ARP_HIP_OK(hipMemcpyAsync(b.idx.p, b.idx_pin.p, (size_t)B * 4, hipMemcpyHostToDevice, st));
-    // (profiled on the synchronous slot only: the profiler belongs to the compute thread, the uploader thread must not touch it)
-    hipEvent_t t0 = si == 2 && c->prof.on ? c->prof.begin(st) : nullptr;
-    ARP_TRY(ds_gather_on(ds, st, b.idx.as<int32_t>(), B, k.window, use_encodings ? nullptr : b.img32.as<float>(), use_encodings ? b.enc32.as<float>() : nullptr,
-                         b.action.as<int32_t>(), with_rtg ? b.rtg.as<float>() : nullptr));
-    if (t0) c->prof.end(use_encodings ? "ds.gather_encodings" : "ds.gather_frames", t0, st);
-    b.B = B;
-    b.images = !use_encodings;
-    b.goals = false;
-    return 0;
-}
-
-// arp_dt_upload_batch*_async for a batch of row indices: same slots, same copy stream, same protocol (upload_async) -- the host waits for the slot's last
-// reader under the capture lock, `up` is recorded behind the gathers, arp_dt_select_batch / arp_dt_encode_ahead order the step and the encoder behind it.
-int arp_dt_upload_batch_indices_async(arp_dt* c, int slot, arp_ds* ds, const int64_t* idx, int B, int use_encodings) {
-    if (!c || !ds || !idx || B <= 0 || slot < 0 || slot > 1) return fail("bad argument");
-    ARP_HIP_OK(hipSetDevice(c->cfg.device));
-    arp_dt::BatchSlot& b = c->bt[slot];
-    std::lock_guard<std::mutex> capture_lock(c->capture_mu);
-    if (b.used) ARP_HIP_OK(hipEventSynchronize(b.use));
-    if (b.up_recorded) ARP_HIP_OK(hipEventSynchronize(b.up));  // (the copy that last read this slot's pinned staging buffer)
-    if (b.enc_ahead && b.enc_done) ARP_HIP_OK(hipEventSynchronize(b.enc_done));  // (an encode-ahead pass nobody consumed still writes enc32 / reads img32)
-    if (!c->copy_stream) ARP_TRY(c->copy_stream.create());
-    ARP_TRY(stage_slot_indices(c, slot, c->copy_stream, ds, idx, B, use_encodings));
-    ARP_HIP_OK(hipEventRecord(b.up, c->copy_stream));
-    b.up_pending = true;
-    b.up_recorded = true;
-    b.enc_ahead = false;
-    return 0;
-}
-
-// The synchronous form (slot 2, the compute stream), as arp_dt_set_batch / arp_dt_set_batch_images.
-int arp_dt_set_batch_indices(arp_dt* c, arp_ds* ds, const int64_t* idx, int B, int use_encodings) {
-    if (!c || !ds || !idx || B <= 0) return fail("bad argument");
-    ARP_HIP_OK(hipSetDevice(c->cfg.device));
-    if (c->bt[2].enc_ahead && c->enc_stream) ARP_HIP_OK(hipStreamSynchronize(c->enc_stream));
-    ARP_TRY(stage_slot_indices(c, 2, c->stream, ds, idx, B, use_encodings));  // (a refused batch leaves the staged one selected)
-    c->cur = 2;
-    c->bt[2].enc_ahead = false;
-    ARP_TRY(ensure_buffers(c, B));
-    ARP_HIP_OK(hipStreamSynchronize(c->stream));
-    c->use_images = !use_encodings;
-    return 0;
-}
-
-// Model GCBC from the device-resident set: B (row, goal row) pairs into slot `si`.  stage_slot_indices with a second index array: both go through the slot's
-// pinned staging ([idx | goal_idx], one copy) into b.idx, ONE frame-gather launch fills img32 and goal32 (ds_gather_pairs_on), the actions follow idx.
-// Every check runs on the host before anything is enqueued.
-static int stage_slot_index_pairs(arp_dt* c, int si, hipStream_t st, arp_ds* ds, const int64_t* idx, const int64_t* gidx, int B) {
-    const arp_dt_cfg& k = c->cfg;
-    if (!c->gcbc()) return fail("goal indices belong to model GCBC (ARP_DT_MODEL_GCBC)");
-    if (!c->enc) return fail("no encoder attached: index pairs gather frames and goal frames, which need arp_dt_attach_encoder first");
-    int tokens = 0, width = 0, res = 0, dev = k.device;
-    ARP_TRY(enc_geometry(c->enc, &tokens, &width, &res, &dev));
-    ARP_TRY(ds_check_batch(ds, idx, B, k.window, k.device, k.n_actions, false, 0, res, k.enc_tokens, k.enc_dim));
-    ARP_TRY(ds_check_goals(ds, gidx, B));
-    arp_dt::BatchSlot& b = c->bt[si];
-    const size_t R = (size_t)B * k.window, fb = (size_t)res * res * 3 * 4;
-    ARP_TRY(b.action.ensure(R * 4));
-    ARP_TRY(b.enc32.ensure(R * k.enc_tokens * k.enc_dim * 4));  // the encoder's output buffer
-    ARP_TRY(b.img32.ensure(R * fb));
-    ARP_TRY(b.goal32.ensure(R * fb));
-    ARP_TRY(b.idx.ensure((size_t)B * 8));
-    ARP_TRY(b.idx_pin.ensure((size_t)B * 8));
-    for (int i = 0; i < B; ++i) {
-        b.idx_pin.as<int32_t>()[i] = (int32_t)idx[i];
-        b.idx_pin.as<int32_t>()[B + i] = (int32_t)gidx[i];
-    }
-    ARP_HIP_OK(hipMemcpyAsync(b.idx.p, b.idx_pin.p, (size_t)B * 8, hipMemcpyHostToDevice, st));
-    hipEvent_t t0 = si == 2 && c->prof.on ? c->prof.begin(st) : nullptr;  // (the synchronous slot only, as stage_slot_indices)
-    ARP_TRY(ds_gather_pairs_on(ds, st, b.idx.as<int32_t>(), b.idx.as<int32_t>() + B, B, k.window, b.img32.as<float>(), b.goal32.as<float>(), b.action.as<int32_t>()));
-    if (t0) c->prof.end("ds.gather_pairs", t0, st);
-    b.B = B;
-    b.images = true;
-    b.goals = true;
-    return 0;
-}
-
-// arp_dt_upload_batch_indices_async for (row, goal row) pairs: same slots, same copy stream, same protocol.  The encode-ahead pass nobody consumed reads
-// goal32 too, so the same host wait on enc_done covers it.
-int arp_dt_upload_batch_index_pairs_async(arp_dt* c, int slot, arp_ds* ds, const int64_t* idx, const int64_t* goal_idx, int B) {
-    if (!c || !ds || !idx || !goal_idx || B <= 0 || slot < 0 || slot > 1) return fail("bad argument");
-    ARP_HIP_OK(hipSetDevice(c->cfg.device));
-    arp_dt::BatchSlot& b = c->bt[slot];
-    std::lock_guard<std::mutex> capture_lock(c->capture_mu);
-    if (b.used) ARP_HIP_OK(hipEventSynchronize(b.use));
-    if (b.up_recorded) ARP_HIP_OK(hipEventSynchronize(b.up));
-    if (b.enc_ahead && b.enc_done) ARP_HIP_OK(hipEventSynchronize(b.enc_done));
-    if (!c->copy_stream) ARP_TRY(c->copy_stream.create());
-    ARP_TRY(stage_slot_index_pairs(c, slot, c->copy_stream, ds, idx, goal_idx, B));
-    ARP_HIP_OK(hipEventRecord(b.up, c->copy_stream));
-    b.up_pending = true;
-    b.up_recorded = true;
-    b.enc_ahead = false;
-    return 0;
-}
-
-// The synchronous form (slot 2, the compute stream), as arp_dt_set_batch_indices.
-int arp_dt_set_batch_index_pairs(arp_dt* c, arp_ds* ds, const int64_t* idx, const int64_t* goal_idx, int B) {
-    if (!c || !ds || !idx || !goal_idx || B <= 0) return fail("bad argument");
-    ARP_HIP_OK(hipSetDevice(c->cfg.device));
-    if (c->bt[2].enc_ahead && c->enc_stream) ARP_HIP_OK(hipStreamSynchronize(c->enc_stream));
-    ARP_TRY(stage_slot_index_pairs(c, 2, c->stream, ds, idx, goal_idx, B));  // (a refused batch leaves the staged one selected)
-    c->cur = 2;
-    c->bt[2].enc_ahead = false;
-    ARP_TRY(ensure_buffers(c, B));
-    ARP_HIP_OK(hipStreamSynchronize(c->stream));
-    c->use_images = true;
-    return 0;
-}
-
 int arp_dt_attach_encoder(arp_dt* c, arp_enc* enc) {
     if (!c || !enc) return fail("null argument");
     // The reference's InstructRL encoder sees the BERT-tokenized instruction beside the frame (BC.py:286-321: 1 + 256 + 77 tokens); this encoder is
@@ -1828,35 +1789,6 @@ int arp_dt_attach_encoder(arp_dt* c, arp_enc* enc) {
     if (tokens != c->cfg.enc_tokens || width != c->cfg.enc_dim) return fail("encoder geometry does not match enc_tokens / enc_dim");
     if (dev != c->cfg.device) return fail("encoder lives on another device");
     c->enc = enc;
-    return 0;
-}
-
-static int set_batch_frames(arp_dt* c, const float* images, const float* goals, const int32_t* action, const float* rtg, int B);
-
-int arp_dt_set_batch_images(arp_dt* c, const float* images, const int32_t* action, const float* rtg, int B) {
-    if (c && c->gcbc()) return fail("model GCBC encodes (frame, goal) pairs: stage frames and goals with arp_dt_set_batch_images_goal");
-    if (!c || !images || !action || !rtg || B <= 0) return fail("bad argument");
-    return set_batch_frames(c, images, nullptr, action, rtg, B);
-}
-
-// Model GCBC's synchronous staging slot: frames and goal frames, both [B, T, res, res, 3] f32, and the actions; the step then runs the goal-conditioned
-// encoder pass (enc_forward_gc_on) where an ARP-DT step runs enc_forward_on.
-int arp_dt_set_batch_images_goal(arp_dt* c, const float* images, const float* goals, const int32_t* action, int B) {
-    if (!c || !images || !goals || !action || B <= 0) return fail("bad argument");
-    if (!c->gcbc()) return fail("goal frames belong to model GCBC (ARP_DT_MODEL_GCBC)");
-    return set_batch_frames(c, images, goals, action, nullptr, B);
-}
-
-static int set_batch_frames(arp_dt* c, const float* images, const float* goals, const int32_t* action, const float* rtg, int B) {
-    if (!c->enc) return fail("no encoder attached: call arp_dt_attach_encoder first");  // (never the case for model BC: arp_dt_attach_encoder refuses it)
-    ARP_HIP_OK(hipSetDevice(c->cfg.device));
-    c->cur = 2;  // the synchronous slot
-    if (c->bt[2].enc_ahead && c->enc_stream) ARP_HIP_OK(hipStreamSynchronize(c->enc_stream));  // (an encode-ahead pass still reading the frames about to be replaced)
-    c->bt[2].enc_ahead = false;
-    ARP_TRY(stage_slot(c, 2, c->stream, nullptr, images, action, rtg, B, goals));
-    ARP_TRY(ensure_buffers(c, B));
-    ARP_HIP_OK(hipStreamSynchronize(c->stream));
-    c->use_images = true;
     return 0;
 }
 
@@ -1898,9 +1830,7 @@ int dt_rollout_bind(arp_dt* c, int B, float** enc32, int32_t** action, float** r
     const size_t R = (size_t)B * c->cfg.window;
     if (b.enc32.bytes < R * c->cfg.enc_tokens * c->cfg.enc_dim * 4 || b.action.bytes < R * 4 || (!c->bc() && b.rtg.bytes < R * 4))
         ARP_HIP_OK(hipStreamSynchronize(c->stream));  // (the buffers grow: nothing queued may still read the old ones)
-    ARP_TRY(b.action.ensure(R * 4));
-    if (!c->bc()) ARP_TRY(b.rtg.ensure(R * 4));
-    ARP_TRY(b.enc32.ensure(R * c->cfg.enc_tokens * c->cfg.enc_dim * 4));
+    ARP_TRY(size_slot(c, b, B, 0, false, 0));  // encodings in: the session writes them itself
     b.B = B;
     b.images = false;
     ARP_TRY(ensure_buffers(c, B));

@@ -95,6 +95,11 @@ class PolicyTrainer:
         h = C.c_void_p()
         check(lib.arp_dt_create(C.byref(c), C.byref(h)))
         self._h = h
+        self._B = 0                    # windows in the batch the next forward / step reads
+        self._inflight = {}            # slot -> (arrays of an upload, kept alive until the slot is refilled, ..., B)
+        self._encoder = None           # attach_encoder
+        self._dataset, self._ds_use_enc = None, False  # attach_dataset
+        self._prefetch_owner = None    # prefetch_to_device: the live prefetcher that owns slots 0 / 1
         # None: the library's default -- ON in f16 mode where the corrected products exist (enc_dim a multiple of 256, >= 512), since round 6
         if adapter_corrections is not None:
             check(lib.arp_dt_set_adapter_corrections(h, int(bool(adapter_corrections))))
@@ -167,33 +172,34 @@ class PolicyTrainer:
             raise ValueError(f"batch shapes: rtg {rtg.shape}, expected {B * T} values")
         return rtg, _ffi.as_ptr(rtg, C.c_float)
 
-    def set_batch(self, enc, action, rtg=None):
-        enc = np.require(np.asarray(enc, dtype=np.float32), requirements="C")
-        action = np.require(np.asarray(action, dtype=np.int32), requirements="C")
-        B, T = action.shape
-        if enc.shape != (B, T, self.cfg.enc_tokens, self.cfg.enc_dim) or T != self.cfg.window:
-            raise ValueError(f"batch shapes: enc {enc.shape}, action {action.shape}")
-        rtg, rp = self._rtg(rtg, B, T)
-        check(lib.arp_dt_set_batch(self._h, _ffi.as_ptr(enc, C.c_float), _ffi.as_ptr(action, C.c_int32), rp, B))
-        self._B = B
-
-    # -- two device-resident batch slots: the reference's prefetch_to_device(..., 2) (main_procgen.py:703) ----------------------
-    def upload_async(self, slot, enc, action, rtg=None, images=False, goals=None):
-        """Enqueue the host -> device copy of a batch into slot 0 / 1 on the handle's copy stream.  Safe to call from another
-        thread while :meth:`train_step` runs on the other slot.  The arrays must stay alive until :meth:`select` (kept here).
-        ``goals``: refused -- goal batches (model GCBC) exist in the synchronous slot only (:meth:`set_batch_images`)."""
-        if goals is not None:
-            raise _ffi.ArpError("goal batches exist in the synchronous slot only: set_batch_images(images, action, goals=goals) (no prefetch slot, no encode_ahead)")
+    # -- batches: the synchronous slot, and two prefetch slots -- the reference's prefetch_to_device(..., 2) (main_procgen.py:703) ---------
+    def _stage_host(self, slot, enc, action, rtg, images=False):
+        """Host arrays -- encodings, or with ``images`` frames -- into the synchronous slot (``slot`` None) or into prefetch slot 0 / 1."""
         enc = np.require(np.asarray(enc, dtype=np.float32), requirements="C")
         action = np.require(np.asarray(action, dtype=np.int32), requirements="C")
         B, T = action.shape
         if T != self.cfg.window or (not images and enc.shape != (B, T, self.cfg.enc_tokens, self.cfg.enc_dim)):
             raise ValueError(f"batch shapes: enc {enc.shape}, action {action.shape}")
         rtg, rp = self._rtg(rtg, B, T)
-        fn = lib.arp_dt_upload_batch_images_async if images else lib.arp_dt_upload_batch_async
-        check(fn(self._h, int(slot), _ffi.as_ptr(enc, C.c_float), _ffi.as_ptr(action, C.c_int32), rp, B))
-        self._inflight = getattr(self, "_inflight", {})
-        self._inflight[int(slot)] = (enc, action, rtg, B)
+        args = (_ffi.as_ptr(enc, C.c_float), _ffi.as_ptr(action, C.c_int32), rp, B)
+        if slot is None:
+            check(lib.arp_dt_set_batch(self._h, *args))
+            self._B = B
+        else:
+            fn = lib.arp_dt_upload_batch_images_async if images else lib.arp_dt_upload_batch_async
+            check(fn(self._h, slot, *args))
+            self._inflight[slot] = (enc, action, rtg, B)
+
+    def set_batch(self, enc, action, rtg=None):
+        self._stage_host(None, enc, action, rtg)
+
+    def upload_async(self, slot, enc, action, rtg=None, images=False, goals=None):
+        """Enqueue the host -> device copy of a batch into slot 0 / 1 on the handle's copy stream.  Safe to call from another
+        thread while :meth:`train_step` runs on the other slot.  The arrays must stay alive until :meth:`select` (kept here).
+        ``goals``: refused -- goal batches (model GCBC) exist in the synchronous slot only (:meth:`set_batch_images`)."""
+        if goals is not None:
+            raise _ffi.ArpError("goal batches exist in the synchronous slot only: set_batch_images(images, action, goals=goals) (no prefetch slot, no encode_ahead)")
+        self._stage_host(int(slot), enc, action, rtg, images)
 
     def encode_ahead(self, slot):
         """Enqueue the frozen encoder's pass for the frames in batch slot ``slot`` now, on the encoder's own stream, so that it runs beside the current step's
@@ -235,78 +241,91 @@ class PolicyTrainer:
             raise _ffi.ArpError("model GCBC: attach_dataset(use_encodings=True) has nothing to gather -- the encoder reads (frame, goal) pairs and the goal is "
                                 "drawn per sample, so a pair's encoding is not a per-row quantity and there is nothing to cache; attach the frames "
                                 '(use_encodings=False) and feed {"index", "goal_index"} batches')
-        if not use_encodings and getattr(self, "_encoder", None) is None:
+        if not use_encodings and self._encoder is None:
             raise _ffi.ArpError("attach_dataset(use_encodings=False) gathers frames: attach the frozen encoder first (attach_encoder)")
         self._dataset, self._ds_use_enc = ds, bool(use_encodings)
         ds._trainers.add(self)
 
-    def _index_args(self, index):
-        ds = getattr(self, "_dataset", None)
+    def _stage_indices(self, slot, index, goal_index=None):
+        """Rows (and, model GCBC, goal rows) of the attached dataset into the synchronous slot (``slot`` None) or into prefetch slot 0 / 1, gathered on the
+        GPU.  Returns whether the slot now holds frames."""
+        ds = self._dataset
         if ds is None:
             raise _ffi.ArpError('a batch of row indices ({"index": ...}) needs attach_dataset first')
         idx = np.require(np.asarray(index, dtype=np.int64).reshape(-1), requirements="C")
-        return ds, idx
+        pairs, B = goal_index is not None, len(idx)
+        if pairs:
+            gidx = np.require(np.asarray(goal_index, dtype=np.int64).reshape(-1), requirements="C")
+            if len(gidx) != B:
+                raise _ffi.ArpError(f"a pair batch names one goal row per row: {B} indices, {len(gidx)} goal indices")
+            args = (ds._h, _ffi.as_ptr(idx, C.c_int64), _ffi.as_ptr(gidx, C.c_int64), B)
+        else:
+            args = (ds._h, _ffi.as_ptr(idx, C.c_int64), B, int(self._ds_use_enc))
+        if slot is None:
+            check((lib.arp_dt_set_batch_index_pairs if pairs else lib.arp_dt_set_batch_indices)(self._h, *args))
+            self._B = B
+        else:
+            check((lib.arp_dt_upload_batch_index_pairs_async if pairs else lib.arp_dt_upload_batch_indices_async)(self._h, slot, *args))
+            self._inflight[slot] = (None, None, None, B)
+        return pairs or not self._ds_use_enc
 
     def set_batch_indices(self, index):
-        ds, idx = self._index_args(index)
-        check(lib.arp_dt_set_batch_indices(self._h, ds._h, _ffi.as_ptr(idx, C.c_int64), len(idx), int(self._ds_use_enc)))
-        self._B = len(idx)
+        self._stage_indices(None, index)
 
     def upload_indices_async(self, slot, index):
         """:meth:`upload_async` for a batch of row indices: the gathers run on the handle's copy stream.  Returns whether the slot now holds frames."""
-        ds, idx = self._index_args(index)
-        check(lib.arp_dt_upload_batch_indices_async(self._h, int(slot), ds._h, _ffi.as_ptr(idx, C.c_int64), len(idx), int(self._ds_use_enc)))
-        self._inflight = getattr(self, "_inflight", {})
-        self._inflight[int(slot)] = (None, None, None, len(idx))
-        return not self._ds_use_enc
+        return self._stage_indices(int(slot), index)
 
     # -- model GCBC: (row, goal row) pairs of the attached dataset ---------------------------------------------------------------------
-    def _index_pair_args(self, index, goal_index):
-        ds, idx = self._index_args(index)
-        gidx = np.require(np.asarray(goal_index, dtype=np.int64).reshape(-1), requirements="C")
-        if len(gidx) != len(idx):
-            raise _ffi.ArpError(f"a pair batch names one goal row per row: {len(idx)} indices, {len(gidx)} goal indices")
-        return ds, idx, gidx
-
     def set_batch_index_pairs(self, index, goal_index):
         """Frames of the windows of ``index`` and goal frames of the windows of ``goal_index``, gathered on the GPU into the synchronous slot
         (``arp_dt_set_batch_index_pairs``); the step then encodes the pairs at its head, as after ``set_batch_images(..., goals=)``."""
-        ds, idx, gidx = self._index_pair_args(index, goal_index)
-        check(lib.arp_dt_set_batch_index_pairs(self._h, ds._h, _ffi.as_ptr(idx, C.c_int64), _ffi.as_ptr(gidx, C.c_int64), len(idx)))
-        self._B = len(idx)
+        self._stage_indices(None, index, goal_index)
 
     def upload_index_pairs_async(self, slot, index, goal_index):
         """:meth:`upload_indices_async` for a pair batch: one gather launch on the handle's copy stream fills the slot's frames and goal frames.  Returns
         True (the slot holds frames: :meth:`encode_ahead` may follow)."""
-        ds, idx, gidx = self._index_pair_args(index, goal_index)
-        check(lib.arp_dt_upload_batch_index_pairs_async(self._h, int(slot), ds._h, _ffi.as_ptr(idx, C.c_int64), _ffi.as_ptr(gidx, C.c_int64), len(idx)))
-        self._inflight = getattr(self, "_inflight", {})
-        self._inflight[int(slot)] = (None, None, None, len(idx))
-        return True
+        return self._stage_indices(int(slot), index, goal_index)
 
     def set_batch_images(self, images, action, rtg=None, goals=None):
         """Frames ``[B, T, H, W, 3]`` in front of the attached encoder.  ``goals`` (model GCBC): the hindsight goal frames, same shape; the step then encodes
         (frame, goal) pairs (``arp_dt_set_batch_images_goal``) and reads no return-to-go."""
+        if goals is None and self.gcbc:
+            raise _ffi.ArpError("model GCBC encodes (frame, goal) pairs: set_batch_images needs goals=")
+        if goals is None and rtg is None:
+            raise ValueError("rtg is None (only a goal batch of model GCBC takes no return-to-go)")
         images = np.require(np.asarray(images, dtype=np.float32), requirements="C")
         action = np.require(np.asarray(action, dtype=np.int32), requirements="C")
+        B, T = action.shape
         if goals is not None:
             goals = np.require(np.asarray(goals, dtype=np.float32), requirements="C")
-            B, T = action.shape
             if images.ndim != 5 or images.shape[:2] != (B, T) or goals.shape != images.shape or T != self.cfg.window:
                 raise ValueError(f"batch shapes: images {images.shape}, goals {goals.shape}, action {action.shape}")
             check(lib.arp_dt_set_batch_images_goal(self._h, _ffi.as_ptr(images, C.c_float), _ffi.as_ptr(goals, C.c_float), _ffi.as_ptr(action, C.c_int32), B))
-            self._B = B
-            return
-        if self.gcbc:
-            raise _ffi.ArpError("model GCBC encodes (frame, goal) pairs: set_batch_images needs goals=")
-        if rtg is None:
-            raise ValueError("rtg is None (only a goal batch of model GCBC takes no return-to-go)")
-        rtg = np.require(np.asarray(rtg, dtype=np.float32), requirements="C")
-        B, T = action.shape
-        if images.shape[:2] != (B, T) or rtg.size != B * T or T != self.cfg.window:
-            raise ValueError(f"batch shapes: images {images.shape}, action {action.shape}, rtg {rtg.shape}")
-        check(lib.arp_dt_set_batch_images(self._h, _ffi.as_ptr(images, C.c_float), _ffi.as_ptr(action, C.c_int32), _ffi.as_ptr(rtg, C.c_float), B))
+        else:
+            rtg = np.require(np.asarray(rtg, dtype=np.float32), requirements="C")
+            if images.shape[:2] != (B, T) or rtg.size != B * T or T != self.cfg.window:
+                raise ValueError(f"batch shapes: images {images.shape}, action {action.shape}, rtg {rtg.shape}")
+            check(lib.arp_dt_set_batch_images(self._h, _ffi.as_ptr(images, C.c_float), _ffi.as_ptr(action, C.c_int32), _ffi.as_ptr(rtg, C.c_float), B))
         self._B = B
+
+    def classify(self, batch, use_symlog=None):
+        """:func:`classify_batch` with this trainer's facts."""
+        return classify_batch(batch, encoder=self._encoder is not None, gcbc=self.gcbc, use_symlog=self.cfg.use_symlog if use_symlog is None else use_symlog)
+
+    def stage_batch(self, b, slot=None):
+        """Put a classified batch (:func:`classify_batch`) in front of the policy step: synchronously (``slot`` None: the next forward / step reads it), or
+        asynchronously into prefetch slot 0 / 1, to be read after :meth:`select`.  Returns whether the slot now holds frames (:meth:`encode_ahead` may follow)."""
+        if b.kind in ("index", "index_pairs"):
+            return self._stage_indices(slot if slot is None else int(slot), b.index, b.goal_index)
+        frames = b.kind != "encodings"
+        if slot is not None:
+            self.upload_async(slot, b.image, b.action, b.rtg, images=frames, goals=b.goals)
+        elif frames:
+            self.set_batch_images(b.image, b.action, b.rtg, goals=b.goals)
+        else:
+            self.set_batch(b.image, b.action, b.rtg)
+        return frames
 
     def forward(self):
         """ARPDT.__call__ (ARPDT.py:152-236) on the staged batch; model BC: BC.__call__ (BC.py:135-181), {action_pred, loss, acc}."""
@@ -325,21 +344,13 @@ class PolicyTrainer:
     def backward(self):
         check(lib.arp_dt_backward(self._h))
 
-    def _set_batch_any(self, enc, action, rtg, goals=None):
-        """encodings [B, T, tokens, dim], or -- with a frozen encoder attached -- normalised frames [B, T, H, W, 3] (row N1: what the rollout loop has),
-        or -- with a dataset attached -- a batch dict whose only key is ``"index"``, or -- model GCBC -- the reference's batch dict with
-        ``"image"``, ``"goal"`` and ``"action"`` (or frames with ``goals``)"""
-        if isinstance(enc, dict) and "goal" in enc:
-            goals = _first_view(enc["goal"]) if self.gcbc else None  # (the reference's dataset puts "goal" in every batch; only GCBC reads it)
-            enc, action, rtg = _batch_arrays(enc, self.cfg.use_symlog)
-        if is_index_pair_batch(enc):
-            self.set_batch_index_pairs(enc["index"], enc["goal_index"])
-        elif is_index_batch(enc):
-            self.set_batch_indices(enc["index"])
-        elif getattr(self, "_encoder", None) is not None and np.ndim(enc) == 5 and np.shape(enc)[-1] == 3:
-            self.set_batch_images(enc, action, rtg, goals=goals)
-        else:
-            self.set_batch(enc, action, rtg)
+    def _set_batch_any(self, enc, action=None, rtg=None):
+        """Stage synchronously what :meth:`greedy_action` / :meth:`greedy_return` are given: a batch dict of any kind (:func:`classify_batch`), or the arrays
+        of one -- encodings [B, T, tokens, dim] or, with a frozen encoder attached, normalised frames [B, T, H, W, 3] (row N1: what the rollout loop has)."""
+        if isinstance(enc, dict):
+            self.stage_batch(self.classify(enc))
+        else:  # (arrays are staged as given: the caller has prepared the return-to-go)
+            self.stage_batch(self.classify({"image": enc, "action": action, "rtg": rtg}, use_symlog=False))
 
     def greedy_action(self, enc, action=None, rtg=None):
         """ARPDT.greedy_action (ARPDT.py:488-492): argmax of the LAST time step's action logits."""
@@ -469,6 +480,37 @@ def _batch_arrays(batch, use_symlog=False):
         views = [symlog(v) for v in views]
     rtg = np.mean(np.stack(views), axis=0) if isinstance(rtg, dict) else views[0]
     return np.asarray(enc), np.asarray(batch["action"]), np.asarray(rtg)
+
+
+@dataclass
+class ClassifiedBatch:
+    """What :func:`classify_batch` makes of a host batch: its kind and the arrays that kind carries (the others stay None)."""
+    kind: str                 # "encodings" | "frames" | "frames+goals" | "index" | "index_pairs"
+    image: object = None      # encodings [B, T, tokens, dim], or frames [B, T, H, W, 3]
+    goals: object = None      # "frames+goals": the goal frames, the frames' shape
+    action: object = None
+    rtg: object = None        # the mean over the views, symlog'd first under use_symlog; None where the batch holds none
+    index: object = None      # "index" / "index_pairs": rows of the attached dataset
+    goal_index: object = None  # "index_pairs": the goal row of every row
+
+
+def classify_batch(batch, *, encoder, gcbc, use_symlog=False):
+    """The one place that answers "what kind of batch is this?", for a batch dict already cut to this rank (:func:`shard_batch`).  ``encoder``: a frozen
+    encoder is attached; ``gcbc``: the model is GCBC.  Needs no GPU.
+
+    * exactly ``{"index", "goal_index"}`` / exactly ``{"index"}``: rows of the attached device-resident dataset (``DeviceDataset.index_batches``);
+    * otherwise the reference's batch dict (:func:`_batch_arrays`): ``batch["image"]`` holds frames when an encoder is attached and the array is
+      ``[B, T, H, W, 3]``, else encodings; ``batch["goal"]`` -- the reference's dataset puts it in every batch -- is read by model GCBC alone, beside frames."""
+    if is_index_pair_batch(batch):
+        return ClassifiedBatch("index_pairs", index=batch["index"], goal_index=batch["goal_index"])
+    if is_index_batch(batch):
+        return ClassifiedBatch("index", index=batch["index"])
+    image, action, rtg = _batch_arrays(batch, use_symlog)
+    if not (encoder and image.ndim == 5 and image.shape[-1] == 3):
+        return ClassifiedBatch("encodings", image=image, action=action, rtg=rtg)
+    if gcbc and batch.get("goal") is not None:
+        return ClassifiedBatch("frames+goals", image=image, goals=_first_view(batch["goal"]), action=action, rtg=rtg)
+    return ClassifiedBatch("frames", image=image, action=action, rtg=rtg)
 
 
 def shard_batch(batch, rank, world, device_axis=False):
@@ -636,7 +678,7 @@ def prefetch_to_device(iterator, size, trainer, *, rank=0, world=1, device_axis=
     # Ownership is decided HERE, when the prefetcher is created -- not at the first next() (this used to be a generator function: whichever
     # iterator was pulled first won, so a validation iterator pulled before the training one silently demoted the training loop).
     with _SLOT_OWNER_LOCK:
-        owner = getattr(trainer, "_prefetch_owner", None) is None
+        owner = trainer._prefetch_owner is None
         if owner:
             token = object()
             trainer._prefetch_owner = token
@@ -658,14 +700,7 @@ def prefetch_to_device(iterator, size, trainer, *, rank=0, world=1, device_axis=
                 if stop.is_set():
                     return
                 part = shard_batch(batch, rank, world, device_axis)
-                if is_index_pair_batch(part):  # model GCBC: rows and goal rows of the attached dataset, one gather launch for both
-                    images = trainer.upload_index_pairs_async(slot, part["index"], part["goal_index"])
-                elif is_index_batch(part):  # rows of the attached dataset: gathered on the GPU into the slot
-                    images = trainer.upload_indices_async(slot, part["index"])
-                else:
-                    enc, act, rtg = _batch_arrays(part, trainer.cfg.use_symlog)
-                    images = getattr(trainer, "_encoder", None) is not None and enc.ndim == 5 and enc.shape[-1] == 3
-                    trainer.upload_async(slot, enc, act, rtg, images=images)
+                images = trainer.stage_batch(trainer.classify(part), slot)
                 if images and os.environ.get("ARP_DT_ENCODE_AHEAD", "1") != "0" and os.environ.get("ARP_DT_ENC_EAGER", "1") != "0":
                     trainer.encode_ahead(slot)  # the frozen encoder's pass for this batch runs beside the step that is reading the OTHER slot
                 ready.put(DeviceBatch(trainer, slot, lambda s=slot: free.put(s)))
@@ -684,7 +719,7 @@ def prefetch_to_device(iterator, size, trainer, *, rank=0, world=1, device_axis=
             # the worker is still inside an upload: the slots are NOT free -- keep the ownership (a new prefetcher is demoted to host staging) and say so
             raise RuntimeError("prefetch_to_device: the upload thread did not stop within 30 s; the device slots stay owned by this prefetcher")
         with _SLOT_OWNER_LOCK:
-            if getattr(trainer, "_prefetch_owner", None) is token:
+            if trainer._prefetch_owner is token:
                 trainer._prefetch_owner = None
 
     def gen():
@@ -709,7 +744,7 @@ def prefetch_to_device(iterator, size, trainer, *, rank=0, world=1, device_axis=
 
 def _release_if_unstarted(trainer, token):
     with _SLOT_OWNER_LOCK:
-        if getattr(trainer, "_prefetch_owner", None) is token:
+        if trainer._prefetch_owner is token:
             trainer._prefetch_owner = None
 
 
@@ -719,17 +754,7 @@ def _stage(tr, batch, rank, world, device_axis):
         tr.select(batch.slot)
         return batch
     part = shard_batch(batch, rank, world, device_axis)
-    if is_index_pair_batch(part):
-        tr.set_batch_index_pairs(part["index"], part["goal_index"])
-        return None
-    if is_index_batch(part):
-        tr.set_batch_indices(part["index"])
-        return None
-    enc, act, rtg = _batch_arrays(part, tr.cfg.use_symlog)
-    if part.get("goal") is not None and getattr(tr, "gcbc", False):  # the reference's GCBC batch dict: image, goal, action
-        tr._set_batch_any(enc, act, None, goals=_first_view(part["goal"]))
-        return None
-    tr._set_batch_any(enc, act, rtg) if hasattr(tr, "_set_batch_any") else tr.set_batch(enc, act, rtg)  # frames in with a frozen encoder attached (row N1): set_batch_images
+    tr.stage_batch(tr.classify(part))
     return None
 
 

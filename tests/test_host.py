@@ -362,18 +362,20 @@ def test_two_prefetchers_on_one_trainer_never_share_device_slots():
     """the reference opens train_iter AND val_iter with prefetch_to_device(..., 2) on the same state (main_procgen.py:703-708).
     The trainer's two device slots have ONE owner at a time: the second live prefetcher yields host batches (staged synchronously by the step
     functions), so no upload can land in a slot that holds an uploaded-but-unconsumed batch of the other iterator.  Stub trainer, no GPU."""
-    from arp_amd.train import DeviceBatch, PolicyConfig, prefetch_to_device
+    from arp_amd.train import DeviceBatch, PolicyConfig, PolicyTrainer, prefetch_to_device
     import threading
 
     class Stub:
         cfg = PolicyConfig(emb=8, depth=1, heads=2, window=2, enc_tokens=2, enc_dim=4)
+        gcbc, _encoder, _prefetch_owner = False, None, None
+        classify, stage_batch = PolicyTrainer.classify, PolicyTrainer.stage_batch  # the trainer's own routing, over this stub's upload
 
         def __init__(self):
             self.holds = {}  # slot -> tag of the uploaded-but-unconsumed batch in it
             self.lock = threading.Lock()
             self.clobbered = []
 
-        def upload_async(self, slot, enc, act, rtg, images=False):
+        def upload_async(self, slot, enc, act, rtg, images=False, goals=None):
             with self.lock:
                 if slot in self.holds:
                     self.clobbered.append((slot, self.holds[slot], float(enc.flat[0])))
@@ -420,16 +422,18 @@ def test_two_prefetchers_on_one_trainer_never_share_device_slots():
 def test_prefetcher_enqueues_the_next_batch_encoder_pass_behind_its_upload(monkeypatch):
     """Round 6 (row N1): with a frozen encoder attached and FRAMES in the batches, the prefetch worker enqueues the slot's encoder pass (arp_dt_encode_ahead) right
     behind that slot's upload -- never before it, never for encodings-in batches, and not at all with ARP_DT_ENCODE_AHEAD=0.  Stub trainer, no GPU."""
-    from arp_amd.train import DeviceBatch, PolicyConfig, prefetch_to_device
+    from arp_amd.train import DeviceBatch, PolicyConfig, PolicyTrainer, prefetch_to_device
 
     class Stub:
         cfg = PolicyConfig(emb=8, depth=1, heads=2, window=2, enc_tokens=2, enc_dim=4)
+        gcbc, _prefetch_owner = False, None
+        classify, stage_batch = PolicyTrainer.classify, PolicyTrainer.stage_batch  # the trainer's own routing, over this stub's upload
 
         def __init__(self, encoder):
             self._encoder = encoder
             self.log = []
 
-        def upload_async(self, slot, enc, act, rtg, images=False):
+        def upload_async(self, slot, enc, act, rtg, images=False, goals=None):
             self.log.append(("upload", slot, bool(images)))
 
         def encode_ahead(self, slot):
