@@ -205,11 +205,14 @@ SIGNATURES = {
     "arp_enc_forward": (_i, [_vp, _fp, _i, _fp]),
     "arp_enc_forward_gc": (_i, [_vp, _fp, _fp, _i, _fp]),
     "arp_enc_gc_tokens": (_i, [_vp]),
+    "arp_enc_forward_text": (_i, [_vp, _fp, _i, _i32p, _fp, _i, _i, _fp]),
+    "arp_enc_text_tokens": (_i, [_vp, _i]),
     "arp_enc_set_streams": (_i, [_vp, _i, _i, _i]),
     "arp_enc_set_latency": (_i, [_vp, _i, _i]),
     "arp_enc_profile_enable": (_i, [_vp, _i]),
     "arp_enc_profile_json": (_i, [_vp, C.c_char_p, _i]),
     "arp_dt_attach_encoder": (_i, [_vp, _vp]),
+    "arp_dt_attach_text_encoder": (_i, [_vp, _vp, _i32p, _fp, _i]),
     "arp_dt_set_batch_images": (_i, [_vp, _fp, _i32p, _fp, _i]),
     "arp_dt_set_batch_images_goal": (_i, [_vp, _fp, _fp, _i32p, _i]),
     "arp_dt_encode_ahead": (_i, [_vp, _i]),
@@ -232,6 +235,7 @@ SIGNATURES = {
     "arp_rollout_create_with_encoder": (_i, [_vp, _vp, _vp, _i, _i, _i, _f, C.POINTER(_vp)]),
     "arp_rollout_create_ft": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _f, C.POINTER(_vp)]),
     "arp_rollout_create_gc": (_i, [_vp, _vp, _vp, _i, _i, _i, _f, C.POINTER(_vp)]),
+    "arp_rollout_create_text": (_i, [_vp, _vp, _i, _i, _i, _i32p, _fp, _i, C.POINTER(_vp)]),
     "arp_rollout_reset_goal": (_i, [_vp, _i32p, _i, _fp, _u8p]),
     "arp_rollout_destroy": (_i, [_vp]),
     "arp_rollout_reset": (_i, [_vp, _i32p, _i, _fp]),
@@ -258,6 +262,7 @@ SIGNATURES = {
     "arp_op_layernorm": (_i, [_fp, _fp, _fp, _fp, _i, _i, _f]),
     "arp_op_attention": (_i, [_i, _i, _fp, _fp, _i, _i, _i, _i, _i]),
     "arp_op_attention_forms": (_i, [_i, _i, _fp, _vp, C.c_size_t, _i, _i, _i, _i, _i, _i, _i, _f, _i]),
+    "arp_op_attention_masked": (_i, [_i, _fp, _vp, C.c_size_t, _i, _i, _i, _i, _i, _i, _i, C.POINTER(C.c_uint32), _i, _i]),
     "arp_op_qkv_attention": (_i, [_i, _fp, _fp, _fp, _vp, C.c_size_t, _i, _i, _i, _i, _i, _i]),
     "arp_op_layernorm_forms": (_i, [_i, _fp, C.c_size_t, C.c_size_t, _i32p, _fp, _fp, _vp, C.c_size_t, _i, _i, _i, _f]),
     "arp_op_row_stats": (_i, [_i, _fp, _vp, C.c_size_t, _vp, C.c_size_t, _i, _i]),

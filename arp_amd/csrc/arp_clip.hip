@@ -1642,6 +1642,40 @@ int arp_op_attention_forms(int mode, int impl, const float* qkv, void* out, size
     return fail("attention_forms: mode must be f32, bf16 or f16");
 }
 
+// launch_attention with a key mask (tower.h::launch_attention_masked), on a byte buffer the caller fills.  mask: n_words visible-bit words on the host, sample b's
+// at mask + b * stride (stride 0: one mask); causal and form are passed on so that the launcher's refusals can be seen.
+int arp_op_attention_masked(int mode, const float* qkv, void* out, size_t out_bytes, int B, int N, int D, int heads, int causal, int nq, int form,
+                            const uint32_t* mask, int n_words, int stride) {
+    if (!qkv || !out || !mask || B <= 0 || N <= 0 || D <= 0 || heads <= 0 || D % heads || stride < 0) return fail("bad argument");
+    const int per = (N + 31) / 32;
+    if (n_words < (stride ? (B - 1) * stride : 0) + per || (stride && stride < per)) return fail("attention_masked: fewer mask words than (N + 31) / 32 per sample");
+    DevBuf dm;
+    ARP_TRY(dm.ensure((size_t)n_words * 4));
+    ARP_HIP_OK(hipMemcpy(dm.p, mask, (size_t)n_words * 4, hipMemcpyHostToDevice));
+    AttnKeyMask km;
+    km.dev = dm.as<uint32_t>(); km.stride = stride; km.host = mask;
+    auto run = [&](auto tag) -> int {
+        using T = decltype(tag);
+        const size_t rows = (size_t)B * N, esz = sizeof(T);
+        const size_t row_bytes = form == ARP_ATTN_OUT_PLAIN ? D * esz : (form == ARP_ATTN_OUT_E4M3 ? (size_t)D : (form == ARP_ATTN_OUT_F16C ? (size_t)3 * D : (size_t)6 * D));
+        if (form < ARP_ATTN_OUT_PLAIN || form > ARP_ATTN_OUT_SPLIT3) return fail("attention_masked: unknown output form");
+        if (out_bytes < rows * row_bytes) return fail("attention_masked: output buffer shorter than B * N rows");
+        DevBuf dq, dout;
+        ARP_TRY(to_dev<T>(qkv, rows * 3 * D, dq));
+        ARP_TRY(dout.ensure(std::max<size_t>(out_bytes, 16)));
+        ARP_HIP_OK(hipMemcpy(dout.p, out, out_bytes, hipMemcpyHostToDevice));
+        const int rc = launch_attention<T>(nullptr, 0, dq.as<T>(), dout.as<T>(), B, N, D, heads, causal, nq, form == ARP_ATTN_OUT_E4M3 ? 16.f : 0.f,
+                                           form == ARP_ATTN_OUT_SPLIT3 ? dout.as<f16_t>() : nullptr, form == ARP_ATTN_OUT_F16C ? 1 : 0, &km);
+        ARP_HIP_OK(hipDeviceSynchronize());
+        ARP_HIP_OK(hipMemcpy(out, dout.p, out_bytes, hipMemcpyDeviceToHost));
+        return rc;
+    };
+    if (mode == ARP_MODE_F16) return run(f16_t{});
+    if (mode == ARP_MODE_BF16) return run(bf16_t{});
+    if (mode == ARP_MODE_F32) return run(float{});
+    return fail("attention_masked: mode must be f32, bf16 or f16");
+}
+
 int arp_op_qkv_attention(int mode, const float* A, const float* W, const float* bias, void* out, size_t out_bytes, int B, int N, int K, int heads, int causal,
                          int nq) {
     if (!A || !W || !bias || !out || B <= 0 || N <= 0 || K <= 0 || heads <= 0) return fail("bad argument");

@@ -100,6 +100,11 @@ struct arp_dt {
     // nothing else queued, beside the step on the other slot
     Stream copy_stream;
     arp_enc* enc = nullptr;   // optional frozen encoder in front (row N1)
+    // model BC behind the image + text encoder (arp_dt_attach_text_encoder): ONE instruction on the handle -- the game being trained -- as the encoder's text pass
+    // takes it: L token ids followed by the visible-bit words of the 1 + P + L keys, in HBM, and the words on the host.  Every frames slot then encodes with it.
+    int text_L = 0;  // > 0: the instruction is set
+    DevBuf text_dev;
+    std::vector<uint32_t> text_words;
     bool use_images = false;
     // The encoder's part streams fork and join around ~150 long kernels: replayed as parallel branches of the step's hipGraph that costs more than it overlaps
     // (1.33 vs 0.99 ms for two short branches), and the encoder's launches are far longer than the host takes to issue them -- so with frames in
@@ -682,6 +687,15 @@ int policy_fused(arp_dt* c, bool do_bwd) {
     return 0;
 }
 
+// The frozen encoder's pass over the n frames of a slot, on `st`: the goal-conditioned pass where the slot holds goal frames, the image + text pass where the
+// handle carries an instruction (model BC), else the image-only pass.
+int encode_slot_on(arp_dt* c, arp_dt::BatchSlot& b, hipStream_t st, int n) {
+    if (b.goals) return enc_forward_gc_on(c->enc, st, b.img32.as<float>(), b.goal32.as<float>(), n, b.enc32.as<float>());
+    if (c->text_L > 0)
+        return enc_forward_text_on(c->enc, st, b.img32.as<float>(), n, c->text_dev.as<int32_t>(), reinterpret_cast<const uint32_t*>(c->text_dev.as<int32_t>() + c->text_L),
+                                   c->text_words.data(), c->text_L, 0, b.enc32.as<float>());
+    return enc_forward_on(c->enc, st, b.img32.as<float>(), n, b.enc32.as<float>());
+}
 // The encoder pass of batch slot `slot` on the encoder stream; after_compute: ordered behind everything on the compute stream (a batch staged synchronously
 // there, and the earlier steps' reads of this slot's enc32); otherwise behind the slot's upload and its last reader.  Caller holds capture_mu.
 int enqueue_encode(arp_dt* c, int slot, bool after_compute) {
@@ -698,8 +712,7 @@ int enqueue_encode(arp_dt* c, int slot, bool after_compute) {
         if (b.used) ARP_HIP_OK(hipStreamWaitEvent(c->enc_stream, b.use, 0));
     }
     if (c->gcbc() && !b.goals) return fail("encode: model GCBC encodes (frame, goal) pairs and this slot holds no goal frames");
-    if (b.goals) ARP_TRY(enc_forward_gc_on(c->enc, c->enc_stream, b.img32.as<float>(), b.goal32.as<float>(), b.B * c->cfg.window, b.enc32.as<float>()));
-    else ARP_TRY(enc_forward_on(c->enc, c->enc_stream, b.img32.as<float>(), b.B * c->cfg.window, b.enc32.as<float>()));
+    ARP_TRY(encode_slot_on(c, b, c->enc_stream, b.B * c->cfg.window));
     ARP_HIP_OK(hipEventRecord(b.enc_done, c->enc_stream));
     b.enc_ahead = true;
     return 0;
@@ -708,9 +721,7 @@ int enqueue_encode(arp_dt* c, int slot, bool after_compute) {
 int encode_current(arp_dt* c) {
     if (c->gcbc() && !c->bt[c->cur].goals) return fail("encode: model GCBC encodes (frame, goal) pairs and this slot holds no goal frames");
     if (!c->enc_eager) {  // rounds 1-5: on the step's own stream (ARP_DT_ENC_EAGER=0: inside the captured chain)
-        if (c->bt[c->cur].goals)
-            return enc_forward_gc_on(c->enc, c->stream, c->bt[c->cur].img32.as<float>(), c->bt[c->cur].goal32.as<float>(), c->R(), c->bt[c->cur].enc32.as<float>());
-        return enc_forward_on(c->enc, c->stream, c->bt[c->cur].img32.as<float>(), c->R(), c->bt[c->cur].enc32.as<float>());
+        return encode_slot_on(c, c->bt[c->cur], c->stream, c->R());
     }
     arp_dt::BatchSlot& b = c->bt[c->cur];
     if (!b.enc_ahead) {
@@ -1719,7 +1730,7 @@ int arp_dt_set_batch(arp_dt* c, const float* enc, const int32_t* action, const f
 
 int arp_dt_set_batch_images(arp_dt* c, const float* images, const int32_t* action, const float* rtg, int B) {
     if (c && c->gcbc()) return fail("model GCBC encodes (frame, goal) pairs: stage frames and goals with arp_dt_set_batch_images_goal");
-    if (!c || !images || !action || !rtg || B <= 0) return fail("bad argument");
+    if (!c || !images || !action || (!rtg && !c->bc()) || B <= 0) return fail("bad argument");  // (model BC reads no return-to-go)
     return stage_sync(c, {.B = B, .frames = images, .action = action, .rtg = rtg});
 }
 
@@ -1788,6 +1799,35 @@ int arp_dt_attach_encoder(arp_dt* c, arp_enc* enc) {
     if (c->gcbc()) ARP_TRY(enc_gc_tokens(enc, &tokens));
     if (tokens != c->cfg.enc_tokens || width != c->cfg.enc_dim) return fail("encoder geometry does not match enc_tokens / enc_dim");
     if (dev != c->cfg.device) return fail("encoder lives on another device");
+    c->enc = enc;
+    return 0;
+}
+
+// Model BC (InstructRL) with frames in: the image + text encoder and the ONE instruction of the game being trained (BC.encode, arp_dt/BC.py:283-321, tiles the
+// batch's instructions over the window with jnp.tile(text, (T, 1)), which pairs frame row i with instruction i mod B, not i // T: the reference is only
+// meaningful with one instruction per batch).  tokens int32 [L], mask f32 [L] (> 0 = padded).  Afterwards every frames slot of the handle -- the synchronous
+// slot, the prefetch slots, arp_dt_encode_ahead, index batches of frames -- encodes with the encoder's text pass, through the same stager as every other batch.
+int arp_dt_attach_text_encoder(arp_dt* c, arp_enc* enc, const int32_t* tokens, const float* mask, int L) {
+    if (!c || !enc || !tokens || !mask || L <= 0) return fail("bad argument");
+    if (!c->bc() || c->gcbc()) return fail("the image + text encoder belongs to model BC (ARP_DT_MODEL_BC): ARP-DT attaches the image-only encoder, GCBC the goal-conditioned one (arp_dt_attach_encoder)");
+    int tokens_n = 0, plain = 0, width = 0, res = 0, dev = 0;
+    ARP_TRY(enc_geometry(enc, &plain, &width, &res, &dev));
+    ARP_TRY(enc_text_tokens(enc, L, &tokens_n));
+    if (tokens_n != c->cfg.enc_tokens || width != c->cfg.enc_dim) return fail("encoder geometry does not match enc_tokens / enc_dim (enc_tokens must be 1 + P + L)");
+    if (dev != c->cfg.device) return fail("encoder lives on another device");
+    ARP_HIP_OK(hipSetDevice(c->cfg.device));
+    ARP_TRY(enc_text_prepare(enc, L));  // the text weights, the mode, and the position rows on the device before any step (or capture) needs them
+    const int per = (tokens_n + 31) / 32;
+    std::vector<uint32_t> words(per);
+    ARP_TRY(enc_text_words(enc, tokens, mask, 1, L, words.data()));
+    ARP_HIP_OK(hipDeviceSynchronize());  // (a re-attach: no pass in flight may still read the instruction about to be replaced)
+    std::vector<int32_t> blob(L + per);
+    memcpy(blob.data(), tokens, (size_t)L * 4);
+    memcpy(blob.data() + L, words.data(), (size_t)per * 4);
+    ARP_TRY(c->text_dev.ensure(blob.size() * 4));
+    ARP_HIP_OK(hipMemcpy(c->text_dev.p, blob.data(), blob.size() * 4, hipMemcpyHostToDevice));
+    c->text_words = std::move(words);
+    c->text_L = L;
     c->enc = enc;
     return 0;
 }

@@ -86,6 +86,39 @@ int launch_assemble_gc(hipStream_t stream, const float* pe, const float* cls, co
     return 0;
 }
 
+// The image + text sequence (forward_representation with an instruction, arp_dt/models/m3ae/model.py:471-496; BC.encode, arp_dt/BC.py:283-321): class token,
+// the frame's GG patches, the L instruction tokens.  Rows 0 .. GG are enc_assemble_kernel's values, expression for expression; text row i is
+//   x[b, 1 + GG + i] = text_emb[tok[i]] + tpos[i]      (tpos already holds get_1d_sincos_pos_embed(width, L)[i] + the text type embedding)
+// tok: int32 ids, [L] shared by the nb frames (per_row = 0) or [nb, L]; the host has checked them against the vocabulary.
+__global__ __launch_bounds__(256) void enc_assemble_text_kernel(const float* __restrict__ pe, const float* __restrict__ cls, const float* __restrict__ pos,
+                                                                const float* __restrict__ text_emb, const float* __restrict__ tpos,
+                                                                const int32_t* __restrict__ tok, int per_row, float* __restrict__ x, int nb, int GG, int L, int D) {
+    const int ntok = 1 + GG + L;
+    const size_t i = ((size_t)blockIdx.x * 256 + threadIdx.x) * 4;
+    if (i >= (size_t)nb * ntok * D) return;
+    const int c = (int)(i % D);
+    const size_t row = i / D;
+    const int t = (int)(row % ntok);
+    const size_t b = row / ntok;
+    float v[4];
+    if (t == 0) {
+        load4(cls + c, v);
+    } else {
+        float p4[4];
+        if (t <= GG) {
+            load4(pe + (b * GG + (t - 1)) * D + c, v);
+            load4(pos + (size_t)(t - 1) * D + c, p4);
+        } else {
+            const int j = t - 1 - GG;
+            const int id = tok[(per_row ? b * L : 0) + j];
+            load4(text_emb + (size_t)id * D + c, v);
+            load4(tpos + (size_t)j * D + c, p4);
+        }
+        v[0] += p4[0]; v[1] += p4[1]; v[2] += p4[2]; v[3] += p4[3];
+    }
+    store4(x + i, v[0], v[1], v[2], v[3]);
+}
+
 // ARP_MODE_F16X3: f32 [rows, K] -> binary16 [rows, 3K] = [hi | lo | hi], hi = rn16(x), lo = rn16(x - hi): the A operand of a K-concatenated product against
 // [W_hi | W_hi | W_lo] -- x.W to ~2^-22 on three 16-bit MFMAs (hi.hi is exact in the f32 accumulator; lo.lo, ~2^-24, is dropped).  Values whose lo falls below
 // binary16's normal range keep an absolute error <= 3e-8 (subnormals are not flushed on this path).  8 elements per thread.
@@ -149,6 +182,21 @@ struct HostTensor {
     std::vector<int64_t> shape;
 };
 
+// The instruction of an image + text pass as the kernels see it: token ids and visible-bit words (attention_long.h's mask format over the 1 + P + L keys: class
+// and patch keys always visible, text key i visible where the caller's padding mask is <= 0), both in HBM; the words on the host as well (the attention
+// launcher checks key 0 there).  per_row = 0: one instruction for every frame; 1: frame f's ids at tok + f * L, its words at words + f * per.
+struct TextPass {
+    const int32_t* tok = nullptr;
+    const uint32_t* words = nullptr;
+    const uint32_t* words_host = nullptr;
+    int L = 0, per_row = 0, per = 0;
+    TextPass at(int frame) const {  // the pass of the frames from `frame` on
+        TextPass t = *this;
+        if (per_row) { t.tok += (size_t)frame * L; t.words += (size_t)frame * per; t.words_host += (size_t)frame * per; }
+        return t;
+    }
+};
+
 }  // namespace
 
 struct arp_enc {
@@ -206,6 +254,16 @@ struct arp_enc {
     int plan[4] = {1, 1, 1, 0};
     std::vector<int> sw_d[4], sw_w[4];
     void* w_emb3 = nullptr;  // ARP_MODE_F16C: the patch embedding's [W_hi | W_hi | W_lo] (its product runs as ARP_MODE_F16X3's K-concatenation)
+    // The optional text branch (arp_enc_forward_text): text_embedding/embedding [vocab, width] and encoder_text_type_embedding, loaded when the caller staged them.
+    // text_pos rows i < text_pos_L hold get_1d_sincos_pos_embed(width, L)[i] + the type embedding (row i does not depend on L), built at the first call that
+    // needs them.  txt_pin / txt_dev: a host call's token ids followed by its visible-bit words, staged through pinned memory with one async copy on the call's stream.
+    float *text_emb = nullptr, *text_type = nullptr;
+    int vocab = 0;
+    std::vector<float> text_type_host;
+    DevBuf text_pos;
+    int text_pos_L = 0;
+    PinBuf txt_pin;
+    DevBuf txt_dev;
     Profiler prof;
     int gemm_force = 0;
     int tokens() const { return (cfg.img_res / cfg.patch) * (cfg.img_res / cfg.patch) + 1; }
@@ -322,9 +380,25 @@ int ensure_ws(arp_enc* c, arp_enc::Ws& w, int frames) {
 
 // goal_dev != null (here and in forward_chunk_x3): nb (frame, goal) pairs -- both frame sets through patchify and ONE patch-embedding product of 2 nb GG rows,
 // the goal-conditioned assembly, then the blocks over 2 GG + 1 tokens per sample.  goal_dev == null is the plain pass, launch for launch what it always was.
-template <typename T> int forward_chunk(arp_enc* c, arp_enc::Ws& w, hipStream_t stream, const float* img_dev, int nb, float* out_dev, const float* goal_dev) {
+// tx != null (here and in forward_chunk_x3; never together with goal_dev): the image + text pass -- the plain pass's patch embedding, the text assembly, then the
+// blocks over 1 + P + L tokens per sample with the instruction's key mask on every attention (tower.h: the key-blocked masked kernels at any length).
+int launch_assemble_text(arp_enc* c, hipStream_t stream, const float* pe, const TextPass& tx, float* x, int nb, int GG, int D) {
+    const size_t tot = (size_t)nb * (1 + GG + tx.L) * D;
+    hipLaunchKernelGGL(enc_assemble_text_kernel, dim3((unsigned)((tot / 4 + 255) / 256)), dim3(256), 0, stream, pe, c->cls, c->pos, c->text_emb, c->text_pos.as<float>(),
+                       tx.tok, tx.per_row, x, nb, GG, tx.L, D);
+    ARP_HIP_OK(hipGetLastError());
+    return 0;
+}
+AttnKeyMask key_mask_of(const TextPass& tx) {
+    AttnKeyMask km;
+    km.dev = tx.words; km.stride = tx.per_row ? tx.per : 0; km.host = tx.words_host;
+    return km;
+}
+
+template <typename T> int forward_chunk(arp_enc* c, arp_enc::Ws& w, hipStream_t stream, const float* img_dev, int nb, float* out_dev, const float* goal_dev,
+                                        const TextPass* tx) {
     const arp_enc_cfg& k = c->cfg;
-    const int G = k.img_res / k.patch, N = goal_dev ? c->gc_tokens() : c->tokens(), D = k.width, KP = k.patch * k.patch * 3;
+    const int G = k.img_res / k.patch, N = tx ? c->tokens() + tx->L : (goal_dev ? c->gc_tokens() : c->tokens()), D = k.width, KP = k.patch * k.patch * 3;
     TowerCtx t;
     t.stream = stream; t.prof = &c->prof; t.attn_impl = k.attn_impl; t.gemm_force = c->gemm_force; t.shared_chip = c->shared_chip;
     if (sizeof(T) == 2 && c->lat_now) {  // (the patch embedding below then goes through tower_gemm's skinny route where skinny_supported holds)
@@ -344,7 +418,10 @@ template <typename T> int forward_chunk(arp_enc* c, arp_enc::Ws& w, hipStream_t 
     }
     ARP_TRY((tower_gemm<T, float, ACT_NONE, false, 8 + SITE_PATCH>(t, "m3ae.image_embedding", w.patches.p, c->w_emb, c->b_emb, nullptr, w.pe.p,
                                                                    (goal_dev ? 2 : 1) * nb * G * G, D, KP)));
-    if (goal_dev) {
+    if (tx) {
+        ProfScope ps(c->prof, stream, "m3ae.assemble");
+        ARP_TRY(launch_assemble_text(c, stream, w.pe.as<float>(), *tx, w.x.as<float>(), nb, G * G, D));
+    } else if (goal_dev) {
         ProfScope ps(c->prof, stream, "m3ae.assemble");
         ARP_TRY(launch_assemble_gc(stream, w.pe.as<float>(), c->cls, c->pos, w.x.as<float>(), nb, G * G, D));
     } else {
@@ -354,8 +431,9 @@ template <typename T> int forward_chunk(arp_enc* c, arp_enc::Ws& w, hipStream_t 
                            w.x.as<float>(), nb * N, N, D);
         ARP_HIP_OK(hipGetLastError());
     }
+    const AttnKeyMask km = tx ? key_mask_of(*tx) : AttnKeyMask{};
     ARP_TRY((run_blocks<T, ACT_GELU_TANH, 8>(t, c->tower, "m3ae", w.x.as<float>(), w.h.as<T>(), w.qkv.as<T>(), w.ao.as<T>(), w.fc.as<T>(), nb, N, 0,
-                                             1e-6f)));
+                                             1e-6f, nullptr, tx ? &km : nullptr)));
     ARP_TRY(tower_layernorm<float>(t, "m3ae.ln_final", w.x.as<float>(), (size_t)D, out_dev, D, c->lnf_w, c->lnf_b, nb * N, D, 1e-6f));
     return 0;
 }
@@ -363,9 +441,9 @@ template <typename T> int forward_chunk(arp_enc* c, arp_enc::Ws& w, hipStream_t 
 // ARP_MODE_F16X3: the same network with every GEMM as a K-concatenated (hi, lo) product on the f16 kernels and everything between the GEMMs in f32
 // (LayerNorm outputs, the exact-f32 attention kernel, the tanh-GELU'd hidden activation): 12 x (ln -> split -> in_proj -> attention -> split -> out_proj -> ln ->
 // split -> fc1 -> split -> fc2).  Three MFMAs per product plus the split passes: ~4x the plain f16 step, ~2x faster than the f32-MFMA mode, f32-level error.
-int forward_chunk_x3(arp_enc* c, arp_enc::Ws& w, hipStream_t stream, const float* img_dev, int nb, float* out_dev, const float* goal_dev) {
+int forward_chunk_x3(arp_enc* c, arp_enc::Ws& w, hipStream_t stream, const float* img_dev, int nb, float* out_dev, const float* goal_dev, const TextPass* tx) {
     const arp_enc_cfg& k = c->cfg;
-    const int G = k.img_res / k.patch, N = goal_dev ? c->gc_tokens() : c->tokens(), D = k.width, KP = k.patch * k.patch * 3, H = k.mlp_ratio * D, M = nb * N;
+    const int G = k.img_res / k.patch, N = tx ? c->tokens() + tx->L : (goal_dev ? c->gc_tokens() : c->tokens()), D = k.width, KP = k.patch * k.patch * 3, H = k.mlp_ratio * D, M = nb * N;
     TowerCtx t;
     t.stream = stream; t.prof = &c->prof; t.attn_impl = k.attn_impl; t.gemm_force = c->gemm_force; t.shared_chip = c->shared_chip;
     f16_t* a3 = w.a3.as<f16_t>();
@@ -385,7 +463,10 @@ int forward_chunk_x3(arp_enc* c, arp_enc::Ws& w, hipStream_t stream, const float
     }
     ARP_TRY((tower_gemm<f16_t, float, ACT_NONE, false, 8 + SITE_PATCH>(t, "m3ae.image_embedding", a3, c->w_emb, c->b_emb, nullptr, w.pe.p,
                                                                        (goal_dev ? 2 : 1) * nb * G * G, D, 3 * KP)));
-    if (goal_dev) {
+    if (tx) {
+        ProfScope ps(c->prof, stream, "m3ae.assemble");
+        ARP_TRY(launch_assemble_text(c, stream, w.pe.as<float>(), *tx, w.x.as<float>(), nb, G * G, D));
+    } else if (goal_dev) {
         ProfScope ps(c->prof, stream, "m3ae.assemble");
         ARP_TRY(launch_assemble_gc(stream, w.pe.as<float>(), c->cls, c->pos, w.x.as<float>(), nb, G * G, D));
     } else {
@@ -394,17 +475,18 @@ int forward_chunk_x3(arp_enc* c, arp_enc::Ws& w, hipStream_t stream, const float
         hipLaunchKernelGGL(enc_assemble_kernel, dim3((unsigned)((tot / 4 + 255) / 256)), dim3(256), 0, stream, w.pe.as<float>(), c->cls, c->pos, w.x.as<float>(), nb * N, N, D);
         ARP_HIP_OK(hipGetLastError());
     }
+    const AttnKeyMask km = tx ? key_mask_of(*tx) : AttnKeyMask{};
     float *x = w.x.as<float>(), *qkv = w.qkv.as<float>(), *ao = w.ao.as<float>();
     for (int i = 0; i < k.layers; ++i) {
         const LayerW& L = c->tower.L[i];
         // LayerNorm and the attention write the (hi, lo, hi) triples of their f32 results themselves (f16x3_t / out3): no f32 copy, no split pass
-        const bool direct = k.attn_impl == 0 && D / k.heads == 64 && N <= 288;  // (the VALU attention has no such output: it keeps the split pass)
+        const bool direct = k.attn_impl == 0 && D / k.heads == 64 && N <= 288 && !tx;  // (the VALU attention has no such output, nor has a masked call -- the exact-f32 masked kernel: both keep the split pass)
         ARP_TRY(tower_layernorm<f16x3_t>(t, "m3ae.ln_1", x, D, reinterpret_cast<f16x3_t*>(a3), 3 * D, L.ln1_w, L.ln1_b, M, D, 1e-6f));
         ARP_TRY((tower_gemm<f16_t, float, ACT_NONE, false, 8 + SITE_QKV>(t, "m3ae.qkv", a3, L.w_in, L.b_in, nullptr, qkv, M, 3 * D, 3 * D)));
         {
             ProfScope ps(c->prof, stream, "m3ae.attn");
             // the (hi, lo) binary16 attention (attention.h::attn_x3_kernel) where it exists
-            ARP_TRY(launch_attention<float>(stream, direct ? 3 : k.attn_impl, qkv, ao, nb, N, D, k.heads, 0, 0, 0.f, direct ? a3 : nullptr));
+            ARP_TRY(launch_attention<float>(stream, direct ? 3 : k.attn_impl, qkv, ao, nb, N, D, k.heads, 0, 0, 0.f, direct ? a3 : nullptr, 0, tx ? &km : nullptr));
         }
         if (!direct) ARP_TRY(split("m3ae.split", ao, M, D));
         ARP_TRY((tower_gemm<f16_t, float, ACT_NONE, true, 8 + SITE_OUT>(t, "m3ae.out_proj", a3, L.w_out, L.b_out, x, x, M, D, 3 * D)));
@@ -495,15 +577,19 @@ int forward_chunk_c(arp_enc* c, arp_enc::Ws& w, hipStream_t stream, const float*
 namespace arp {
 
 // goal != null: nb (frame, goal) pairs.  A pair is 2 GG + 1 token rows and 2 GG patch rows: every workspace buffer of 2 nb plain frames holds it.
-static int forward_part(arp_enc* c, arp_enc::Ws& w, hipStream_t stream, const float* img, int nb, float* out, const float* goal = nullptr) {
+// tx != null: nb frames with an instruction, 1 + P + L token rows each: the workspace of ceil(nb (1 + P + L) / (1 + P)) plain frames holds them.
+static int forward_part(arp_enc* c, arp_enc::Ws& w, hipStream_t stream, const float* img, int nb, float* out, const float* goal = nullptr, const TextPass* tx = nullptr) {
     if (goal && c->cfg.mode == ARP_MODE_F16C)
         return fail("f16c: no goal-conditioned pass (its [hi | x4 | dx4] attention rows exist on the LDS-resident kernel only, <= 288 tokens)");
-    ARP_TRY(ensure_ws(c, w, goal ? 2 * nb : nb));
-    if (c->cfg.mode == ARP_MODE_F16X3) return forward_chunk_x3(c, w, stream, img, nb, out, goal);
+    if (tx && c->cfg.mode == ARP_MODE_F16C)
+        return fail("f16c: no image + text pass (its [hi | x4 | dx4] attention rows exist on the LDS-resident kernel only, <= 288 tokens)");
+    if (tx && goal) return fail("forward: an instruction and a goal frame do not combine");
+    ARP_TRY(ensure_ws(c, w, tx ? (int)(((long)nb * (c->tokens() + tx->L) + c->tokens() - 1) / c->tokens()) : (goal ? 2 * nb : nb)));
+    if (c->cfg.mode == ARP_MODE_F16X3) return forward_chunk_x3(c, w, stream, img, nb, out, goal, tx);
     if (c->cfg.mode == ARP_MODE_F16C) return forward_chunk_c(c, w, stream, img, nb, out);
-    if (c->cfg.mode == ARP_MODE_BF16) return forward_chunk<bf16_t>(c, w, stream, img, nb, out, goal);
-    if (c->cfg.mode == ARP_MODE_F16) return forward_chunk<f16_t>(c, w, stream, img, nb, out, goal);
-    return forward_chunk<float>(c, w, stream, img, nb, out, goal);
+    if (c->cfg.mode == ARP_MODE_BF16) return forward_chunk<bf16_t>(c, w, stream, img, nb, out, goal, tx);
+    if (c->cfg.mode == ARP_MODE_F16) return forward_chunk<f16_t>(c, w, stream, img, nb, out, goal, tx);
+    return forward_chunk<float>(c, w, stream, img, nb, out, goal, tx);
 }
 
 // the encoder's GEMM instances (forward_chunk / forward_chunk_x3 / forward_chunk_c above), by name
@@ -539,18 +625,21 @@ int enc_op_gemm_site(const arp_gemm_site& d) {
 // stream capture of `stream` (the part streams join the capture through the fork event and leave it through the join events), but every buffer must
 // exist beforehand: the first call of a geometry allocates and must run eagerly (arp_dt.hip runs two eager steps before it captures).
 // goals_dev != null: the goal-conditioned pass of n (frame, goal) pairs (enc_forward_gc_on); max_frames and the part sizes then count pairs
-static int enc_forward_any(arp_enc* c, hipStream_t stream, const float* images_dev, const float* goals_dev, int n, float* out_dev, bool latency) {
+// tx != null: the image + text pass of n frames (enc_forward_text_on); chunks, parts and the latency rule as for the other two, on n (1 + P + L) rows
+static int enc_forward_any(arp_enc* c, hipStream_t stream, const float* images_dev, const float* goals_dev, int n, float* out_dev, bool latency,
+                           const TextPass* tx = nullptr) {
     if (!c || !c->finalized) return fail("encoder weights not finalized");
     if (n <= 0) return 0;
     const int mb = c->cfg.max_frames;
-    const size_t fi = (size_t)c->cfg.img_res * c->cfg.img_res * 3, fo = (size_t)(goals_dev ? c->gc_tokens() : c->tokens()) * c->cfg.width;
+    const int ntok = tx ? c->tokens() + tx->L : (goals_dev ? c->gc_tokens() : c->tokens());
+    const size_t fi = (size_t)c->cfg.img_res * c->cfg.img_res * 3, fo = (size_t)ntok * c->cfg.width;
     // the latency path: decided on the call's TOTAL rows (never per part or per chunk: a frame's bits must not depend on how a call is cut), one part
     // (a goal-conditioned call counts its pairs' rows, 2 P + 1 each: one real pair is 513 rows, two pairs are over SKINNY_MAX_M)
-    const long rows = (long)n * (goals_dev ? c->gc_tokens() : c->tokens());
+    const long rows = (long)n * ntok;
     if (latency && (c->cfg.mode == ARP_MODE_F16 || c->cfg.mode == ARP_MODE_BF16) && n <= mb && rows <= c->lat_rows) {
         ARP_TRY(c->lat_part.ensure((size_t)4 * rows * c->cfg.width * 4));
         c->lat_now = true;
-        const int rc = forward_part(c, c->ws[0], stream, images_dev, n, out_dev, goals_dev);
+        const int rc = forward_part(c, c->ws[0], stream, images_dev, n, out_dev, goals_dev, tx);
         c->lat_now = false;
         return rc;
     }
@@ -559,10 +648,11 @@ static int enc_forward_any(arp_enc* c, hipStream_t stream, const float* images_d
         const float* img = images_dev + off * fi;
         float* out = out_dev + off * fo;
         const float* goal = goals_dev ? goals_dev + off * fi : nullptr;
+        const TextPass txo = tx ? tx->at(off) : TextPass{};
         int parts = std::min(c->n_parts, (int)arp_enc::MAX_PARTS);
         while (parts > 1 && nb / parts < c->min_part_frames) --parts;
         if (parts < 2) {
-            ARP_TRY(forward_part(c, c->ws[0], stream, img, nb, out, goal));
+            ARP_TRY(forward_part(c, c->ws[0], stream, img, nb, out, goal, tx ? &txo : nullptr));
             continue;
         }
         // contiguous parts: part 0 on the caller's stream, part k on its own
@@ -582,7 +672,9 @@ static int enc_forward_any(arp_enc* c, hipStream_t stream, const float* images_d
         for (int i = 0; i < parts && !rc; ++i) {
             hipStream_t st = i == 0 ? stream : c->ws[i].stream;
             if (i > 0 && hipStreamWaitEvent(st, c->ev_fork, 0) != hipSuccess) rc = fail("hipStreamWaitEvent(fork) failed");
-            if (!rc) rc = forward_part(c, c->ws[i], st, img + (size_t)cut[i] * fi, cut[i + 1] - cut[i], out + (size_t)cut[i] * fo, goal ? goal + (size_t)cut[i] * fi : nullptr);
+            const TextPass txp = tx ? txo.at(cut[i]) : TextPass{};
+            if (!rc) rc = forward_part(c, c->ws[i], st, img + (size_t)cut[i] * fi, cut[i + 1] - cut[i], out + (size_t)cut[i] * fo, goal ? goal + (size_t)cut[i] * fi : nullptr,
+                                       tx ? &txp : nullptr);
         }
         c->shared_chip = false;
         // join even after a failure: a part stream that entered a capture must leave it before the capture ends
@@ -603,6 +695,65 @@ int enc_forward_gc_on(arp_enc* c, hipStream_t stream, const float* images_dev, c
     if (!goals_dev) return fail("forward_gc: null goal frames");
     if (c && c->cfg.mode == ARP_MODE_F16C) return fail("f16c: no goal-conditioned pass (its [hi | x4 | dx4] attention rows exist on the LDS-resident kernel only, <= 288 tokens)");
     return enc_forward_any(c, stream, images_dev, goals_dev, n, out_dev, latency);
+}
+// What a text call needs before anything is enqueued: both text weights, a supported mode and length, and the position rows of L tokens on the device
+// (built and uploaded, synchronously, by the first call that needs rows this far; never again afterwards).
+static int text_prepare(arp_enc* c, int L) {
+    if (!c || !c->finalized) return fail("encoder weights not finalized");
+    if (c->cfg.mode == ARP_MODE_F16C) return fail("f16c: no image + text pass (its [hi | x4 | dx4] attention rows exist on the LDS-resident kernel only, <= 288 tokens)");
+    if (!c->text_emb || !c->text_type)
+        return fail("forward_text: the text weights were not loaded (text_embedding/embedding [vocab, width] and encoder_text_type_embedding [1, 1, width])");
+    if (L < 1 || c->tokens() + L > ATTN_LONG_MAX) return fail("forward_text: 1 + P + L must be at most 1024 token rows and L at least 1");
+    if (c->cfg.width / c->cfg.heads != 64) return fail("forward_text: the key-masked attention kernels need head_dim 64");
+    if (L <= c->text_pos_L) return 0;
+    const int D = c->cfg.width, half = D / 2;
+    std::vector<float> pos((size_t)L * D);
+    for (int i = 0; i < L; ++i)  // get_1d_sincos_pos_embed (m3ae/model.py:95-115) + the text type embedding
+        for (int d = 0; d < half; ++d) {
+            const double omega = 1.0 / std::pow(10000.0, (double)d / (double)half);
+            pos[(size_t)i * D + d] = (float)std::sin(i * omega) + c->text_type_host[d];
+            pos[(size_t)i * D + half + d] = (float)std::cos(i * omega) + c->text_type_host[half + d];
+        }
+    ARP_TRY(c->text_pos.ensure(pos.size() * 4));
+    ARP_HIP_OK(hipMemcpy(c->text_pos.p, pos.data(), pos.size() * 4, hipMemcpyHostToDevice));
+    c->text_pos_L = L;
+    return 0;
+}
+// n device-resident frames with an instruction -> out_dev [n, 1 + P + L, width] f32.  tok_dev: int32 ids ([L], or [n, L] with per_row), already checked against
+// the vocabulary; words_dev / words_host: the visible-bit words over the 1 + P + L keys ((1 + P + L + 31) / 32 per instruction), in HBM and on the host.
+// Stream, capture, chunk, part and latency rules as enc_forward_on (the first call of an L uploads its position rows and must run eagerly).
+int enc_text_prepare(arp_enc* c, int L) { return text_prepare(c, L); }
+int enc_forward_text_on(arp_enc* c, hipStream_t stream, const float* images_dev, int n, const int32_t* tok_dev, const uint32_t* words_dev, const uint32_t* words_host,
+                        int L, int per_row, float* out_dev, bool latency) {
+    ARP_TRY(text_prepare(c, L));
+    if (!tok_dev || !words_dev || !words_host) return fail("forward_text: null instruction");
+    TextPass tx;
+    tx.tok = tok_dev; tx.words = words_dev; tx.words_host = words_host; tx.L = L; tx.per_row = per_row ? 1 : 0; tx.per = (c->tokens() + L + 31) / 32;
+    return enc_forward_any(c, stream, images_dev, nullptr, n, out_dev, latency, &tx);
+}
+// Host side of an instruction: ids checked against the vocabulary, the visible-bit words built from the padding mask (mask > 0 = padded, the reference's
+// convention; class and patch keys always visible).  S instructions of L tokens -> words [S, (1 + P + L + 31) / 32].
+int enc_text_words(arp_enc* c, const int32_t* tokens, const float* mask, int S, int L, uint32_t* words) {
+    if (!c || !tokens || !mask || !words) return fail("forward_text: null instruction");
+    const int P1 = c->tokens(), per = (P1 + L + 31) / 32;
+    for (int s = 0; s < S; ++s) {
+        uint32_t* w = words + (size_t)s * per;
+        std::fill(w, w + per, 0u);
+        for (int k = 0; k < P1 + L; ++k) {
+            if (k >= P1) {
+                const int id = tokens[(size_t)s * L + k - P1];
+                if (id < 0 || id >= c->vocab) return fail("forward_text: token id " + std::to_string(id) + " is outside the vocabulary [0, " + std::to_string(c->vocab) + ")");
+                if (mask[(size_t)s * L + k - P1] > 0.f) continue;
+            }
+            w[k >> 5] |= 1u << (k & 31);
+        }
+    }
+    return 0;
+}
+int enc_text_tokens(arp_enc* c, int L, int* tokens) {
+    if (!c) return fail("null encoder");
+    *tokens = c->tokens() + L;
+    return 0;
 }
 int enc_gc_tokens(arp_enc* c, int* tokens) {
     if (!c) return fail("null encoder");
@@ -759,6 +910,19 @@ int arp_enc_finalize_weights(arp_enc* c) {
     }
     ARP_TRY(staged(c, "encoder/LayerNorm_0/scale", {D}, &t)); ARP_TRY(up_f32(c, t->data.data(), D, &c->lnf_w));
     ARP_TRY(staged(c, "encoder/LayerNorm_0/bias", {D}, &t)); ARP_TRY(up_f32(c, t->data.data(), D, &c->lnf_b));
+    // the optional text branch: each of the two tensors is uploaded when it was staged (f32 in every mode: a row kernel adds them into the f32 residual stream);
+    // arp_enc_forward_text needs both.  The vocabulary size is the embedding's first dimension.
+    if (auto it = c->staged.find("text_embedding/embedding"); it != c->staged.end()) {
+        const HostTensor& e = it->second;
+        if (e.shape.size() != 2 || e.shape[0] < 1 || e.shape[0] > INT32_MAX || e.shape[1] != D) return fail("weight text_embedding/embedding has an unexpected shape");
+        ARP_TRY(up_f32(c, e.data.data(), e.data.size(), &c->text_emb));
+        c->vocab = (int)e.shape[0];
+    }
+    if (c->staged.count("encoder_text_type_embedding")) {
+        ARP_TRY(staged(c, "encoder_text_type_embedding", {1, 1, D}, &t));
+        ARP_TRY(up_f32(c, t->data.data(), D, &c->text_type));
+        c->text_type_host = t->data;
+    }
     c->staged.clear();
     c->finalized = true;
     return 0;
@@ -809,6 +973,42 @@ int arp_enc_forward_gc(arp_enc* c, const float* images, const float* goals, int 
     return 0;
 }
 int arp_enc_gc_tokens(arp_enc* c) { return c ? c->gc_tokens() : fail("null handle"); }
+
+int arp_enc_forward_text(arp_enc* c, const float* images, int n, const int32_t* tokens, const float* mask, int L, int per_row, float* out) {
+    if (!c || !c->finalized) return fail("encoder weights not finalized");
+    if (n < 0) return fail("negative frame count");
+    if (n == 0) return 0;
+    if (!images || !out || !tokens || !mask) return fail("null buffer");
+    ARP_HIP_OK(hipSetDevice(c->cfg.device));
+    ARP_TRY(text_prepare(c, L));
+    const int S = per_row ? n : 1, per = (c->tokens() + L + 31) / 32;
+    const size_t fi = (size_t)c->cfg.img_res * c->cfg.img_res * 3, fo = (size_t)(c->tokens() + L) * c->cfg.width;
+    const int mb = c->cfg.max_frames;
+    if (!c->stream) ARP_TRY(c->stream.create());
+    // ids, then words: one pinned block, one async copy in front of the first chunk (the previous call synchronised before it returned: the block is free)
+    const size_t tb = (size_t)S * L * 4, wb = (size_t)S * per * 4;
+    ARP_TRY(c->txt_pin.ensure(tb + wb));
+    ARP_TRY(c->txt_dev.ensure(tb + wb));
+    int32_t* tok_h = c->txt_pin.as<int32_t>();
+    uint32_t* words_h = reinterpret_cast<uint32_t*>(c->txt_pin.as<char>() + tb);
+    ARP_TRY(enc_text_words(c, tokens, mask, S, L, words_h));
+    memcpy(tok_h, tokens, tb);
+    ARP_HIP_OK(hipMemcpyAsync(c->txt_dev.p, c->txt_pin.p, tb + wb, hipMemcpyHostToDevice, c->stream));
+    const int32_t* tok_d = c->txt_dev.as<int32_t>();
+    const uint32_t* words_d = reinterpret_cast<const uint32_t*>(c->txt_dev.as<char>() + tb);
+    ARP_TRY(c->img_in.ensure((size_t)std::min(n, mb) * fi * 4));
+    ARP_TRY(c->out.ensure((size_t)std::min(n, mb) * fo * 4));
+    for (int off = 0; off < n; off += mb) {
+        const int nb = std::min(mb, n - off);
+        const size_t to = per_row ? (size_t)off * L : 0, wo = per_row ? (size_t)off * per : 0;
+        ARP_HIP_OK(hipMemcpyAsync(c->img_in.p, images + off * fi, nb * fi * 4, hipMemcpyHostToDevice, c->stream));
+        ARP_TRY(enc_forward_text_on(c, c->stream, c->img_in.as<float>(), nb, tok_d + to, words_d + wo, words_h + wo, L, per_row, c->out.as<float>(), c->lat_host && n <= mb));
+        ARP_HIP_OK(hipMemcpyAsync(out + off * fo, c->out.p, nb * fo * 4, hipMemcpyDeviceToHost, c->stream));
+        ARP_HIP_OK(hipStreamSynchronize(c->stream));
+    }
+    return 0;
+}
+int arp_enc_text_tokens(arp_enc* c, int L) { return c && L >= 0 ? c->tokens() + L : fail("null handle or negative length"); }
 
 // Part streams of a call (see arp_enc::Ws).  n_streams 1 = everything on the caller's stream (rounds 1-5); first_part_frames > 0: that many frames in part 0 of two, 0: the default cut (15/32), < 0: equal parts;
 // min_part_frames <= 0 keeps the default (a part of fewer frames runs with fewer parts).  Takes effect from the next call.

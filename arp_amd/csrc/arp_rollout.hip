@@ -11,6 +11,7 @@
 //
 // A session made by arp_rollout_create_gc also holds one GOAL frame per environment (the reference fixes it per episode, :94, and re-attaches it to every
 // observation, :108,130).  Model GCBC: the encoder pass above becomes the goal-conditioned one on the E new (frame, goal) pairs, everything else is the BC step.
+// A session made by arp_rollout_create_text (model BC, InstructRL) holds the game's instruction: the encoder pass is the image + text one on the E new frames.
 // An ARP-DT policy with a plain labelling handle: the reward pass becomes the features of the E new frames and a kernel that writes -||f - g||_2 against the
 // goals' features, which were computed at arp_rollout_reset_goal (clip_goal_conditioned, envs/vl_reward.py:26-41).
 #include <algorithm>
@@ -173,6 +174,12 @@ struct arp_rollout {
     DevBuf goals_u8, goal32, goal_feat, frame_feat;
     std::vector<char> has_goal;     // [E]
     bool goal_reward() const { return gc && clip; }
+    // A session made by arp_rollout_create_text (model BC, InstructRL): the instruction its steps encode the E new frames with -- L token ids followed by the
+    // visible-bit words of the 1 + P + L keys in HBM, the words on the host (enc_internal.h::enc_forward_text_on).  Constant over the episode, so a ring
+    // entry stays valid for as long as its frame is in the window.
+    int text_L = 0;
+    DevBuf text_dev;
+    std::vector<uint32_t> text_words;
     const float* logits = nullptr;  // the policy's logits buffer as of the last step
     float* slot_enc = nullptr;
     int32_t* slot_action = nullptr;
@@ -195,7 +202,7 @@ int quiesce(arp_rollout* s) {
 extern "C" {
 
 static int rollout_create(arp_dt* policy, arp_enc* encoder, arp_clip* reward, arp_ft* head, int n_envs, int H, int W, float scale, arp_rollout** out,
-                          bool gc = false) {
+                          bool gc = false, int text_L = 0) {
     if (!policy || !out) return fail("null argument");
     if (n_envs <= 0) return fail("rollout: n_envs must be positive");
     if (!(scale != 0.f)) return fail("rollout: scale must not be zero");
@@ -205,7 +212,8 @@ static int rollout_create(arp_dt* policy, arp_enc* encoder, arp_clip* reward, ar
     if (gc && head) return fail("rollout: create_gc takes a plain labelling handle: the fine-tuned goal reward stays with the host function");
     if (gc && s->pi.bc && !s->pi.gcbc) return fail("rollout: create_gc: model BC reads no goal frame (model GCBC does)");
     if (gc && !s->pi.bc && !reward) return fail("rollout: create_gc: an ARP-DT policy carries goal frames for the goal reward only: pass a labelling handle");
-    // Model BC refuses arp_dt_attach_encoder (its reference encoder reads the instruction's text tokens too): the session is then LENT an encoder for its own
+    // Model BC refuses arp_dt_attach_encoder (its reference encoder reads the instruction's text tokens too; arp_rollout_create_text is the session that
+    // carries them): a session without an instruction is LENT an encoder for its own
     // passes (arp_rollout_create_with_encoder); the handle's refusal stands.  BC.encode reads no return-to-go: no ring, no reward source.
     if (encoder) s->pi.enc = encoder;
     if (!s->pi.enc)
@@ -215,6 +223,7 @@ static int rollout_create(arp_dt* policy, arp_enc* encoder, arp_clip* reward, ar
     int tokens = 0, width = 0, res = 0, dev = 0;
     ARP_TRY(enc_geometry(s->pi.enc, &tokens, &width, &res, &dev));
     if (s->pi.gcbc) ARP_TRY(enc_gc_tokens(s->pi.enc, &tokens));  // a (frame, goal) pair per ring entry
+    if (text_L > 0) ARP_TRY(enc_text_tokens(s->pi.enc, text_L, &tokens));  // a frame and the instruction per ring entry
     if (H != res || W != res) return fail("rollout: frames are " + std::to_string(H) + " x " + std::to_string(W) + ", the attached encoder reads " + std::to_string(res) + " x " + std::to_string(res));
     if (tokens != s->pi.enc_tokens || width != s->pi.enc_dim) return fail("rollout: encoder geometry does not match the policy's enc_tokens / enc_dim");
     if (dev != s->pi.device) return fail("rollout: the encoder lives on another device");
@@ -275,6 +284,37 @@ int arp_rollout_create_ft(arp_dt* policy, arp_enc* encoder_or_null, arp_clip* to
 
 int arp_rollout_create_gc(arp_dt* policy, arp_enc* encoder_or_null, arp_clip* reward_or_null, int n_envs, int H, int W, float scale, arp_rollout** out) {
     return rollout_create(policy, encoder_or_null, reward_or_null, nullptr, n_envs, H, W, scale, out, true);
+}
+
+// Model BC (InstructRL) with the instruction of the game: tokens int32 [L], mask f32 [L] (> 0 = padded).  The encoder is the one given, or the one the policy
+// carries from arp_dt_attach_text_encoder; either way it must hold the text weights, and enc_tokens == 1 + P + L.
+int arp_rollout_create_text(arp_dt* policy, arp_enc* encoder_or_null, int n_envs, int H, int W, const int32_t* tokens, const float* mask, int L, arp_rollout** out) {
+    if (!policy || !tokens || !mask || !out) return fail("null argument");
+    if (L <= 0) return fail("rollout: create_text: the instruction has no tokens");
+    DtRolloutInfo pi{};
+    ARP_TRY(dt_rollout_info(policy, &pi));
+    if (!pi.bc || pi.gcbc) return fail("rollout: create_text: an instruction belongs to model BC (ARP-DT's and GCBC's encoder calls read no text)");
+    arp_enc* enc = encoder_or_null ? encoder_or_null : pi.enc;
+    if (!enc) return fail("rollout: create_text: no encoder (pass one, or attach one with arp_dt_attach_text_encoder)");
+    ARP_HIP_OK(hipSetDevice(pi.device));
+    ARP_TRY(enc_text_prepare(enc, L));  // the text weights, the mode, the position rows: before the first step
+    int ntok = 0;
+    ARP_TRY(enc_text_tokens(enc, L, &ntok));
+    const int per = (ntok + 31) / 32;
+    std::vector<uint32_t> words(per);
+    ARP_TRY(enc_text_words(enc, tokens, mask, 1, L, words.data()));
+    arp_rollout* s = nullptr;
+    ARP_TRY(rollout_create(policy, enc, nullptr, nullptr, n_envs, H, W, 1.f, &s, false, L));
+    std::unique_ptr<arp_rollout> own(s);
+    std::vector<int32_t> blob(L + per);
+    memcpy(blob.data(), tokens, (size_t)L * 4);
+    memcpy(blob.data() + L, words.data(), (size_t)per * 4);
+    ARP_TRY(s->text_dev.ensure(blob.size() * 4));
+    ARP_HIP_OK(hipMemcpy(s->text_dev.p, blob.data(), blob.size() * 4, hipMemcpyHostToDevice));
+    s->text_words = std::move(words);
+    s->text_L = L;
+    *out = own.release();
+    return 0;
 }
 
 int arp_rollout_destroy(arp_rollout* s) {
@@ -430,6 +470,9 @@ static int rollout_step(arp_rollout* s, const uint8_t* frames_host, const float*
     // 3. the encoder on the E new frames (model GCBC: on the E new (frame, goal) pairs), straight into ring slot `head`
     float* slot = s->ring.as<float>() + (size_t)s->head * E * s->F;
     if (s->pi.gcbc) ARP_TRY(enc_forward_gc_on(s->enc, S, s->enc_in.as<float>(), s->goal32.as<float>(), E, slot, true));
+    else if (s->text_L > 0)  // (model BC with its instruction: the image + text pass)
+        ARP_TRY(enc_forward_text_on(s->enc, S, s->enc_in.as<float>(), E, s->text_dev.as<int32_t>(), reinterpret_cast<const uint32_t*>(s->text_dev.as<int32_t>() + s->text_L),
+                                    s->text_words.data(), s->text_L, 0, slot, true));
     else ARP_TRY(enc_forward_on(s->enc, S, s->enc_in.as<float>(), E, slot, true));
     // 4. window
     {

@@ -6,6 +6,9 @@
 //                           O^T = V^T.P^T, V^T fragments by ds_read_b64_tr_b16 -- with the keys walked in blocks of 64 through a ring of three LDS stages.
 //   attn_long_f32_kernel  : exact f32, the parity mode.  attn_valu_kernel's arithmetic (one query per lane, one key at a time, expf), K / V staged
 //                           128 keys at a time: a row comes out with the bits attn_valu_kernel gives it.
+//   attn_long_masked_kernel<T>, attn_long_f32_masked_kernel : the same two bodies with a per-sample KEY MASK (one bit per key; M3AE's image + text pass takes
+//                           its padded instruction tokens out of every softmax), for any N from 1 to 1024.  The unmasked kernels are the MASKED = false
+//                           instances of the bodies and compile none of it.
 //
 // What a row's bits depend on: its own q row, the K / V rows, N, causal.  Not on B, the workgroup, the wave or gridDim.y: a 16-query block is always
 // computed by one wave, over key blocks 0, 1, 2, ... in that order, and query blocks never share an accumulator.
@@ -50,9 +53,10 @@ constexpr int ATTN_LONG_LDS = ATTN_LONG_RING * ATTN_LONG_KB * 256;
 #define ARP_AL_VWAIT(R)                                                                                                               \
     asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(R[0]), "+v"(R[1]), "+v"(R[2]), "+v"(R[3]), "+v"(R[4]), "+v"(R[5]), "+v"(R[6]), "+v"(R[7]) : : "memory")
 
-template <typename T>
-__global__ __launch_bounds__(256) void attn_long_kernel(const T* __restrict__ qkv, T* __restrict__ out, int N, int D, int heads, float scale, int causal,
-                                                        int nq) {
+// MASKED: a key mask per sample (the comment above attn_long_masked_kernel); the unmasked instance compiles none of it.
+template <typename T, bool MASKED>
+__device__ __forceinline__ void attn_long_body(const T* __restrict__ qkv, T* __restrict__ out, int N, int D, int heads, float scale, int causal, int nq,
+                                               const uint32_t* __restrict__ mask, int mask_stride) {
     constexpr int KB = ATTN_LONG_KB, STAGE = KB * 256;
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -63,6 +67,7 @@ __global__ __launch_bounds__(256) void attn_long_kernel(const T* __restrict__ qk
     const int prow = lane >> 3, pch = lane & 7;
     const int nqb = (nq + 15) >> 4, ntiles = (nqb + 3) >> 2, nkb = (N + KB - 1) / KB;
     const float c2 = scale * 1.4426950408889634f;  // exp(x * scale) = exp2(x * c2)
+    const uint32_t* mw = MASKED ? mask + (size_t)b * mask_stride : nullptr;  // this sample's visible-bit words: workgroup-uniform
     // transposing-read addressing (attn_mfma_kernel's): lane 4q + p of a 16-lane group points at row 4 fg + q (+ 32 st, + 16 for the second half: neither
     // changes row & 7), columns 4p .. 4p + 3 of the 16-column block dt.  vrd[dt]: this lane's byte address inside the V image of ring stage 0.
     uint32_t vrd[4];
@@ -120,10 +125,19 @@ __global__ __launch_bounds__(256) void attn_long_kernel(const T* __restrict__ qk
             __builtin_amdgcn_s_barrier();
             if (j + 2 < nk) stage(j + 2, buf == 0 ? 2 : buf - 1);
             const int kb0 = j * KB;
-            if (active && !(causal && kb0 > qb * 16 + 15)) {
+            // MASKED: the block's two words, pad keys (>= N) cleared -- bit i of vis <-> key kb0 + i.  Uniform over the workgroup; read behind the barrier
+            // and the requests, so the ring protocol above sees the same waits, barriers and requests whatever the words hold.
+            uint64_t vis = ~0ull;
+            if constexpr (MASKED) {
+                const int left = N - kb0;  // >= 1
+                const uint32_t lo = mw[2 * j] & (left >= 32 ? 0xffffffffu : (1u << left) - 1u);
+                const uint32_t hi = left > 32 ? mw[2 * j + 1] & (left >= 64 ? 0xffffffffu : (1u << (left - 32)) - 1u) : 0u;
+                vis = (uint64_t)hi << 32 | lo;
+            }
+            if (active && !(causal && kb0 > qb * 16 + 15) && !(MASKED && vis == 0)) {
                 const char* Ks = smem + buf * STAGE;
                 const char* Vs = Ks + KB * 128;
-                const bool upper = kb0 + 32 < N && !(causal && kb0 + 32 > qb * 16 + 15);  // wave-uniform
+                const bool upper = MASKED ? (vis >> 32) != 0 : kb0 + 32 < N && !(causal && kb0 + 32 > qb * 16 + 15);  // wave-uniform
                 // S^T tile kt: rows = keys kb0 + 16 kt + 4 fg + r, column = query fr
                 f32x4_v s[4];
 #pragma unroll
@@ -148,7 +162,15 @@ __global__ __launch_bounds__(256) void attn_long_kernel(const T* __restrict__ qk
                 ARP_AL_VREAD(0, v0, va);
                 if (upper) ARP_AL_VREAD(4096, v1, va);
                 // masks only where the block holds a pad key or a key behind one of the wave's queries
-                if (kb0 + KB > N || (causal && kb0 + KB - 1 > qb * 16)) {
+                if constexpr (MASKED) {
+                    if (vis != ~0ull) {  // a hidden or pad key in the block
+                        const uint64_t mine = vis >> (fg * 4);
+#pragma unroll
+                        for (int kt = 0; kt < 4; ++kt)
+#pragma unroll
+                            for (int r = 0; r < 4; ++r) s[kt][r] = (mine >> (kt * 16 + r)) & 1 ? s[kt][r] : -INFINITY;
+                    }
+                } else if (kb0 + KB > N || (causal && kb0 + KB - 1 > qb * 16)) {
 #pragma unroll
                     for (int kt = 0; kt < 4; ++kt)
 #pragma unroll
@@ -210,6 +232,23 @@ __global__ __launch_bounds__(256) void attn_long_kernel(const T* __restrict__ qk
         }
     }
 }
+template <typename T>
+__global__ __launch_bounds__(256) void attn_long_kernel(const T* __restrict__ qkv, T* __restrict__ out, int N, int D, int heads, float scale, int causal,
+                                                        int nq) {
+    attn_long_body<T, false>(qkv, out, N, D, heads, scale, causal, nq, nullptr, 0);
+}
+// The key-masked instance (M3AE's image + text pass: padded instruction tokens are taken out of every softmax).  mask: one bit per key, 1 = visible, key k in
+// bit k & 31 of word k >> 5, (N + 31) / 32 words per sample, sample b's words at mask + b * mask_stride (stride 0: one mask for the whole call).  A hidden key
+// scores -inf for every query of its sample.  A block of 64 keys that are all hidden is staged and meets its barriers like any other, and its compute is
+// skipped (as the causal skip does: m, l and o stay as they are); the upper 32 keys are skipped when all hidden; the per-score select runs only in blocks
+// that hold a hidden or pad key.  Key 0 must be visible (the launcher refuses otherwise): block 0 is then computed for every query and m is finite from
+// there on.  No causal mask in this instance.  With every key visible each query block runs the unmasked instance's operations in its order: the same bits.
+// Any N from 1 to 1024: pad keys alias key N - 1 and are cleared from the words.
+template <typename T>
+__global__ __launch_bounds__(256) void attn_long_masked_kernel(const T* __restrict__ qkv, T* __restrict__ out, int N, int D, int heads, float scale, int nq,
+                                                               const uint32_t* __restrict__ mask, int mask_stride) {
+    attn_long_body<T, true>(qkv, out, N, D, heads, scale, 0, nq, mask, mask_stride);
+}
 #undef ARP_AL_VREAD
 #undef ARP_AL_VWAIT
 
@@ -217,9 +256,11 @@ __global__ __launch_bounds__(256) void attn_long_kernel(const T* __restrict__ qk
 // operation for operation; only where K and V rows are when they are read differs.
 constexpr int ATTN_LONG_F32_KB = 128, ATTN_LONG_F32_Q = 128;
 constexpr int ATTN_LONG_F32_LDS = 2 * ATTN_LONG_F32_KB * 64 * 4;
-template <int QW>  // queries (= lanes) per workgroup
-__global__ __launch_bounds__(QW) void attn_long_f32_kernel(const float* __restrict__ qkv, float* __restrict__ out, int N, int D, int heads,
-                                                                         float scale, int causal, int nq) {
+// MASKED (mask format as attn_long_masked_kernel's): a hidden key is skipped in the per-key loop -- a uniform branch -- so a query row gets the bits the
+// unmasked kernel gives it on the sequence with the hidden K / V rows removed.
+template <int QW, bool MASKED>  // queries (= lanes) per workgroup
+__device__ __forceinline__ void attn_long_f32_body(const float* __restrict__ qkv, float* __restrict__ out, int N, int D, int heads, float scale, int causal,
+                                                   int nq, const uint32_t* __restrict__ mask, int mask_stride) {
     constexpr int HD = 64, KB = ATTN_LONG_F32_KB;
     extern __shared__ __attribute__((aligned(16))) char smem[];
     float* Ks = reinterpret_cast<float*>(smem);
@@ -249,6 +290,10 @@ __global__ __launch_bounds__(QW) void attn_long_f32_kernel(const float* __restri
         __syncthreads();
         const int ke = min(nb, kend - k0);
         for (int k = 0; k < ke; ++k) {
+            if constexpr (MASKED) {
+                const int key = k0 + k;
+                if (!((mask[(size_t)b * mask_stride + (key >> 5)] >> (key & 31)) & 1)) continue;
+            }
             const float* kr = Ks + k * HD;
             float s = 0.f;
 #pragma unroll
@@ -269,6 +314,16 @@ __global__ __launch_bounds__(QW) void attn_long_f32_kernel(const float* __restri
 #pragma unroll
         for (int d = 0; d < HD; d += 4) store4(o + d, acc[d] * inv, acc[d + 1] * inv, acc[d + 2] * inv, acc[d + 3] * inv);
     }
+}
+template <int QW>
+__global__ __launch_bounds__(QW) void attn_long_f32_kernel(const float* __restrict__ qkv, float* __restrict__ out, int N, int D, int heads,
+                                                                         float scale, int causal, int nq) {
+    attn_long_f32_body<QW, false>(qkv, out, N, D, heads, scale, causal, nq, nullptr, 0);
+}
+template <int QW>
+__global__ __launch_bounds__(QW) void attn_long_f32_masked_kernel(const float* __restrict__ qkv, float* __restrict__ out, int N, int D, int heads, float scale,
+                                                                  int nq, const uint32_t* __restrict__ mask, int mask_stride) {
+    attn_long_f32_body<QW, true>(qkv, out, N, D, heads, scale, 0, nq, mask, mask_stride);
 }
 
 }  // namespace arp

@@ -261,12 +261,54 @@ static int tower_layernorm(TowerCtx& c, const char* site, const float* in, size_
 // the key-blocked kernels (attention_long.h) take this sequence length: head_dim 64, past the LDS-resident instances, up to 1024 keys
 static inline bool attn_long_has(int N, int hd) { return hd == 64 && N >= ATTN_LONG_MIN && N <= ATTN_LONG_MAX; }
 
+// A key mask of a launch_attention call (attention_long.h::attn_long_masked_kernel has the format): dev = the visible-bit words in HBM, (N + 31) / 32 per sample,
+// sample b's at dev + b * stride (stride 0: one mask shared by the call); host = the same words on the host, which is where "key 0 is visible" is checked.
+struct AttnKeyMask {
+    const uint32_t* dev = nullptr;
+    int stride = 0;
+    const uint32_t* host = nullptr;
+};
+
+// A masked call always takes the two key-blocked kernels, at any N from 1 to 1024 (head_dim 64): they are the only ones that carry a mask, so a masked row's
+// bits do not depend on which side of 288 keys the sequence falls.  Everything else about a masked call is refused by name.
+template <typename T>
+static int launch_attention_masked(hipStream_t stream, const T* qkv, T* out, int B, int N, int D, int heads, int causal, int nq, float out8, f16_t* out3, int outc,
+                                   const AttnKeyMask& km) {
+    const int hd = D / heads;
+    if (causal) return fail("attention: a key mask and the causal mask do not combine (the masked kernels have no causal instance)");
+    if (out8 != 0.f || outc || out3) return fail("attention: a key mask goes with the plain output only (no e4m3, [hi | x4 | dx4] or (hi, lo, hi) form)");
+    if (hd != 64) return fail("attention: the key-masked kernels need head_dim 64, got " + std::to_string(hd));
+    if (N < 1 || N > ATTN_LONG_MAX) return fail("attention: sequence too long for the key-masked kernels (" + std::to_string(N) + " > 1024 keys)");
+    if (D & 3) return fail("attention: the key-masked kernels need a width that is a multiple of 4");
+    if (!km.host || km.stride < 0) return fail("attention: a key mask needs its words on the host too (key 0 is checked there)");
+    for (int b = 0; b < (km.stride ? B : 1); ++b)
+        if (!(km.host[(size_t)b * km.stride] & 1u)) return fail("attention: key 0 is hidden in the mask of sample " + std::to_string(b) + " (it must be visible)");
+    const float scale = 1.0f / sqrtf((float)hd);
+    if constexpr (sizeof(T) == 2) {
+        auto kern = attn_long_masked_kernel<T>;
+        ARP_HIP_OK(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, ATTN_LONG_LDS));
+        const int ntiles = ((nq + 15) / 16 + 3) / 4;
+        const int qsplit = B * heads < 128 ? ntiles : 1;
+        hipLaunchKernelGGL(kern, dim3(B * heads, qsplit), dim3(256), ATTN_LONG_LDS, stream, qkv, out, N, D, heads, scale, nq, km.dev, km.stride);
+    } else {
+        auto kern = attn_long_f32_masked_kernel<ATTN_LONG_F32_Q>;
+        ARP_HIP_OK(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, ATTN_LONG_F32_LDS));
+        hipLaunchKernelGGL(kern, dim3(B * heads, (nq + ATTN_LONG_F32_Q - 1) / ATTN_LONG_F32_Q), dim3(ATTN_LONG_F32_Q), ATTN_LONG_F32_LDS, stream, qkv, out, N, D,
+                           heads, scale, nq, km.dev, km.stride);
+    }
+    ARP_HIP_OK(hipGetLastError());
+    return 0;
+}
+
 template <typename T>
 static int launch_attention(hipStream_t stream, int impl, const T* qkv, T* out, int B, int N, int D, int heads, int causal, int nq = 0, float out8 = 0.f,
-                            f16_t* out3 = nullptr, int outc = 0) {  // out3 (T = float, the f32-MFMA kernel only): (hi, lo, hi) binary16 rows instead of f32
+                            f16_t* out3 = nullptr, int outc = 0,  // out3 (T = float, the f32-MFMA kernel only): (hi, lo, hi) binary16 rows instead of f32
                                                                     // outc (T = f16, the MFMA kernel only): [hi | x4 | dx4] rows (ARP_MODE_F16C)
+                            const AttnKeyMask* mask = nullptr) {    // a key mask: the key-blocked kernels' masked instances, whatever impl says
     const int hd = D / heads;
     if (nq <= 0 || nq > N) nq = N;  // query rows produced per sample
+    if (mask && !mask->dev) return fail("attention: a key mask without its device words");
+    if (mask) return launch_attention_masked<T>(stream, qkv, out, B, N, D, heads, causal, nq, out8, out3, outc, *mask);
     const float scale = 1.0f / sqrtf((float)hd);
     if constexpr (sizeof(T) == 2) {
         if (impl == 0 && hd == 64) {
@@ -425,11 +467,11 @@ static int tower_attn_fp8(TowerCtx& c, const TowerW& tw, const LayerW& L, const 
 // ln_1 output -> attention output: the fused kernel where the geometry allows it, else projection + attention kernel
 template <typename T, int SITE>
 static int tower_qkv_attention(TowerCtx& c, const TowerW& tw, const LayerW& L, const char* s_qkv, const char* s_attn, const char* s_fused, const T* h,
-                               T* qkv, T* ao, int B, int N, int causal, int nq) {
+                               T* qkv, T* ao, int B, int N, int causal, int nq, const AttnKeyMask* mask = nullptr) {
     const int D = tw.width, M = B * N;
     if constexpr (sizeof(T) == 2) {
         // (with <= SKINNY_MAX_M rows the fused kernel is 12-60 workgroups walking K one round trip at a time: 18 us per block at one frame)
-        if (c.qkv_fused && L.w_in_hm && c.attn_impl == 0 && qkv_attn_supported(N, D, tw.heads, (int)sizeof(T)) && !c.skinny) {
+        if (c.qkv_fused && L.w_in_hm && c.attn_impl == 0 && qkv_attn_supported(N, D, tw.heads, (int)sizeof(T)) && !c.skinny && !mask) {  // (the fused kernel carries no key mask)
             QkvAttnArgs q;
             q.A = h; q.W = L.w_in_hm; q.bias = L.b_in_hm; q.out = ao;
             q.B = B; q.N = N; q.K = D; q.heads = tw.heads; q.lda = D; q.ldw = D; q.ldo = D; q.fpt = 0; q.nq = nq; q.causal = causal; q.scale = 0.f;
@@ -439,7 +481,7 @@ static int tower_qkv_attention(TowerCtx& c, const TowerW& tw, const LayerW& L, c
     }
     ARP_TRY((tower_gemm<T, T, ACT_NONE, false, SITE>(c, s_qkv, h, L.w_in, L.b_in, nullptr, qkv, M, 3 * D, D)));
     ProfScope ps(*c.prof, c.stream, s_attn);
-    return launch_attention<T>(c.stream, c.attn_impl, qkv, ao, B, N, D, tw.heads, causal, nq);
+    return launch_attention<T>(c.stream, c.attn_impl, qkv, ao, B, N, D, tw.heads, causal, nq, 0.f, nullptr, 0, mask);
 }
 
 constexpr float FP8_S_H = 32.f, FP8_S_G = 16.f;  // activation scales of the fp8 MLP: LayerNorm output, QuickGELU output
@@ -496,7 +538,7 @@ static inline int tower_split_of(int M, int D, int K) {
 // SB: site-id base so that every call site is its own kernel instantiation in a rocprof trace.
 template <typename T, int ACT, int SB>
 static int run_blocks(TowerCtx& c, const TowerW& tw, const char* tag, float* x, T* h, T* qkv, T* ao, T* fc, int B, int N, int causal,
-                      float eps, float* stats = nullptr) {
+                      float eps, float* stats = nullptr, const AttnKeyMask* mask = nullptr) {  // mask: a key mask for every block's attention (throughput and latency path alike)
     const int D = tw.width, M = B * N;
     const std::string t(tag);
     const std::string s_ln1 = t + ".ln_1", s_qkv = t + ".qkv", s_attn = t + ".attn", s_out = t + ".out_proj", s_ln2 = t + ".ln_2",
@@ -517,7 +559,7 @@ static int run_blocks(TowerCtx& c, const TowerW& tw, const char* tag, float* x, 
             ARP_TRY((tower_gemm<T, T, ACT_NONE, false, SB + SITE_QKV>(c, s_qkv.c_str(), h, L.w_in_f, L.d_in, nullptr, qkv, M, 3 * D, D, &cons)));
             {
                 ProfScope ps(*c.prof, c.stream, s_attn.c_str());
-                ARP_TRY(launch_attention<T>(c.stream, c.attn_impl, qkv, ao, B, N, D, tw.heads, causal));
+                ARP_TRY(launch_attention<T>(c.stream, c.attn_impl, qkv, ao, B, N, D, tw.heads, causal, 0, 0.f, nullptr, 0, mask));
             }
             ARP_TRY((tower_gemm<T, float, ACT_NONE, true, SB + SITE_OUT>(c, s_out.c_str(), ao, L.w_out, L.b_out, x, x, M, D, D, &prod)));
             cons.c = L.c_fc;
@@ -575,7 +617,7 @@ static int run_blocks(TowerCtx& c, const TowerW& tw, const char* tag, float* x, 
                 ARP_TRY(consumer(s_qkv.c_str(), L.w_in_f, L.d_in, L.c_in, qkv, 3 * D, ACT_NONE));
                 {
                     ProfScope ps(*c.prof, c.stream, s_attn.c_str());
-                    ARP_TRY(launch_attention<T>(c.stream, c.attn_impl, qkv, ao, B, N, D, tw.heads, causal));
+                    ARP_TRY(launch_attention<T>(c.stream, c.attn_impl, qkv, ao, B, N, D, tw.heads, causal, 0, 0.f, nullptr, 0, mask));
                 }
                 ARP_TRY(producer(s_out.c_str(), ao, L.w_out, L.b_out, D));
                 ARP_TRY(consumer(s_fc1.c_str(), L.w_fc_f, L.d_fc, L.c_fc, fc, 4 * D, ACT));
@@ -585,7 +627,7 @@ static int run_blocks(TowerCtx& c, const TowerW& tw, const char* tag, float* x, 
             }
             if (lat && !(c.cls_only_last && i == tw.layers - 1 && N > 1)) {
                 if (!h_ready) ARP_TRY(tower_layernorm<T>(c, s_ln1.c_str(), x, D, h, D, L.ln1_w, L.ln1_b, M, D, eps));
-                ARP_TRY((tower_qkv_attention<T, SB + SITE_QKV>(c, tw, L, s_qkv.c_str(), s_attn.c_str(), s_qa.c_str(), h, qkv, ao, B, N, causal, 0)));
+                ARP_TRY((tower_qkv_attention<T, SB + SITE_QKV>(c, tw, L, s_qkv.c_str(), s_attn.c_str(), s_qa.c_str(), h, qkv, ao, B, N, causal, 0, mask)));
                 ARP_TRY(tower_gemm_split_ln<T>(c, s_out.c_str(), s_red2.c_str(), ao, L.w_out, L.b_out, x, M, D, D, S_out, h, L.ln2_w, L.ln2_b, eps));
                 ARP_TRY((tower_gemm<T, T, ACT, false, SB + SITE_FC1>(c, s_fc1.c_str(), h, L.w_fc, L.b_fc, nullptr, fc, M, 4 * D, D)));
                 const LayerW* nx = i + 1 < tw.layers ? &tw.L[i + 1] : nullptr;
@@ -602,10 +644,10 @@ static int run_blocks(TowerCtx& c, const TowerW& tw, const char* tag, float* x, 
             const int ND = N * D;  // row stride of the class-token rows inside the [B*N, D] buffers
             if (qkv_ready) {
                 ProfScope ps(*c.prof, c.stream, s_attn1.c_str());
-                ARP_TRY(launch_attention<T>(c.stream, c.attn_impl, qkv, ao, B, N, D, tw.heads, causal, 1));
+                ARP_TRY(launch_attention<T>(c.stream, c.attn_impl, qkv, ao, B, N, D, tw.heads, causal, 1, 0.f, nullptr, 0, mask));
             } else {
                 if (!h_ready) ARP_TRY(tower_layernorm<T>(c, s_ln1.c_str(), x, D, h, D, L.ln1_w, L.ln1_b, M, D, eps));  // K and V need every token
-                ARP_TRY((tower_qkv_attention<T, SB + SITE_QKV>(c, tw, L, s_qkv.c_str(), s_attn1.c_str(), s_qa1.c_str(), h, qkv, ao, B, N, causal, 1)));
+                ARP_TRY((tower_qkv_attention<T, SB + SITE_QKV>(c, tw, L, s_qkv.c_str(), s_attn1.c_str(), s_qa1.c_str(), h, qkv, ao, B, N, causal, 1, mask)));
             }
             ARP_TRY((tower_gemm<T, float, ACT_NONE, true, SB + SITE_OUT>(c, s_out1.c_str(), ao, L.w_out, L.b_out, x, x, B, D, D, nullptr, ND, ND, ND)));
             ARP_TRY(tower_layernorm<T>(c, s_ln21.c_str(), x, ND, h, D, L.ln2_w, L.ln2_b, B, D, eps));
@@ -616,7 +658,7 @@ static int run_blocks(TowerCtx& c, const TowerW& tw, const char* tag, float* x, 
         }
         bool attn_done = false;
         if constexpr (sizeof(T) == 2) {
-            if (c.fp8_attn && L.w_in8 && c.attn_impl == 0 && (D % 128) == 0 && attn_mfma_has(N, D / tw.heads) &&
+            if (!mask && c.fp8_attn && L.w_in8 && c.attn_impl == 0 && (D % 128) == 0 && attn_mfma_has(N, D / tw.heads) &&
                 !(c.qkv_fused && L.w_in_hm && qkv_attn_supported(N, D, tw.heads, (int)sizeof(T)))) {
                 const std::string s_ln18 = t + ".ln_1_fp8", s_qkv8 = t + ".qkv_fp8", s_attn8 = t + ".attn_out8", s_out8 = t + ".out_proj_fp8";
                 ARP_TRY((tower_attn_fp8<T, SB>(c, tw, L, s_ln18.c_str(), s_qkv8.c_str(), s_attn8.c_str(), s_out8.c_str(), x, h, qkv, ao, B, N, causal, eps)));
@@ -625,7 +667,7 @@ static int run_blocks(TowerCtx& c, const TowerW& tw, const char* tag, float* x, 
         }
         if (!attn_done) {
             ARP_TRY(tower_layernorm<T>(c, s_ln1.c_str(), x, D, h, D, L.ln1_w, L.ln1_b, M, D, eps));
-            ARP_TRY((tower_qkv_attention<T, SB + SITE_QKV>(c, tw, L, s_qkv.c_str(), s_attn.c_str(), s_qa.c_str(), h, qkv, ao, B, N, causal, 0)));
+            ARP_TRY((tower_qkv_attention<T, SB + SITE_QKV>(c, tw, L, s_qkv.c_str(), s_attn.c_str(), s_qa.c_str(), h, qkv, ao, B, N, causal, 0, mask)));
             ARP_TRY((tower_gemm<T, float, ACT_NONE, true, SB + SITE_OUT>(c, s_out.c_str(), ao, L.w_out, L.b_out, x, x, M, D, D)));
         }
         if (sizeof(T) == 2 && c.fp8_mlp && L.w_fc8 && (D % 128) == 0) {

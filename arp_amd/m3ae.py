@@ -35,6 +35,10 @@ class EncoderConfig:
         """tokens of one (frame, goal) pair in :meth:`M3AEEncoder.forward_gc_representations`: class token + both frames' patches"""
         return 2 * (self.img_res // self.patch) ** 2 + 1
 
+    def text_tokens(self, L):
+        """tokens of one frame with an instruction of ``L`` tokens (:meth:`M3AEEncoder.forward_representation` with ``text``): class token + patches + L"""
+        return self.tokens + int(L)
+
 
 def flops_per_frame(cfg):
     n, d = cfg.tokens, cfg.width
@@ -63,12 +67,30 @@ class M3AEEncoder:
             check(lib.arp_enc_load_weight(h, name.encode(), _ffi.as_ptr(a, C.c_float), shape, a.ndim))
         check(lib.arp_enc_finalize_weights(h))
 
-    def forward_representation(self, images):
+    def forward_representation(self, images, text=None, text_padding_mask=None):
+        """Without ``text``: the image-only call, ``[n, tokens, width]``.  With ``text`` (InstructRL's call, arp_dt/BC.py:283-321): int token ids ``[L]`` (one
+        instruction for every frame) or ``[n, L]``, ``text_padding_mask`` of the same shape with > 0 = padded (default: nothing padded) ->
+        ``[n, 1 + P + L, width]``; padded text keys are out of every softmax.  Needs the two text weights in ``params``
+        (``synth_policy.add_m3ae_text_params`` for seeded ones).  Modes f32 / f16 / bf16 / f16x3; f16c raises."""
         x = np.require(np.asarray(images, dtype=np.float32), requirements="C")
         if x.ndim != 4 or x.shape[1:] != (self.cfg.img_res, self.cfg.img_res, 3):
             raise ValueError(f"images must be float [n, {self.cfg.img_res}, {self.cfg.img_res}, 3]")
-        out = np.empty((x.shape[0], self.cfg.tokens, self.cfg.width), np.float32)
-        check(lib.arp_enc_forward(self._h, _ffi.as_ptr(x, C.c_float), x.shape[0], _ffi.as_ptr(out, C.c_float)))
+        if text is None:
+            if text_padding_mask is not None:
+                raise ValueError("text_padding_mask without text")
+            out = np.empty((x.shape[0], self.cfg.tokens, self.cfg.width), np.float32)
+            check(lib.arp_enc_forward(self._h, _ffi.as_ptr(x, C.c_float), x.shape[0], _ffi.as_ptr(out, C.c_float)))
+            return out
+        tok = np.require(np.asarray(text, dtype=np.int32), requirements="C")
+        if tok.ndim not in (1, 2) or tok.shape[-1] < 1 or (tok.ndim == 2 and tok.shape[0] != x.shape[0]):
+            raise ValueError("text must be int [L] or [n, L]")
+        mask = np.zeros(tok.shape, np.float32) if text_padding_mask is None else np.require(np.asarray(text_padding_mask, dtype=np.float32), requirements="C")
+        if mask.shape != tok.shape:
+            raise ValueError("text_padding_mask must have the shape of text")
+        L = tok.shape[-1]
+        out = np.empty((x.shape[0], self.cfg.text_tokens(L), self.cfg.width), np.float32)
+        check(lib.arp_enc_forward_text(self._h, _ffi.as_ptr(x, C.c_float), x.shape[0], _ffi.as_ptr(tok, C.c_int32), _ffi.as_ptr(mask, C.c_float), L,
+                                       int(tok.ndim == 2), _ffi.as_ptr(out, C.c_float)))
         return out
 
     def forward_gc_representations(self, images, goals):

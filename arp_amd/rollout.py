@@ -41,10 +41,13 @@ class RolloutSession:
     (the reference fixes it per episode, rollout_procgen.py:94).  With a GCBC trainer a step encodes the new (frame, goal) pairs; with an ARP-DT trainer and a
     plain :class:`arp_amd.clip.ClipLabeller` (no prompts needed) the reward is ``clip_goal_conditioned``, ``-||f(frame) - f(goal)||`` on the device, the goal's
     feature computed once per reset; ``use_crop`` is then refused.  Without the flag a GCBC trainer is refused, as ever.
+    ``instruct=(tokens, text_padding_mask)`` (``arp_rollout_create_text``): model BC as the reference rolls it out -- InstructRL, with the game's instruction
+    (int ids ``[L]`` or ``[1, L]``, mask > 0 = padded, or None).  A step encodes the new frames with the encoder's image + text pass; the encoder is
+    ``encoder``, or the one the trainer carries from ``attach_encoder(enc, instruct=...)``, and must hold the text weights.
     """
 
     def __init__(self, trainer, reward_model=None, n_envs=1, return_to_go=100.0, scale=100.0, reward_min=0.0, use_normalize=False, lut=None, encoder=None,
-                 goal_conditioned=False):
+                 goal_conditioned=False, instruct=None):
         from . import _ffi, dataset
         from .finetune import FinetunedClip
         self._ffi = _ffi
@@ -58,7 +61,14 @@ class RolloutSession:
         h = C.c_void_p()
         rm = reward_model._h if reward_model is not None and not finetuned else None
         self.goal_conditioned = bool(goal_conditioned)
-        if goal_conditioned:
+        if instruct is not None:
+            from .train import _one_instruction
+            if goal_conditioned or reward_model is not None:
+                raise _ffi.ArpError("rollout: instruct= is model BC's session: no goal frames, no reward model (BC reads no return-to-go)")
+            tok, mask = _one_instruction(*instruct) if isinstance(instruct, (tuple, list)) else _one_instruction(instruct)
+            _ffi.check(_ffi.lib.arp_rollout_create_text(trainer._h, encoder._h if encoder is not None else None, int(n_envs), res, res,
+                                                        _ffi.as_ptr(tok, C.c_int32), _ffi.as_ptr(mask, C.c_float), len(tok), C.byref(h)))
+        elif goal_conditioned:
             if finetuned:
                 raise _ffi.ArpError("rollout: create_gc takes a plain labelling handle: the fine-tuned goal reward stays with the host function")
             _ffi.check(_ffi.lib.arp_rollout_create_gc(trainer._h, encoder._h if encoder is not None else None, rm, int(n_envs), res, res, float(scale), C.byref(h)))

@@ -106,6 +106,17 @@ def m3ae_params(cfg, seed=0, dtype=np.float32):
     return P
 
 
+def add_m3ae_text_params(P, cfg, vocab=30522, seed=0, dtype=np.float32):
+    """A copy of the encoder tree ``P`` with the two seeded tensors of the text branch (m3ae/model.py:340-345, 393-397): ``text_embedding/embedding``
+    ``[vocab, width]`` (unit variance: text rows of the size of the seeded patch embeddings, so that an instruction moves the encoding) and
+    ``encoder_text_type_embedding`` (0.02, as the image type embedding).  A generator of its own: what :func:`m3ae_params` returns does not change."""
+    rng = np.random.default_rng([seed, 0x7e47])
+    out = dict(P)
+    out["text_embedding/embedding"] = rng.standard_normal((int(vocab), cfg.width)).astype(dtype)
+    out["encoder_text_type_embedding"] = (0.02 * rng.standard_normal((1, 1, cfg.width))).astype(dtype)
+    return out
+
+
 def normalized_frames(n, res=256, seed=0, dtype=np.float32):
     """Frames as the training pipeline hands them to the encoder: float NHWC, normalised with the Procgen
     statistics of the reference's augmentation (main_procgen.py:232-276)."""

@@ -217,13 +217,28 @@ class PolicyTrainer:
         check(lib.arp_dt_val_step(self._h, _ffi.as_ptr(m, C.c_float)))
         return {"loss": float(m[0]), "trans_loss": float(m[1]), "return_loss": float(m[2]), "acc": float(m[3])}
 
-    def attach_encoder(self, encoder):
+    def attach_encoder(self, encoder, instruct=None, text_padding_mask=None):
         """Put the frozen M3AE encoder (arp_amd.m3ae.M3AEEncoder) inside the step: the boundary then is the
-        reference's own -- batch["image"] holds frames, not encodings (ARPDT.py:413-462).  Refused for model BC: the reference's InstructRL
-        encoder reads the instruction's text tokens beside the frame (BC.py:286-321), this one is image-only.  Accepted for model GCBC, whose encoder call
-        reads frames and goal frames alone (GCBC.py:462-468): ``cfg.enc_tokens`` must be the encoder's ``gc_tokens``."""
-        check(lib.arp_dt_attach_encoder(self._h, encoder._h))
-        self._encoder = encoder
+        reference's own -- batch["image"] holds frames, not encodings (ARPDT.py:413-462).  Model BC (InstructRL) needs ``instruct``: its encoder call reads
+        the instruction's text tokens beside the frame (BC.py:286-321), so without one the image-only encoder is refused.  ``instruct``: int token ids
+        ``[L]``, ``[1, L]`` or ``[B, L]`` with all rows equal, ``text_padding_mask`` likewise (> 0 = padded; default: nothing padded) -- ONE instruction, the
+        game's, stored on the handle (``arp_dt_attach_text_encoder``); ``cfg.enc_tokens`` must be the encoder's ``text_tokens(L)`` and the encoder must carry
+        the text weights.  Every frames batch of the handle is then encoded with the text pass.  Accepted without ``instruct`` for model GCBC, whose
+        encoder call reads frames and goal frames alone (GCBC.py:462-468): ``cfg.enc_tokens`` must be the encoder's ``gc_tokens``."""
+        if instruct is None:
+            if text_padding_mask is not None:
+                raise ValueError("text_padding_mask without instruct")
+            check(lib.arp_dt_attach_encoder(self._h, encoder._h))
+            self._encoder = encoder
+            return
+        tok, mask = _one_instruction(instruct, text_padding_mask)
+        check(lib.arp_dt_attach_text_encoder(self._h, encoder._h, _ffi.as_ptr(tok, C.c_int32), _ffi.as_ptr(mask, C.c_float), len(tok)))
+        self._encoder, self._instruct = encoder, (tok, mask)
+
+    def check_instruction(self, batch):
+        """A BC batch dict may carry the reference's keys ``"instruct"`` and ``"text_padding_mask"`` (main_procgen.py:547-553): with an instruction attached
+        they must repeat it on every row -- the encoder pass uses the attached one."""
+        _check_instruction(getattr(self, "_instruct", None), batch)
 
     # -- batches named by row indices of a device-resident dataset (arp_amd.dataset.DeviceDataset) -----------------------------------
     def attach_dataset(self, ds, use_encodings=False):
@@ -292,8 +307,8 @@ class PolicyTrainer:
         (frame, goal) pairs (``arp_dt_set_batch_images_goal``) and reads no return-to-go."""
         if goals is None and self.gcbc:
             raise _ffi.ArpError("model GCBC encodes (frame, goal) pairs: set_batch_images needs goals=")
-        if goals is None and rtg is None:
-            raise ValueError("rtg is None (only a goal batch of model GCBC takes no return-to-go)")
+        if goals is None and rtg is None and not self.bc:
+            raise ValueError("rtg is None (only model BC and a goal batch of model GCBC take no return-to-go)")
         images = np.require(np.asarray(images, dtype=np.float32), requirements="C")
         action = np.require(np.asarray(action, dtype=np.int32), requirements="C")
         B, T = action.shape
@@ -303,14 +318,15 @@ class PolicyTrainer:
                 raise ValueError(f"batch shapes: images {images.shape}, goals {goals.shape}, action {action.shape}")
             check(lib.arp_dt_set_batch_images_goal(self._h, _ffi.as_ptr(images, C.c_float), _ffi.as_ptr(goals, C.c_float), _ffi.as_ptr(action, C.c_int32), B))
         else:
-            rtg = np.require(np.asarray(rtg, dtype=np.float32), requirements="C")
-            if images.shape[:2] != (B, T) or rtg.size != B * T or T != self.cfg.window:
-                raise ValueError(f"batch shapes: images {images.shape}, action {action.shape}, rtg {rtg.shape}")
-            check(lib.arp_dt_set_batch_images(self._h, _ffi.as_ptr(images, C.c_float), _ffi.as_ptr(action, C.c_int32), _ffi.as_ptr(rtg, C.c_float), B))
+            if images.shape[:2] != (B, T) or T != self.cfg.window:
+                raise ValueError(f"batch shapes: images {images.shape}, action {action.shape}")
+            rtg, rp = self._rtg(rtg, B, T)  # (model BC: None / NULL)
+            check(lib.arp_dt_set_batch_images(self._h, _ffi.as_ptr(images, C.c_float), _ffi.as_ptr(action, C.c_int32), rp, B))
         self._B = B
 
     def classify(self, batch, use_symlog=None):
-        """:func:`classify_batch` with this trainer's facts."""
+        """:func:`classify_batch` with this trainer's facts (and, model BC with an instruction attached, :meth:`check_instruction`)."""
+        _check_instruction(getattr(self, "_instruct", None), batch)
         return classify_batch(batch, encoder=self._encoder is not None, gcbc=self.gcbc, use_symlog=self.cfg.use_symlog if use_symlog is None else use_symlog)
 
     def stage_batch(self, b, slot=None):
@@ -453,6 +469,33 @@ def symlog(x):
 def is_index_batch(batch):
     """A batch that names rows of an attached device-resident dataset: a dict whose only key is ``"index"``."""
     return isinstance(batch, dict) and set(batch) == {"index"}
+
+
+def _one_instruction(instruct, text_padding_mask=None):
+    """(tokens int32 [L], mask f32 [L]) of ``instruct`` given as ``[L]``, ``[1, L]`` or ``[B, L]`` with all rows equal (the mask likewise; None: nothing padded).
+    Rows that differ are refused: BC.py:290-291 tiles the instructions with ``jnp.tile(text, (T, 1))``, which pairs frame row i of the ``[B * T]`` frames with
+    instruction ``i mod B``, not ``i // T`` -- with differing rows the reference itself feeds frames the wrong instruction, so only one instruction per
+    batch is meaningful."""
+    tok = np.asarray(_first_view(instruct))
+    mask = np.zeros(tok.shape, np.float32) if text_padding_mask is None else np.asarray(_first_view(text_padding_mask), np.float32)
+    if tok.ndim not in (1, 2) or mask.shape != tok.shape or tok.shape[-1] < 1:
+        raise ValueError(f"instruct must be int [L], [1, L] or [B, L] and text_padding_mask of its shape: {tok.shape}, {mask.shape}")
+    if tok.ndim == 2:
+        if (tok != tok[:1]).any() or ((mask > 0) != (mask[:1] > 0)).any():
+            raise _ffi.ArpError("instruct rows differ: one instruction per batch (BC.py:290-291 tiles them with jnp.tile(text, (T, 1)), pairing frame row i with "
+                                "instruction i mod B, not i // T, so the reference itself is only meaningful with one)")
+        tok, mask = tok[0], mask[0]
+    return np.require(tok.astype(np.int32), requirements="C"), np.require(mask.astype(np.float32), requirements="C")
+
+
+def _check_instruction(attached, batch):
+    """:meth:`PolicyTrainer.check_instruction`: ``attached`` is the (tokens, mask) of attach_encoder(instruct=...), or None"""
+    if attached is None or not isinstance(batch, dict) or batch.get("instruct") is None:
+        return
+    tok, mask = _one_instruction(batch["instruct"], batch.get("text_padding_mask"))
+    if tok.shape != attached[0].shape or (tok != attached[0]).any() or ((mask > 0) != (attached[1] > 0)).any():
+        raise _ffi.ArpError('batch["instruct"] / batch["text_padding_mask"] differ from the instruction attached with attach_encoder(instruct=...): a handle '
+                            "trains one game, one instruction")
 
 
 def is_index_pair_batch(batch):
@@ -701,7 +744,10 @@ def prefetch_to_device(iterator, size, trainer, *, rank=0, world=1, device_axis=
                     return
                 part = shard_batch(batch, rank, world, device_axis)
                 images = trainer.stage_batch(trainer.classify(part), slot)
-                if images and os.environ.get("ARP_DT_ENCODE_AHEAD", "1") != "0" and os.environ.get("ARP_DT_ENC_EAGER", "1") != "0":
+                # (model BC with its instruction attached: off unless asked for -- measured 0.61 ms lower than the arm without it, inside that arm's 1.30 ms
+                #  spread of round medians: profiles/instructrl_timing.txt; ARP_DT_ENCODE_AHEAD=1 turns it on)
+                ahead_default = "0" if getattr(trainer, "_instruct", None) is not None else "1"
+                if images and os.environ.get("ARP_DT_ENCODE_AHEAD", ahead_default) != "0" and os.environ.get("ARP_DT_ENC_EAGER", "1") != "0":
                     trainer.encode_ahead(slot)  # the frozen encoder's pass for this batch runs beside the step that is reading the OTHER slot
                 ready.put(DeviceBatch(trainer, slot, lambda s=slot: free.put(s)))
             ready.put(None)

@@ -430,6 +430,18 @@ int arp_enc_forward(arp_enc* h, const float* images_host, int n, float* out_host
  * exists up to 288 tokens only).  arp_enc_gc_tokens: 2 P + 1. */
 int arp_enc_forward_gc(arp_enc* h, const float* images_host, const float* goals_host, int n, float* out_host);
 int arp_enc_gc_tokens(arp_enc* h);
+/* The image + text call (forward_representation(image, text, text_padding_mask), arp_dt/models/m3ae/model.py:471-496; InstructRL's encoder call, arp_dt/BC.py:283-321):
+ * n frames f32 NHWC [n,res,res,3] and an instruction of L token ids -> f32 [n, 1 + P + L, width].  One sequence per frame: class token, the frame's P patches, then
+ * row 1 + P + i = text_embedding[tokens[i]] + get_1d_sincos_pos_embed(width, L)[i] + encoder_text_type_embedding.  mask f32, > 0 = padded (the reference's
+ * convention): a padded text key is taken out of every softmax (model.py:247-250) -- as one bit per key for the key-masked attention kernels
+ * (csrc/attention_long.h), which every text call runs on whatever its length; class and patch keys are always visible.  tokens (int32) and mask are [L], shared by
+ * the n frames (per_row = 0), or [n, L] (per_row = 1).  Needs the optional weights "text_embedding/embedding" [vocab, width] and "encoder_text_type_embedding"
+ * [1,1,width] (arp_enc_load_weight; vocab = the loaded tensor's first dimension) -- without both the call returns an error, and with them the other two calls are
+ * unchanged bit for bit.  Ids outside [0, vocab) are refused.  1 + P + L <= 1024, head_dim 64.  Modes f32, f16, bf16, f16x3 (the exact-f32 masked attention + the
+ * split pass); ARP_MODE_F16C returns an error.  max_frames, the part streams and the latency path apply as in arp_enc_forward, the latter on n (1 + P + L) rows.
+ * arp_enc_text_tokens: 1 + P + L. */
+int arp_enc_forward_text(arp_enc* h, const float* images_host, int n, const int32_t* tokens, const float* mask, int L, int per_row, float* out_host);
+int arp_enc_text_tokens(arp_enc* h, int L);
 /* Part streams (round 6): a call's frames are encoded as `n_streams` contiguous parts (1..4, default 2), part 0 on the caller's stream and the others on
  * streams of their own, so that one part's memory-bound kernels and GEMM grid tails run beside another part's GEMMs -- as arp_clip_cfg.n_streams does
  * for the labelling pass.  first_part_frames > 0: that many frames in part 0 of two; 0: the default cut (15/32 of the frames: parts that end at different times
@@ -447,6 +459,14 @@ int arp_enc_profile_json(arp_enc* h, char* buf, int buf_len);
 /* Put the frozen encoder INSIDE the policy step: after attaching, arp_dt_set_batch_images stages raw frames
  * [B,T,res,res,3] f32 and every forward / train step runs the encoder first (on the step's stream). */
 int arp_dt_attach_encoder(arp_dt* h, arp_enc* enc);
+/* InstructRL (model BC) with frames in: attach the encoder for its image + text pass (arp_enc_forward_text) together with ONE instruction, the instruction of
+ * the game being trained -- tokens int32 [L], mask f32 [L] (> 0 = padded).  (BC.encode, arp_dt/BC.py:290-291, tiles the batch's instructions with
+ * jnp.tile(text, (T, 1)), which pairs frame row i with instruction i mod B, not i // T: the reference is only meaningful with one instruction per batch.)
+ * A BC handle only (arp_dt_attach_encoder keeps refusing it; ARP-DT and GCBC handles are refused here); enc_tokens == 1 + P + L (arp_enc_text_tokens) and
+ * enc_dim == width; the encoder must carry the text weights.  Afterwards every frames slot of the handle encodes with the text pass: arp_dt_set_batch_images (rtg
+ * NULL), arp_dt_upload_batch_images_async, arp_dt_encode_ahead, and index batches of frames from a device-resident set -- the same stager, slots and protocol as
+ * the other two models.  The handle owns its copy of the instruction. */
+int arp_dt_attach_text_encoder(arp_dt* h, arp_enc* enc, const int32_t* tokens, const float* mask, int L);
 int arp_dt_set_batch_images(arp_dt* h, const float* images, const int32_t* action, const float* rtg, int B);
 /* Model GCBC's staging slot (synchronous, like arp_dt_set_batch_images): frames and goal frames, both [B,T,res,res,3] f32, and the actions; every forward /
  * train step then runs the goal-conditioned encoder pass (arp_enc_forward_gc's) first.  The goal row is drawn per sample (data_procgen.py:186-189), so the
@@ -534,6 +554,12 @@ int arp_rollout_create_ft(arp_dt* policy, arp_enc* encoder_or_null, arp_clip* to
  * [n, H, W, 3] in host memory; a plain arp_rollout_reset keeps an environment's goal.  arp_rollout_step is refused until every environment has a goal.
  * arp_rollout_read gains "goal" uint8 [E, H, W, 3] and, with the goal reward, "goal_feat" f32 [E, embed]. */
 int arp_rollout_create_gc(arp_dt* policy, arp_enc* encoder_or_null, arp_clip* reward_or_null, int n_envs, int H, int W, float scale, arp_rollout** out);
+/* A session for model BC (InstructRL) WITH the game's instruction: tokens int32 [L], mask f32 [L] (> 0 = padded).  A step encodes the E new frames with the
+ * encoder's image + text pass (arp_enc_forward_text's) under that instruction; the per-position encoding ring stays valid because the instruction is constant
+ * over the episode.  encoder_or_null: the encoder to use, or NULL for the one the policy carries from arp_dt_attach_text_encoder; it must hold the text
+ * weights, and the policy's enc_tokens must be 1 + P + L.  Refused for ARP-DT and GCBC policies.  No reward handle, no return-to-go (BC reads none).  The
+ * existing constructors are unchanged, the image-only BC session (arp_rollout_create_with_encoder) included. */
+int arp_rollout_create_text(arp_dt* policy, arp_enc* encoder_or_null, int n_envs, int H, int W, const int32_t* tokens, const float* mask, int L, arp_rollout** out);
 int arp_rollout_reset_goal(arp_rollout* h, const int32_t* env_ids, int n, const float* rtg0_or_null, const uint8_t* goals_u8 /* [n, H, W, 3] */);
 int arp_rollout_destroy(arp_rollout* h);
 /* start an episode in the n listed environments: return-to-go rtg0[i] (already divided by scale, as :90), episode length 0 */
@@ -657,6 +683,13 @@ int arp_op_attention(int mode, int impl, const float* qkv, float* out, int B, in
 #define ARP_ATTN_OUT_SPLIT3 3
 int arp_op_attention_forms(int mode, int impl, const float* qkv, void* out, size_t out_bytes, int B, int N, int D, int heads, int causal, int nq, int form,
                            float out_scale, int outc);
+/* The same launcher with a KEY MASK (csrc/tower.h::launch_attention_masked -> csrc/attention_long.h: attn_long_masked_kernel in the 16-bit modes,
+ * attn_long_f32_kernel's masked instance in ARP_MODE_F32; head_dim 64, 1 <= N <= 1024).  mask: n_words 32-bit words on the host, one bit per key, 1 = visible,
+ * key k in bit k & 31 of word k >> 5, (N + 31) / 32 words per sample, sample b's words at mask + b * stride (stride 0: one mask shared by the call).  A hidden
+ * key is out of every softmax of its sample.  Key 0 must be visible.  `out` as above (plain rows of the mode's type).  causal and form are passed on to the
+ * launcher, which refuses a masked call that is causal, asks for another output form, has another head_dim or more than 1024 keys. */
+int arp_op_attention_masked(int mode, const float* qkv, void* out, size_t out_bytes, int B, int N, int D, int heads, int causal, int nq, int form,
+                            const uint32_t* mask, int n_words, int stride);
 /* The fused QKV projection + attention kernel (csrc/qkvattn.h; 16-bit modes, head_dim 64, N <= 64, K % 64 == 0): A [B*N, K], in-proj weight W [3 D, K] and
  * bias [3 D] in the reference's order (q | k | v, D = heads * 64) -- the entry builds the head-major operands with the weight loader's own function.
  * out: caller-filled byte buffer as above, rows of D values of the mode's type. */
