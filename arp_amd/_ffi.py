@@ -275,6 +275,7 @@ SIGNATURES = {
     "arp_op_convert_f16c": (_i, [_i, _fp, _vp, C.c_size_t, _vp, C.c_size_t, _i, _i]),
     "arp_op_extract_hi": (_i, [_vp, C.c_size_t, _i, _vp, C.c_size_t, _i, _i]),
     "arp_op_split3": (_i, [_fp, _vp, C.c_size_t, _i, _i]),
+    "arp_op_m3ae_assemble": (_i, [_fp, _fp, _fp, _fp, _fp, _i32p, _i, _i, _i, _i, _i, _i, _i, _fp]),
 }
 
 for _name, (_res, _args) in SIGNATURES.items():

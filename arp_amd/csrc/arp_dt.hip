@@ -100,11 +100,8 @@ struct arp_dt {
     // nothing else queued, beside the step on the other slot
     Stream copy_stream;
     arp_enc* enc = nullptr;   // optional frozen encoder in front (row N1)
-    // model BC behind the image + text encoder (arp_dt_attach_text_encoder): ONE instruction on the handle -- the game being trained -- as the encoder's text pass
-    // takes it: L token ids followed by the visible-bit words of the 1 + P + L keys, in HBM, and the words on the host.  Every frames slot then encodes with it.
-    int text_L = 0;  // > 0: the instruction is set
-    DevBuf text_dev;
-    std::vector<uint32_t> text_words;
+    // model BC behind the image + text encoder (arp_dt_attach_text_encoder): ONE instruction on the handle -- the game being trained.  Every frames slot then encodes with it.
+    EncText text;
     bool use_images = false;
     // The encoder's part streams fork and join around ~150 long kernels: replayed as parallel branches of the step's hipGraph that costs more than it overlaps
     // (1.33 vs 0.99 ms for two short branches), and the encoder's launches are far longer than the host takes to issue them -- so with frames in
@@ -690,11 +687,8 @@ int policy_fused(arp_dt* c, bool do_bwd) {
 // The frozen encoder's pass over the n frames of a slot, on `st`: the goal-conditioned pass where the slot holds goal frames, the image + text pass where the
 // handle carries an instruction (model BC), else the image-only pass.
 int encode_slot_on(arp_dt* c, arp_dt::BatchSlot& b, hipStream_t st, int n) {
-    if (b.goals) return enc_forward_gc_on(c->enc, st, b.img32.as<float>(), b.goal32.as<float>(), n, b.enc32.as<float>());
-    if (c->text_L > 0)
-        return enc_forward_text_on(c->enc, st, b.img32.as<float>(), n, c->text_dev.as<int32_t>(), reinterpret_cast<const uint32_t*>(c->text_dev.as<int32_t>() + c->text_L),
-                                   c->text_words.data(), c->text_L, 0, b.enc32.as<float>());
-    return enc_forward_on(c->enc, st, b.img32.as<float>(), n, b.enc32.as<float>());
+    const EncSeq seq = b.goals ? EncSeq::goal(b.goal32.as<float>()) : c->text.L > 0 ? c->text.seq() : EncSeq{};
+    return enc_forward_on(c->enc, st, b.img32.as<float>(), n, b.enc32.as<float>(), seq);
 }
 // The encoder pass of batch slot `slot` on the encoder stream; after_compute: ordered behind everything on the compute stream (a batch staged synchronously
 // there, and the earlier steps' reads of this slot's enc32); otherwise behind the slot's upload and its last reader.  Caller holds capture_mu.
@@ -1735,7 +1729,7 @@ int arp_dt_set_batch_images(arp_dt* c, const float* images, const int32_t* actio
 }
 
 // Model GCBC: frames and goal frames, both [B, T, res, res, 3] f32, and the actions; the step then runs the goal-conditioned encoder pass
-// (enc_forward_gc_on) where an ARP-DT step runs enc_forward_on.
+// (enc_forward_on with EncSeq::goal) where an ARP-DT step runs the plain one.
 int arp_dt_set_batch_images_goal(arp_dt* c, const float* images, const float* goals, const int32_t* action, int B) {
     if (!c || !images || !goals || !action || B <= 0) return fail("bad argument");
     if (!c->gcbc()) return fail("goal frames belong to model GCBC (ARP_DT_MODEL_GCBC)");
@@ -1796,7 +1790,7 @@ int arp_dt_attach_encoder(arp_dt* c, arp_enc* enc) {
     int tokens = 0, width = 0, res = 0, dev = 0;
     ARP_TRY(enc_geometry(enc, &tokens, &width, &res, &dev));
     // GCBC's encoder call reads no text (GCBC.py:462-468: forward_gc_representations(patch, goal_patch)): one sequence of 2 P + 1 tokens per (frame, goal) pair
-    if (c->gcbc()) ARP_TRY(enc_gc_tokens(enc, &tokens));
+    if (c->gcbc()) ARP_TRY(enc_seq_tokens(enc, EncSeq::goal(), &tokens));
     if (tokens != c->cfg.enc_tokens || width != c->cfg.enc_dim) return fail("encoder geometry does not match enc_tokens / enc_dim");
     if (dev != c->cfg.device) return fail("encoder lives on another device");
     c->enc = enc;
@@ -1812,22 +1806,12 @@ int arp_dt_attach_text_encoder(arp_dt* c, arp_enc* enc, const int32_t* tokens, c
     if (!c->bc() || c->gcbc()) return fail("the image + text encoder belongs to model BC (ARP_DT_MODEL_BC): ARP-DT attaches the image-only encoder, GCBC the goal-conditioned one (arp_dt_attach_encoder)");
     int tokens_n = 0, plain = 0, width = 0, res = 0, dev = 0;
     ARP_TRY(enc_geometry(enc, &plain, &width, &res, &dev));
-    ARP_TRY(enc_text_tokens(enc, L, &tokens_n));
+    ARP_TRY(enc_seq_tokens(enc, EncSeq::text(L), &tokens_n));
     if (tokens_n != c->cfg.enc_tokens || width != c->cfg.enc_dim) return fail("encoder geometry does not match enc_tokens / enc_dim (enc_tokens must be 1 + P + L)");
     if (dev != c->cfg.device) return fail("encoder lives on another device");
     ARP_HIP_OK(hipSetDevice(c->cfg.device));
-    ARP_TRY(enc_text_prepare(enc, L));  // the text weights, the mode, and the position rows on the device before any step (or capture) needs them
-    const int per = (tokens_n + 31) / 32;
-    std::vector<uint32_t> words(per);
-    ARP_TRY(enc_text_words(enc, tokens, mask, 1, L, words.data()));
     ARP_HIP_OK(hipDeviceSynchronize());  // (a re-attach: no pass in flight may still read the instruction about to be replaced)
-    std::vector<int32_t> blob(L + per);
-    memcpy(blob.data(), tokens, (size_t)L * 4);
-    memcpy(blob.data() + L, words.data(), (size_t)per * 4);
-    ARP_TRY(c->text_dev.ensure(blob.size() * 4));
-    ARP_HIP_OK(hipMemcpy(c->text_dev.p, blob.data(), blob.size() * 4, hipMemcpyHostToDevice));
-    c->text_words = std::move(words);
-    c->text_L = L;
+    ARP_TRY(c->text.set(enc, tokens, mask, L));  // the text weights, the mode, and the position rows on the device before any step (or capture) needs them
     c->enc = enc;
     return 0;
 }

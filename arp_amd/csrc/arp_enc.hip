@@ -33,67 +33,17 @@ __global__ __launch_bounds__(256) void patchify_kernel(const float* __restrict__
     store4(out + i, src[0], src[1], src[2], src[3]);
 }
 
-// x[b, 0] = cls;  x[b, 1+p] = pe[b*GG + p] + pos[p]   (pos already holds sincos + type embedding)
-__global__ __launch_bounds__(256) void enc_assemble_kernel(const float* __restrict__ pe, const float* __restrict__ cls,
-                                                           const float* __restrict__ pos, float* __restrict__ x, int rows, int ntok,
-                                                           int D) {
-    const size_t i = ((size_t)blockIdx.x * 256 + threadIdx.x) * 4;
-    if (i >= (size_t)rows * D) return;
-    const int c = (int)(i % D);
-    const size_t row = i / D;
-    const int t = (int)(row % ntok);
-    const size_t b = row / ntok;
-    float v[4];
-    if (t == 0) {
-        load4(cls + c, v);
-    } else {
-        float p4[4];
-        load4(pe + (b * (ntok - 1) + (t - 1)) * D + c, v);
-        load4(pos + (size_t)(t - 1) * D + c, p4);
-        v[0] += p4[0]; v[1] += p4[1]; v[2] += p4[2]; v[3] += p4[3];
-    }
-    store4(x + i, v[0], v[1], v[2], v[3]);
-}
-
-// The goal-conditioned sequence (forward_gc_representations, arp_dt/models/m3ae/model.py:498-525): class token, the frame's GG patches, the goal frame's GG patches;
-// both patch blocks take the same position (+ type) embedding.  pe holds the patch embeddings of the nb frames first, then those of the nb goals:
-//   x[b, 0] = cls;  x[b, 1 + p] = pe[b*GG + p] + pos[p];  x[b, 1 + GG + p] = pe[(nb + b)*GG + p] + pos[p]
-__global__ __launch_bounds__(256) void enc_assemble_gc_kernel(const float* __restrict__ pe, const float* __restrict__ cls, const float* __restrict__ pos,
-                                                              float* __restrict__ x, int nb, int GG, int D) {
-    const int ntok = 2 * GG + 1;
-    const size_t i = ((size_t)blockIdx.x * 256 + threadIdx.x) * 4;
-    if (i >= (size_t)nb * ntok * D) return;
-    const int c = (int)(i % D);
-    const size_t row = i / D;
-    const int t = (int)(row % ntok);
-    const size_t b = row / ntok;
-    float v[4];
-    if (t == 0) {
-        load4(cls + c, v);
-    } else {
-        const int goal = t > GG, p = t - 1 - (goal ? GG : 0);
-        float p4[4];
-        load4(pe + (((goal ? (size_t)nb : 0) + b) * GG + p) * D + c, v);
-        load4(pos + (size_t)p * D + c, p4);
-        v[0] += p4[0]; v[1] += p4[1]; v[2] += p4[2]; v[3] += p4[3];
-    }
-    store4(x + i, v[0], v[1], v[2], v[3]);
-}
-int launch_assemble_gc(hipStream_t stream, const float* pe, const float* cls, const float* pos, float* x, int nb, int GG, int D) {
-    const size_t tot = (size_t)nb * (2 * GG + 1) * D;
-    hipLaunchKernelGGL(enc_assemble_gc_kernel, dim3((unsigned)((tot / 4 + 255) / 256)), dim3(256), 0, stream, pe, cls, pos, x, nb, GG, D);
-    ARP_HIP_OK(hipGetLastError());
-    return 0;
-}
-
-// The image + text sequence (forward_representation with an instruction, arp_dt/models/m3ae/model.py:471-496; BC.encode, arp_dt/BC.py:283-321): class token,
-// the frame's GG patches, the L instruction tokens.  Rows 0 .. GG are enc_assemble_kernel's values, expression for expression; text row i is
-//   x[b, 1 + GG + i] = text_emb[tok[i]] + tpos[i]      (tpos already holds get_1d_sincos_pos_embed(width, L)[i] + the text type embedding)
-// tok: int32 ids, [L] shared by the nb frames (per_row = 0) or [nb, L]; the host has checked them against the vocabulary.
-__global__ __launch_bounds__(256) void enc_assemble_text_kernel(const float* __restrict__ pe, const float* __restrict__ cls, const float* __restrict__ pos,
-                                                                const float* __restrict__ text_emb, const float* __restrict__ tpos,
-                                                                const int32_t* __restrict__ tok, int per_row, float* __restrict__ x, int nb, int GG, int L, int D) {
-    const int ntok = 1 + GG + L;
+// The assembled sequence of a sample (EncSeq, enc_internal.h; arp_dt/models/m3ae/model.py:471-525), f32 [nb, ntok, D], ntok = 1 + GG (+ GG | + L):
+//   x[b, 0] = cls;  x[b, 1 + p] = pe[b*GG + p] + pos[p]                  (pos already holds the 2-D sincos + the image type embedding)
+//   goal:  x[b, 1 + GG + p] = pe[(nb + b)*GG + p] + pos[p]               (pe: the patch embeddings of the nb frames first, then those of the nb goals)
+//   L > 0: x[b, 1 + GG + j] = text_emb[tok[j]] + tpos[j]                 (tpos already holds get_1d_sincos_pos_embed(width, L)[j] + the text type embedding)
+// tok: int32 ids, [L] shared by the nb frames (per_row = 0) or [nb, L]; the host has checked them against the vocabulary.  Never both goal and L > 0.
+// KIND (EncSeq::Kind) is a compile-time argument, so that each kind's instance carries only its own rows' index arithmetic and branches.
+template <int KIND> __global__ __launch_bounds__(256) void enc_assemble_kernel(const float* __restrict__ pe, const float* __restrict__ cls, const float* __restrict__ pos,
+                                                           const float* __restrict__ text_emb, const float* __restrict__ tpos, const int32_t* __restrict__ tok,
+                                                           int per_row, float* __restrict__ x, int nb, int GG, int L_, int D) {
+    constexpr bool goal = KIND == EncSeq::GOAL;
+    const int L = KIND == EncSeq::TEXT ? L_ : 0, ntok = 1 + (goal ? 2 : 1) * GG + L;
     const size_t i = ((size_t)blockIdx.x * 256 + threadIdx.x) * 4;
     if (i >= (size_t)nb * ntok * D) return;
     const int c = (int)(i % D);
@@ -105,11 +55,11 @@ __global__ __launch_bounds__(256) void enc_assemble_text_kernel(const float* __r
         load4(cls + c, v);
     } else {
         float p4[4];
-        if (t <= GG) {
-            load4(pe + (b * GG + (t - 1)) * D + c, v);
-            load4(pos + (size_t)(t - 1) * D + c, p4);
+        const int j = t > GG ? t - 1 - GG : t - 1;  // the row's place in its block: patches, goal patches or instruction
+        if (t <= GG || goal) {
+            load4(pe + (((t > GG ? (size_t)nb : 0) + b) * GG + j) * D + c, v);
+            load4(pos + (size_t)j * D + c, p4);
         } else {
-            const int j = t - 1 - GG;
             const int id = tok[(per_row ? b * L : 0) + j];
             load4(text_emb + (size_t)id * D + c, v);
             load4(tpos + (size_t)j * D + c, p4);
@@ -117,6 +67,15 @@ __global__ __launch_bounds__(256) void enc_assemble_text_kernel(const float* __r
         v[0] += p4[0]; v[1] += p4[1]; v[2] += p4[2]; v[3] += p4[3];
     }
     store4(x + i, v[0], v[1], v[2], v[3]);
+}
+int launch_assemble(hipStream_t stream, const float* pe, const float* cls, const float* pos, const float* text_emb, const float* tpos, const EncSeq& seq, float* x,
+                    int nb, int GG, int D) {
+    // goal rows and text rows both follow seq.kind, as seq.tokens does: a descriptor filled in by hand cannot ask for both
+    const size_t tot = (size_t)nb * seq.tokens(1 + GG) * D;
+    const auto kern = seq.kind == EncSeq::GOAL ? enc_assemble_kernel<EncSeq::GOAL> : seq.kind == EncSeq::TEXT ? enc_assemble_kernel<EncSeq::TEXT> : enc_assemble_kernel<EncSeq::PLAIN>;
+    hipLaunchKernelGGL(kern, dim3((unsigned)((tot / 4 + 255) / 256)), dim3(256), 0, stream, pe, cls, pos, text_emb, tpos, seq.tok_dev, seq.per_row, x, nb, GG, seq.L, D);
+    ARP_HIP_OK(hipGetLastError());
+    return 0;
 }
 
 // ARP_MODE_F16X3: f32 [rows, K] -> binary16 [rows, 3K] = [hi | lo | hi], hi = rn16(x), lo = rn16(x - hi): the A operand of a K-concatenated product against
@@ -182,21 +141,6 @@ struct HostTensor {
     std::vector<int64_t> shape;
 };
 
-// The instruction of an image + text pass as the kernels see it: token ids and visible-bit words (attention_long.h's mask format over the 1 + P + L keys: class
-// and patch keys always visible, text key i visible where the caller's padding mask is <= 0), both in HBM; the words on the host as well (the attention
-// launcher checks key 0 there).  per_row = 0: one instruction for every frame; 1: frame f's ids at tok + f * L, its words at words + f * per.
-struct TextPass {
-    const int32_t* tok = nullptr;
-    const uint32_t* words = nullptr;
-    const uint32_t* words_host = nullptr;
-    int L = 0, per_row = 0, per = 0;
-    TextPass at(int frame) const {  // the pass of the frames from `frame` on
-        TextPass t = *this;
-        if (per_row) { t.tok += (size_t)frame * L; t.words += (size_t)frame * per; t.words_host += (size_t)frame * per; }
-        return t;
-    }
-};
-
 }  // namespace
 
 struct arp_enc {
@@ -235,7 +179,7 @@ struct arp_enc {
     // modes, runs as ONE part on tower.h's latency path -- the W-tiled skinny GEMMs (patch embedding, in_proj, c_fc), out_proj / c_proj as split-K slabs whose
     // reduction kernel adds bias + residual and applies the next LayerNorm.  Only callers that ask for it (enc_forward_on's `latency`: the rollout session, and
     // arp_enc_forward once arp_enc_set_latency turned lat_host on) take it; the training paths never do, whatever their row count.  A goal-conditioned call
-    // (enc_forward_gc_on, arp_enc_forward_gc) follows the same rule on pairs x (2 P + 1) rows: one real pair is 513 rows, measured 1.224 against 1.474 ms per
+    // (EncSeq::GOAL, arp_enc_forward_gc) follows the same rule on pairs x (2 P + 1) rows: one real pair is 513 rows, measured 1.224 against 1.474 ms per
     // GCBC session step with the path on / off (profiles/gc_rollout_timing.txt); two pairs are over SKINNY_MAX_M.
     // Default 514 = two frames at 257 tokens, the largest row count at which the path was measured faster inside a rollout step (ViT-B/16, f16 / bf16:
     // 257 rows 1.10 against 1.56 ms per step, 514 rows 1.39 against 1.69, 771 rows 1.80 against 1.69 -- slower; profiles/rollout_step_timing.txt).
@@ -267,7 +211,6 @@ struct arp_enc {
     Profiler prof;
     int gemm_force = 0;
     int tokens() const { return (cfg.img_res / cfg.patch) * (cfg.img_res / cfg.patch) + 1; }
-    int gc_tokens() const { return 2 * (tokens() - 1) + 1; }  // a (frame, goal) pair: class token + both frames' patches
     size_t esz() const { return (cfg.mode == ARP_MODE_F32 || cfg.mode == ARP_MODE_F16X3) ? 4 : 2; }  // element size of the ACTIVATION buffers
     size_t wsz() const { return cfg.mode == ARP_MODE_F32 ? 4 : 2; }
 };
@@ -378,62 +321,54 @@ int ensure_ws(arp_enc* c, arp_enc::Ws& w, int frames) {
     return 0;
 }
 
-// goal_dev != null (here and in forward_chunk_x3): nb (frame, goal) pairs -- both frame sets through patchify and ONE patch-embedding product of 2 nb GG rows,
-// the goal-conditioned assembly, then the blocks over 2 GG + 1 tokens per sample.  goal_dev == null is the plain pass, launch for launch what it always was.
-// tx != null (here and in forward_chunk_x3; never together with goal_dev): the image + text pass -- the plain pass's patch embedding, the text assembly, then the
-// blocks over 1 + P + L tokens per sample with the instruction's key mask on every attention (tower.h: the key-blocked masked kernels at any length).
-int launch_assemble_text(arp_enc* c, hipStream_t stream, const float* pe, const TextPass& tx, float* x, int nb, int GG, int D) {
-    const size_t tot = (size_t)nb * (1 + GG + tx.L) * D;
-    hipLaunchKernelGGL(enc_assemble_text_kernel, dim3((unsigned)((tot / 4 + 255) / 256)), dim3(256), 0, stream, pe, c->cls, c->pos, c->text_emb, c->text_pos.as<float>(),
-                       tx.tok, tx.per_row, x, nb, GG, tx.L, D);
-    ARP_HIP_OK(hipGetLastError());
-    return 0;
-}
-AttnKeyMask key_mask_of(const TextPass& tx) {
+AttnKeyMask key_mask_of(const EncSeq& seq, int P1) {  // (no instruction: no mask, dev == null)
     AttnKeyMask km;
-    km.dev = tx.words; km.stride = tx.per_row ? tx.per : 0; km.host = tx.words_host;
+    km.dev = seq.words_dev; km.stride = seq.per_row ? seq.words(P1) : 0; km.host = seq.words_host;
     return km;
 }
 
-template <typename T> int forward_chunk(arp_enc* c, arp_enc::Ws& w, hipStream_t stream, const float* img_dev, int nb, float* out_dev, const float* goal_dev,
-                                        const TextPass* tx) {
+// ARP_MODE_F16C runs the plain sequence only
+int f16c_plain_only(const arp_enc* c, const EncSeq& seq) {
+    if (c->cfg.mode != ARP_MODE_F16C) return 0;
+    if (seq.kind == EncSeq::GOAL) return fail("f16c: no goal-conditioned pass (its [hi | x4 | dx4] attention rows exist on the LDS-resident kernel only, <= 288 tokens)");
+    if (seq.kind == EncSeq::TEXT) return fail("f16c: no image + text pass (its [hi | x4 | dx4] attention rows exist on the LDS-resident kernel only, <= 288 tokens)");
+    return 0;
+}
+
+// The front end of every forward_chunk*: the nb frames (a GOAL sequence: then the nb goal frames) -> patch rows at `patches`, typed, or as (hi, lo, hi) binary16
+// triples in one pass (X3: the f16x3 and f16c operand) -> the patch-embedding product against w_emb into w.pe -> the assembled sequences in w.x.
+template <typename T, bool X3> int front_end(arp_enc* c, arp_enc::Ws& w, TowerCtx& t, const float* img_dev, int nb, const EncSeq& seq, T* patches, const void* w_emb) {
     const arp_enc_cfg& k = c->cfg;
-    const int G = k.img_res / k.patch, N = tx ? c->tokens() + tx->L : (goal_dev ? c->gc_tokens() : c->tokens()), D = k.width, KP = k.patch * k.patch * 3;
-    TowerCtx t;
-    t.stream = stream; t.prof = &c->prof; t.attn_impl = k.attn_impl; t.gemm_force = c->gemm_force; t.shared_chip = c->shared_chip;
-    if (sizeof(T) == 2 && c->lat_now) {  // (the patch embedding below then goes through tower_gemm's skinny route where skinny_supported holds)
-        t.skinny = true; t.part = c->lat_part.as<float>(); t.part_floats = c->lat_part.bytes / 4;
-    }
+    const int G = k.img_res / k.patch, KP = k.patch * k.patch * 3, sets = seq.kind == EncSeq::GOAL ? 2 : 1, seg = X3 ? 3 : 1;
+    const size_t tot = (size_t)nb * G * G * KP;
     {
-        ProfScope ps(c->prof, stream, "m3ae.patchify");
-        const size_t tot = (size_t)nb * G * G * KP;
-        hipLaunchKernelGGL((patchify_kernel<T>), dim3((unsigned)((tot / 4 + 255) / 256)), dim3(256), 0, stream, img_dev, w.patches.as<T>(), nb,
-                           k.img_res, k.patch);
-        ARP_HIP_OK(hipGetLastError());
-        if (goal_dev) {
-            hipLaunchKernelGGL((patchify_kernel<T>), dim3((unsigned)((tot / 4 + 255) / 256)), dim3(256), 0, stream, goal_dev, w.patches.as<T>() + tot, nb,
-                               k.img_res, k.patch);
+        ProfScope ps(c->prof, t.stream, "m3ae.patchify");
+        for (int s = 0; s < sets; ++s) {
+            const float* src = s ? seq.goals_dev : img_dev;
+            const dim3 grid((unsigned)((tot / 4 + 255) / 256));
+            if constexpr (X3) hipLaunchKernelGGL(patchify_split3_kernel, grid, dim3(256), 0, t.stream, src, patches + s * seg * tot, nb, k.img_res, k.patch);
+            else hipLaunchKernelGGL((patchify_kernel<T>), grid, dim3(256), 0, t.stream, src, patches + s * tot, nb, k.img_res, k.patch);
             ARP_HIP_OK(hipGetLastError());
         }
     }
-    ARP_TRY((tower_gemm<T, float, ACT_NONE, false, 8 + SITE_PATCH>(t, "m3ae.image_embedding", w.patches.p, c->w_emb, c->b_emb, nullptr, w.pe.p,
-                                                                   (goal_dev ? 2 : 1) * nb * G * G, D, KP)));
-    if (tx) {
-        ProfScope ps(c->prof, stream, "m3ae.assemble");
-        ARP_TRY(launch_assemble_text(c, stream, w.pe.as<float>(), *tx, w.x.as<float>(), nb, G * G, D));
-    } else if (goal_dev) {
-        ProfScope ps(c->prof, stream, "m3ae.assemble");
-        ARP_TRY(launch_assemble_gc(stream, w.pe.as<float>(), c->cls, c->pos, w.x.as<float>(), nb, G * G, D));
-    } else {
-        ProfScope ps(c->prof, stream, "m3ae.assemble");
-        const size_t tot = (size_t)nb * N * D;
-        hipLaunchKernelGGL(enc_assemble_kernel, dim3((unsigned)((tot / 4 + 255) / 256)), dim3(256), 0, stream, w.pe.as<float>(), c->cls, c->pos,
-                           w.x.as<float>(), nb * N, N, D);
-        ARP_HIP_OK(hipGetLastError());
+    ARP_TRY((tower_gemm<T, float, ACT_NONE, false, 8 + SITE_PATCH>(t, "m3ae.image_embedding", patches, w_emb, c->b_emb, nullptr, w.pe.p, sets * nb * G * G, k.width,
+                                                                   seg * KP)));
+    ProfScope ps(c->prof, t.stream, "m3ae.assemble");
+    return launch_assemble(t.stream, w.pe.as<float>(), c->cls, c->pos, c->text_emb, c->text_pos.as<float>(), seq, w.x.as<float>(), nb, G * G, k.width);
+}
+
+template <typename T> int forward_chunk(arp_enc* c, arp_enc::Ws& w, hipStream_t stream, const float* img_dev, int nb, float* out_dev, const EncSeq& seq) {
+    const arp_enc_cfg& k = c->cfg;
+    const int N = seq.tokens(c->tokens()), D = k.width;
+    TowerCtx t;
+    t.stream = stream; t.prof = &c->prof; t.attn_impl = k.attn_impl; t.gemm_force = c->gemm_force; t.shared_chip = c->shared_chip;
+    if (sizeof(T) == 2 && c->lat_now) {  // (the patch embedding then goes through tower_gemm's skinny route where skinny_supported holds)
+        t.skinny = true; t.part = c->lat_part.as<float>(); t.part_floats = c->lat_part.bytes / 4;
     }
-    const AttnKeyMask km = tx ? key_mask_of(*tx) : AttnKeyMask{};
+    ARP_TRY((front_end<T, false>(c, w, t, img_dev, nb, seq, w.patches.as<T>(), c->w_emb)));
+    const AttnKeyMask km = key_mask_of(seq, c->tokens());
     ARP_TRY((run_blocks<T, ACT_GELU_TANH, 8>(t, c->tower, "m3ae", w.x.as<float>(), w.h.as<T>(), w.qkv.as<T>(), w.ao.as<T>(), w.fc.as<T>(), nb, N, 0,
-                                             1e-6f, nullptr, tx ? &km : nullptr)));
+                                             1e-6f, nullptr, km.dev ? &km : nullptr)));
     ARP_TRY(tower_layernorm<float>(t, "m3ae.ln_final", w.x.as<float>(), (size_t)D, out_dev, D, c->lnf_w, c->lnf_b, nb * N, D, 1e-6f));
     return 0;
 }
@@ -441,9 +376,9 @@ template <typename T> int forward_chunk(arp_enc* c, arp_enc::Ws& w, hipStream_t 
 // ARP_MODE_F16X3: the same network with every GEMM as a K-concatenated (hi, lo) product on the f16 kernels and everything between the GEMMs in f32
 // (LayerNorm outputs, the exact-f32 attention kernel, the tanh-GELU'd hidden activation): 12 x (ln -> split -> in_proj -> attention -> split -> out_proj -> ln ->
 // split -> fc1 -> split -> fc2).  Three MFMAs per product plus the split passes: ~4x the plain f16 step, ~2x faster than the f32-MFMA mode, f32-level error.
-int forward_chunk_x3(arp_enc* c, arp_enc::Ws& w, hipStream_t stream, const float* img_dev, int nb, float* out_dev, const float* goal_dev, const TextPass* tx) {
+int forward_chunk_x3(arp_enc* c, arp_enc::Ws& w, hipStream_t stream, const float* img_dev, int nb, float* out_dev, const EncSeq& seq) {
     const arp_enc_cfg& k = c->cfg;
-    const int G = k.img_res / k.patch, N = tx ? c->tokens() + tx->L : (goal_dev ? c->gc_tokens() : c->tokens()), D = k.width, KP = k.patch * k.patch * 3, H = k.mlp_ratio * D, M = nb * N;
+    const int N = seq.tokens(c->tokens()), D = k.width, H = k.mlp_ratio * D, M = nb * N;
     TowerCtx t;
     t.stream = stream; t.prof = &c->prof; t.attn_impl = k.attn_impl; t.gemm_force = c->gemm_force; t.shared_chip = c->shared_chip;
     f16_t* a3 = w.a3.as<f16_t>();
@@ -451,42 +386,20 @@ int forward_chunk_x3(arp_enc* c, arp_enc::Ws& w, hipStream_t stream, const float
         ProfScope ps(c->prof, stream, site);
         return launch_split3(stream, src, a3, rows, K);
     };
-    {   // frames -> (hi, lo, hi) patch triples in one pass
-        ProfScope ps(c->prof, stream, "m3ae.patchify");
-        const size_t tot = (size_t)nb * G * G * KP;
-        hipLaunchKernelGGL(patchify_split3_kernel, dim3((unsigned)((tot / 4 + 255) / 256)), dim3(256), 0, stream, img_dev, a3, nb, k.img_res, k.patch);
-        ARP_HIP_OK(hipGetLastError());
-        if (goal_dev) {
-            hipLaunchKernelGGL(patchify_split3_kernel, dim3((unsigned)((tot / 4 + 255) / 256)), dim3(256), 0, stream, goal_dev, a3 + 3 * tot, nb, k.img_res, k.patch);
-            ARP_HIP_OK(hipGetLastError());
-        }
-    }
-    ARP_TRY((tower_gemm<f16_t, float, ACT_NONE, false, 8 + SITE_PATCH>(t, "m3ae.image_embedding", a3, c->w_emb, c->b_emb, nullptr, w.pe.p,
-                                                                       (goal_dev ? 2 : 1) * nb * G * G, D, 3 * KP)));
-    if (tx) {
-        ProfScope ps(c->prof, stream, "m3ae.assemble");
-        ARP_TRY(launch_assemble_text(c, stream, w.pe.as<float>(), *tx, w.x.as<float>(), nb, G * G, D));
-    } else if (goal_dev) {
-        ProfScope ps(c->prof, stream, "m3ae.assemble");
-        ARP_TRY(launch_assemble_gc(stream, w.pe.as<float>(), c->cls, c->pos, w.x.as<float>(), nb, G * G, D));
-    } else {
-        ProfScope ps(c->prof, stream, "m3ae.assemble");
-        const size_t tot = (size_t)nb * N * D;
-        hipLaunchKernelGGL(enc_assemble_kernel, dim3((unsigned)((tot / 4 + 255) / 256)), dim3(256), 0, stream, w.pe.as<float>(), c->cls, c->pos, w.x.as<float>(), nb * N, N, D);
-        ARP_HIP_OK(hipGetLastError());
-    }
-    const AttnKeyMask km = tx ? key_mask_of(*tx) : AttnKeyMask{};
+    ARP_TRY((front_end<f16_t, true>(c, w, t, img_dev, nb, seq, a3, c->w_emb)));
+    const AttnKeyMask km = key_mask_of(seq, c->tokens());
+    const AttnKeyMask* mask = km.dev ? &km : nullptr;
     float *x = w.x.as<float>(), *qkv = w.qkv.as<float>(), *ao = w.ao.as<float>();
     for (int i = 0; i < k.layers; ++i) {
         const LayerW& L = c->tower.L[i];
         // LayerNorm and the attention write the (hi, lo, hi) triples of their f32 results themselves (f16x3_t / out3): no f32 copy, no split pass
-        const bool direct = k.attn_impl == 0 && D / k.heads == 64 && N <= 288 && !tx;  // (the VALU attention has no such output, nor has a masked call -- the exact-f32 masked kernel: both keep the split pass)
+        const bool direct = k.attn_impl == 0 && D / k.heads == 64 && N <= 288 && !mask;  // (the VALU attention has no such output, nor has a masked call -- the exact-f32 masked kernel: both keep the split pass)
         ARP_TRY(tower_layernorm<f16x3_t>(t, "m3ae.ln_1", x, D, reinterpret_cast<f16x3_t*>(a3), 3 * D, L.ln1_w, L.ln1_b, M, D, 1e-6f));
         ARP_TRY((tower_gemm<f16_t, float, ACT_NONE, false, 8 + SITE_QKV>(t, "m3ae.qkv", a3, L.w_in, L.b_in, nullptr, qkv, M, 3 * D, 3 * D)));
         {
             ProfScope ps(c->prof, stream, "m3ae.attn");
             // the (hi, lo) binary16 attention (attention.h::attn_x3_kernel) where it exists
-            ARP_TRY(launch_attention<float>(stream, direct ? 3 : k.attn_impl, qkv, ao, nb, N, D, k.heads, 0, 0, 0.f, direct ? a3 : nullptr, 0, tx ? &km : nullptr));
+            ARP_TRY(launch_attention<float>(stream, direct ? 3 : k.attn_impl, qkv, ao, nb, N, D, k.heads, 0, 0, 0.f, direct ? a3 : nullptr, 0, mask));
         }
         if (!direct) ARP_TRY(split("m3ae.split", ao, M, D));
         ARP_TRY((tower_gemm<f16_t, float, ACT_NONE, true, 8 + SITE_OUT>(t, "m3ae.out_proj", a3, L.w_out, L.b_out, x, x, M, D, 3 * D)));
@@ -526,27 +439,16 @@ int gemm_c(arp_enc* c, TowerCtx& t, const char* site, const void* A, const void*
     return launch_gemm256_nt<f16_t, OutT, ACT, RESID, SITE, false, 1, true>(g, t.stream);
 }
 
-int forward_chunk_c(arp_enc* c, arp_enc::Ws& w, hipStream_t stream, const float* img_dev, int nb, float* out_dev) {
+int forward_chunk_c(arp_enc* c, arp_enc::Ws& w, hipStream_t stream, const float* img_dev, int nb, float* out_dev, const EncSeq& seq) {
     const arp_enc_cfg& k = c->cfg;
-    const int G = k.img_res / k.patch, N = c->tokens(), D = k.width, KP = k.patch * k.patch * 3, H = k.mlp_ratio * D, M = nb * N;
+    const int N = c->tokens(), D = k.width, H = k.mlp_ratio * D, M = nb * N;  // (the plain sequence only: forward_part)
     if (D / k.heads != 64 || N > 288 || k.attn_impl != 0) return fail("f16c: needs the MFMA attention kernel (head_dim 64, <= 288 tokens)");
     TowerCtx t;
     t.stream = stream; t.prof = &c->prof; t.attn_impl = 0; t.gemm_force = c->gemm_force; t.shared_chip = c->shared_chip;
     char* a4 = static_cast<char*>(w.a3.p);                 // [M, D] operand rows, 3 D bytes each: [hi | x4 | dx4]
     char* a4h = a4 + (((size_t)M * 3 * D + 255) & ~(size_t)255);  // [M, H] operand rows, 3 H bytes each (fc1's epilogue -> fc2)
-    {   // patch embedding on (hi, lo) binary16 pairs (its input rounding alone is a third of the plain f16 encoder's logit error; the product is 0.6 % of the FLOPs)
-        ProfScope ps(c->prof, stream, "m3ae.patchify");
-        const size_t tot = (size_t)nb * G * G * KP;
-        hipLaunchKernelGGL(patchify_split3_kernel, dim3((unsigned)((tot / 4 + 255) / 256)), dim3(256), 0, stream, img_dev, reinterpret_cast<f16_t*>(a4), nb, k.img_res, k.patch);
-        ARP_HIP_OK(hipGetLastError());
-    }
-    ARP_TRY((tower_gemm<f16_t, float, ACT_NONE, false, 8 + SITE_PATCH>(t, "m3ae.image_embedding", a4, c->w_emb3, c->b_emb, nullptr, w.pe.p, nb * G * G, D, 3 * KP)));
-    {
-        ProfScope ps(c->prof, stream, "m3ae.assemble");
-        const size_t tot = (size_t)nb * N * D;
-        hipLaunchKernelGGL(enc_assemble_kernel, dim3((unsigned)((tot / 4 + 255) / 256)), dim3(256), 0, stream, w.pe.as<float>(), c->cls, c->pos, w.x.as<float>(), nb * N, N, D);
-        ARP_HIP_OK(hipGetLastError());
-    }
+    // patch embedding on (hi, lo) binary16 pairs (its input rounding alone is a third of the plain f16 encoder's logit error; the product is 0.6 % of the FLOPs)
+    ARP_TRY((front_end<f16_t, true>(c, w, t, img_dev, nb, seq, reinterpret_cast<f16_t*>(a4), c->w_emb3)));
     float* x = w.x.as<float>();
     f16_t* qkv = w.qkv.as<f16_t>();
     auto ln = [&](const char* site, const float* w, const float* b, int plan) -> int {
@@ -576,20 +478,14 @@ int forward_chunk_c(arp_enc* c, arp_enc::Ws& w, hipStream_t stream, const float*
 
 namespace arp {
 
-// goal != null: nb (frame, goal) pairs.  A pair is 2 GG + 1 token rows and 2 GG patch rows: every workspace buffer of 2 nb plain frames holds it.
-// tx != null: nb frames with an instruction, 1 + P + L token rows each: the workspace of ceil(nb (1 + P + L) / (1 + P)) plain frames holds them.
-static int forward_part(arp_enc* c, arp_enc::Ws& w, hipStream_t stream, const float* img, int nb, float* out, const float* goal = nullptr, const TextPass* tx = nullptr) {
-    if (goal && c->cfg.mode == ARP_MODE_F16C)
-        return fail("f16c: no goal-conditioned pass (its [hi | x4 | dx4] attention rows exist on the LDS-resident kernel only, <= 288 tokens)");
-    if (tx && c->cfg.mode == ARP_MODE_F16C)
-        return fail("f16c: no image + text pass (its [hi | x4 | dx4] attention rows exist on the LDS-resident kernel only, <= 288 tokens)");
-    if (tx && goal) return fail("forward: an instruction and a goal frame do not combine");
-    ARP_TRY(ensure_ws(c, w, tx ? (int)(((long)nb * (c->tokens() + tx->L) + c->tokens() - 1) / c->tokens()) : (goal ? 2 * nb : nb)));
-    if (c->cfg.mode == ARP_MODE_F16X3) return forward_chunk_x3(c, w, stream, img, nb, out, goal, tx);
-    if (c->cfg.mode == ARP_MODE_F16C) return forward_chunk_c(c, w, stream, img, nb, out);
-    if (c->cfg.mode == ARP_MODE_BF16) return forward_chunk<bf16_t>(c, w, stream, img, nb, out, goal, tx);
-    if (c->cfg.mode == ARP_MODE_F16) return forward_chunk<f16_t>(c, w, stream, img, nb, out, goal, tx);
-    return forward_chunk<float>(c, w, stream, img, nb, out, goal, tx);
+static int forward_part(arp_enc* c, arp_enc::Ws& w, hipStream_t stream, const float* img, int nb, float* out, const EncSeq& seq) {
+    ARP_TRY(f16c_plain_only(c, seq));  // (forward_chunk_c; before any workspace is sized)
+    ARP_TRY(ensure_ws(c, w, seq.ws_frames(nb, c->tokens())));
+    if (c->cfg.mode == ARP_MODE_F16X3) return forward_chunk_x3(c, w, stream, img, nb, out, seq);
+    if (c->cfg.mode == ARP_MODE_F16C) return forward_chunk_c(c, w, stream, img, nb, out, seq);
+    if (c->cfg.mode == ARP_MODE_BF16) return forward_chunk<bf16_t>(c, w, stream, img, nb, out, seq);
+    if (c->cfg.mode == ARP_MODE_F16) return forward_chunk<f16_t>(c, w, stream, img, nb, out, seq);
+    return forward_chunk<float>(c, w, stream, img, nb, out, seq);
 }
 
 // the encoder's GEMM instances (forward_chunk / forward_chunk_x3 / forward_chunk_c above), by name
@@ -621,25 +517,51 @@ int enc_op_gemm_site(const arp_gemm_site& d) {
     return fail("gemm_site: 16-bit modes only");
 }
 
-// Enqueues the encoder of `n` device-resident frames behind everything already on `stream`; `stream` continues behind the last part.  Safe under a
-// stream capture of `stream` (the part streams join the capture through the fork event and leave it through the join events), but every buffer must
-// exist beforehand: the first call of a geometry allocates and must run eagerly (arp_dt.hip runs two eager steps before it captures).
-// goals_dev != null: the goal-conditioned pass of n (frame, goal) pairs (enc_forward_gc_on); max_frames and the part sizes then count pairs
-// tx != null: the image + text pass of n frames (enc_forward_text_on); chunks, parts and the latency rule as for the other two, on n (1 + P + L) rows
-static int enc_forward_any(arp_enc* c, hipStream_t stream, const float* images_dev, const float* goals_dev, int n, float* out_dev, bool latency,
-                           const TextPass* tx = nullptr) {
+// What a text call needs before anything is enqueued: both text weights, a supported mode and length, and the position rows of L tokens on the device
+// (built and uploaded, synchronously, by the first call that needs rows this far; never again afterwards).
+static int text_prepare(arp_enc* c, int L) {
+    if (!c || !c->finalized) return fail("encoder weights not finalized");
+    ARP_TRY(f16c_plain_only(c, EncSeq::text(L)));
+    if (!c->text_emb || !c->text_type)
+        return fail("forward_text: the text weights were not loaded (text_embedding/embedding [vocab, width] and encoder_text_type_embedding [1, 1, width])");
+    if (L < 1 || c->tokens() + L > ATTN_LONG_MAX) return fail("forward_text: 1 + P + L must be at most 1024 token rows and L at least 1");
+    if (c->cfg.width / c->cfg.heads != 64) return fail("forward_text: the key-masked attention kernels need head_dim 64");
+    if (L <= c->text_pos_L) return 0;
+    const int D = c->cfg.width, half = D / 2;
+    std::vector<float> pos((size_t)L * D);
+    for (int i = 0; i < L; ++i)  // get_1d_sincos_pos_embed (m3ae/model.py:95-115) + the text type embedding
+        for (int d = 0; d < half; ++d) {
+            const double omega = 1.0 / std::pow(10000.0, (double)d / (double)half);
+            pos[(size_t)i * D + d] = (float)std::sin(i * omega) + c->text_type_host[d];
+            pos[(size_t)i * D + half + d] = (float)std::cos(i * omega) + c->text_type_host[half + d];
+        }
+    ARP_TRY(c->text_pos.ensure(pos.size() * 4));
+    ARP_HIP_OK(hipMemcpy(c->text_pos.p, pos.data(), pos.size() * 4, hipMemcpyHostToDevice));
+    c->text_pos_L = L;
+    return 0;
+}
+
+// (enc_internal.h)  max_frames and the part sizes count samples of the sequence: frames, pairs, or frames with their instruction.
+int enc_forward_on(arp_enc* c, hipStream_t stream, const float* images_dev, int n, float* out_dev, const EncSeq& seq, bool latency) {
+    if (seq.kind == EncSeq::GOAL) {
+        if (!seq.goals_dev) return fail("forward_gc: null goal frames");
+        if (c) ARP_TRY(f16c_plain_only(c, seq));
+    }
+    if (seq.kind == EncSeq::TEXT) {
+        ARP_TRY(text_prepare(c, seq.L));
+        if (!seq.tok_dev || !seq.words_dev || !seq.words_host) return fail("forward_text: null instruction");
+    }
     if (!c || !c->finalized) return fail("encoder weights not finalized");
     if (n <= 0) return 0;
-    const int mb = c->cfg.max_frames;
-    const int ntok = tx ? c->tokens() + tx->L : (goals_dev ? c->gc_tokens() : c->tokens());
+    const int mb = c->cfg.max_frames, P1 = c->tokens(), ntok = seq.tokens(P1);
     const size_t fi = (size_t)c->cfg.img_res * c->cfg.img_res * 3, fo = (size_t)ntok * c->cfg.width;
-    // the latency path: decided on the call's TOTAL rows (never per part or per chunk: a frame's bits must not depend on how a call is cut), one part
-    // (a goal-conditioned call counts its pairs' rows, 2 P + 1 each: one real pair is 513 rows, two pairs are over SKINNY_MAX_M)
+    // the latency path: decided on the call's TOTAL rows (never per part or per chunk: a sample's bits must not depend on how a call is cut), one part
+    // (one real (frame, goal) pair is 513 rows, two pairs are over SKINNY_MAX_M)
     const long rows = (long)n * ntok;
     if (latency && (c->cfg.mode == ARP_MODE_F16 || c->cfg.mode == ARP_MODE_BF16) && n <= mb && rows <= c->lat_rows) {
         ARP_TRY(c->lat_part.ensure((size_t)4 * rows * c->cfg.width * 4));
         c->lat_now = true;
-        const int rc = forward_part(c, c->ws[0], stream, images_dev, n, out_dev, goals_dev, tx);
+        const int rc = forward_part(c, c->ws[0], stream, images_dev, n, out_dev, seq);
         c->lat_now = false;
         return rc;
     }
@@ -647,12 +569,11 @@ static int enc_forward_any(arp_enc* c, hipStream_t stream, const float* images_d
         const int nb = std::min(mb, n - off);
         const float* img = images_dev + off * fi;
         float* out = out_dev + off * fo;
-        const float* goal = goals_dev ? goals_dev + off * fi : nullptr;
-        const TextPass txo = tx ? tx->at(off) : TextPass{};
+        const EncSeq so = seq.at(off, fi, P1);
         int parts = std::min(c->n_parts, (int)arp_enc::MAX_PARTS);
         while (parts > 1 && nb / parts < c->min_part_frames) --parts;
         if (parts < 2) {
-            ARP_TRY(forward_part(c, c->ws[0], stream, img, nb, out, goal, tx ? &txo : nullptr));
+            ARP_TRY(forward_part(c, c->ws[0], stream, img, nb, out, so));
             continue;
         }
         // contiguous parts: part 0 on the caller's stream, part k on its own
@@ -672,9 +593,7 @@ static int enc_forward_any(arp_enc* c, hipStream_t stream, const float* images_d
         for (int i = 0; i < parts && !rc; ++i) {
             hipStream_t st = i == 0 ? stream : c->ws[i].stream;
             if (i > 0 && hipStreamWaitEvent(st, c->ev_fork, 0) != hipSuccess) rc = fail("hipStreamWaitEvent(fork) failed");
-            const TextPass txp = tx ? txo.at(cut[i]) : TextPass{};
-            if (!rc) rc = forward_part(c, c->ws[i], st, img + (size_t)cut[i] * fi, cut[i + 1] - cut[i], out + (size_t)cut[i] * fo, goal ? goal + (size_t)cut[i] * fi : nullptr,
-                                       tx ? &txp : nullptr);
+            if (!rc) rc = forward_part(c, c->ws[i], st, img + (size_t)cut[i] * fi, cut[i + 1] - cut[i], out + (size_t)cut[i] * fo, so.at(cut[i], fi, P1));
         }
         c->shared_chip = false;
         // join even after a failure: a part stream that entered a capture must leave it before the capture ends
@@ -686,54 +605,9 @@ static int enc_forward_any(arp_enc* c, hipStream_t stream, const float* images_d
     }
     return 0;
 }
-int enc_forward_on(arp_enc* c, hipStream_t stream, const float* images_dev, int n, float* out_dev, bool latency) {
-    return enc_forward_any(c, stream, images_dev, nullptr, n, out_dev, latency);
-}
-// n (frame, goal) pairs, both device-resident [n, res, res, 3] f32 -> out_dev [n, 2 GG + 1, width] f32.  Chunks of max_frames PAIRS, part streams as above;
-// latency as in enc_forward_on, on the pairs' rows.  Stream and capture rules as enc_forward_on.
-int enc_forward_gc_on(arp_enc* c, hipStream_t stream, const float* images_dev, const float* goals_dev, int n, float* out_dev, bool latency) {
-    if (!goals_dev) return fail("forward_gc: null goal frames");
-    if (c && c->cfg.mode == ARP_MODE_F16C) return fail("f16c: no goal-conditioned pass (its [hi | x4 | dx4] attention rows exist on the LDS-resident kernel only, <= 288 tokens)");
-    return enc_forward_any(c, stream, images_dev, goals_dev, n, out_dev, latency);
-}
-// What a text call needs before anything is enqueued: both text weights, a supported mode and length, and the position rows of L tokens on the device
-// (built and uploaded, synchronously, by the first call that needs rows this far; never again afterwards).
-static int text_prepare(arp_enc* c, int L) {
-    if (!c || !c->finalized) return fail("encoder weights not finalized");
-    if (c->cfg.mode == ARP_MODE_F16C) return fail("f16c: no image + text pass (its [hi | x4 | dx4] attention rows exist on the LDS-resident kernel only, <= 288 tokens)");
-    if (!c->text_emb || !c->text_type)
-        return fail("forward_text: the text weights were not loaded (text_embedding/embedding [vocab, width] and encoder_text_type_embedding [1, 1, width])");
-    if (L < 1 || c->tokens() + L > ATTN_LONG_MAX) return fail("forward_text: 1 + P + L must be at most 1024 token rows and L at least 1");
-    if (c->cfg.width / c->cfg.heads != 64) return fail("forward_text: the key-masked attention kernels need head_dim 64");
-    if (L <= c->text_pos_L) return 0;
-    const int D = c->cfg.width, half = D / 2;
-    std::vector<float> pos((size_t)L * D);
-    for (int i = 0; i < L; ++i)  // get_1d_sincos_pos_embed (m3ae/model.py:95-115) + the text type embedding
-        for (int d = 0; d < half; ++d) {
-            const double omega = 1.0 / std::pow(10000.0, (double)d / (double)half);
-            pos[(size_t)i * D + d] = (float)std::sin(i * omega) + c->text_type_host[d];
-            pos[(size_t)i * D + half + d] = (float)std::cos(i * omega) + c->text_type_host[half + d];
-        }
-    ARP_TRY(c->text_pos.ensure(pos.size() * 4));
-    ARP_HIP_OK(hipMemcpy(c->text_pos.p, pos.data(), pos.size() * 4, hipMemcpyHostToDevice));
-    c->text_pos_L = L;
-    return 0;
-}
-// n device-resident frames with an instruction -> out_dev [n, 1 + P + L, width] f32.  tok_dev: int32 ids ([L], or [n, L] with per_row), already checked against
-// the vocabulary; words_dev / words_host: the visible-bit words over the 1 + P + L keys ((1 + P + L + 31) / 32 per instruction), in HBM and on the host.
-// Stream, capture, chunk, part and latency rules as enc_forward_on (the first call of an L uploads its position rows and must run eagerly).
-int enc_text_prepare(arp_enc* c, int L) { return text_prepare(c, L); }
-int enc_forward_text_on(arp_enc* c, hipStream_t stream, const float* images_dev, int n, const int32_t* tok_dev, const uint32_t* words_dev, const uint32_t* words_host,
-                        int L, int per_row, float* out_dev, bool latency) {
-    ARP_TRY(text_prepare(c, L));
-    if (!tok_dev || !words_dev || !words_host) return fail("forward_text: null instruction");
-    TextPass tx;
-    tx.tok = tok_dev; tx.words = words_dev; tx.words_host = words_host; tx.L = L; tx.per_row = per_row ? 1 : 0; tx.per = (c->tokens() + L + 31) / 32;
-    return enc_forward_any(c, stream, images_dev, nullptr, n, out_dev, latency, &tx);
-}
 // Host side of an instruction: ids checked against the vocabulary, the visible-bit words built from the padding mask (mask > 0 = padded, the reference's
 // convention; class and patch keys always visible).  S instructions of L tokens -> words [S, (1 + P + L + 31) / 32].
-int enc_text_words(arp_enc* c, const int32_t* tokens, const float* mask, int S, int L, uint32_t* words) {
+static int text_words(arp_enc* c, const int32_t* tokens, const float* mask, int S, int L, uint32_t* words) {
     if (!c || !tokens || !mask || !words) return fail("forward_text: null instruction");
     const int P1 = c->tokens(), per = (P1 + L + 31) / 32;
     for (int s = 0; s < S; ++s) {
@@ -750,14 +624,23 @@ int enc_text_words(arp_enc* c, const int32_t* tokens, const float* mask, int S, 
     }
     return 0;
 }
-int enc_text_tokens(arp_enc* c, int L, int* tokens) {
-    if (!c) return fail("null encoder");
-    *tokens = c->tokens() + L;
+int EncText::set(arp_enc* e, const int32_t* tokens, const float* mask, int L_) {
+    ARP_TRY(text_prepare(e, L_));
+    const int per = EncSeq::text(L_).words(e->tokens());
+    std::vector<uint32_t> w(per);
+    ARP_TRY(text_words(e, tokens, mask, 1, L_, w.data()));
+    std::vector<int32_t> blob(L_ + per);
+    memcpy(blob.data(), tokens, (size_t)L_ * 4);
+    memcpy(blob.data() + L_, w.data(), (size_t)per * 4);
+    ARP_TRY(dev.ensure(blob.size() * 4));
+    ARP_HIP_OK(hipMemcpy(dev.p, blob.data(), blob.size() * 4, hipMemcpyHostToDevice));
+    words = std::move(w);
+    L = L_;
     return 0;
 }
-int enc_gc_tokens(arp_enc* c, int* tokens) {
+int enc_seq_tokens(arp_enc* c, const EncSeq& seq, int* tokens) {
     if (!c) return fail("null encoder");
-    *tokens = c->gc_tokens();
+    *tokens = seq.tokens(c->tokens());
     return 0;
 }
 int enc_geometry(arp_enc* c, int* tokens, int* width, int* img_res, int* device) {
@@ -928,25 +811,37 @@ int arp_enc_finalize_weights(arp_enc* c) {
     return 0;
 }
 
+// The host entries' loop: frames (and goal frames) on the host -> encodings on the host, a chunk of max_frames samples at a time on the handle's own stream:
+// stage, enqueue, copy out, synchronise.  goals != null is the goal-conditioned call: `seq` is ignored and built here, because its device pointer is this
+// function's staging area (a chunk's goal frames behind its frames), the same for every chunk.  Otherwise seq is the call's instruction, if any, its device
+// pointers into txt_dev, whose txt_bytes (ids, then words) leave the pinned block in ONE async copy in front of the first chunk; seq.at walks it by chunk.
+static int forward_host(arp_enc* c, const float* images, const float* goals, int n, float* out, EncSeq seq = {}, size_t txt_bytes = 0) {
+    ARP_HIP_OK(hipSetDevice(c->cfg.device));
+    const int mb = c->cfg.max_frames, P1 = c->tokens(), nb0 = std::min(n, mb);
+    const size_t fi = (size_t)c->cfg.img_res * c->cfg.img_res * 3;
+    if (!c->stream) ARP_TRY(c->stream.create());
+    if (txt_bytes) ARP_HIP_OK(hipMemcpyAsync(c->txt_dev.p, c->txt_pin.p, txt_bytes, hipMemcpyHostToDevice, c->stream));
+    ARP_TRY(c->img_in.ensure((goals ? 2 : 1) * nb0 * fi * 4));
+    if (goals) seq = EncSeq::goal(c->img_in.as<float>() + nb0 * fi);
+    const size_t fo = (size_t)seq.tokens(P1) * c->cfg.width;
+    ARP_TRY(c->out.ensure(nb0 * fo * 4));
+    for (int off = 0; off < n; off += mb) {
+        const int nb = std::min(mb, n - off);
+        ARP_HIP_OK(hipMemcpyAsync(c->img_in.p, images + off * fi, nb * fi * 4, hipMemcpyHostToDevice, c->stream));
+        if (goals) ARP_HIP_OK(hipMemcpyAsync(const_cast<float*>(seq.goals_dev), goals + off * fi, nb * fi * 4, hipMemcpyHostToDevice, c->stream));
+        ARP_TRY(enc_forward_on(c, c->stream, c->img_in.as<float>(), nb, c->out.as<float>(), goals ? seq : seq.at(off, fi, P1), c->lat_host && n <= mb));
+        ARP_HIP_OK(hipMemcpyAsync(out + off * fo, c->out.p, nb * fo * 4, hipMemcpyDeviceToHost, c->stream));
+        ARP_HIP_OK(hipStreamSynchronize(c->stream));
+    }
+    return 0;
+}
+
 int arp_enc_forward(arp_enc* c, const float* images, int n, float* out) {
     if (!c || !c->finalized) return fail("encoder weights not finalized");
     if (n < 0) return fail("negative frame count");
     if (n == 0) return 0;
     if (!images || !out) return fail("null buffer");
-    ARP_HIP_OK(hipSetDevice(c->cfg.device));
-    const size_t fi = (size_t)c->cfg.img_res * c->cfg.img_res * 3, fo = (size_t)c->tokens() * c->cfg.width;
-    const int mb = c->cfg.max_frames;
-    if (!c->stream) ARP_TRY(c->stream.create());
-    ARP_TRY(c->img_in.ensure((size_t)std::min(n, mb) * fi * 4));
-    ARP_TRY(c->out.ensure((size_t)std::min(n, mb) * fo * 4));
-    for (int off = 0; off < n; off += mb) {
-        const int nb = std::min(mb, n - off);
-        ARP_HIP_OK(hipMemcpyAsync(c->img_in.p, images + off * fi, nb * fi * 4, hipMemcpyHostToDevice, c->stream));
-        ARP_TRY(enc_forward_on(c, c->stream, c->img_in.as<float>(), nb, c->out.as<float>(), c->lat_host && n <= mb));
-        ARP_HIP_OK(hipMemcpyAsync(out + off * fo, c->out.p, nb * fo * 4, hipMemcpyDeviceToHost, c->stream));
-        ARP_HIP_OK(hipStreamSynchronize(c->stream));
-    }
-    return 0;
+    return forward_host(c, images, nullptr, n, out);
 }
 
 int arp_enc_forward_gc(arp_enc* c, const float* images, const float* goals, int n, float* out) {
@@ -954,25 +849,10 @@ int arp_enc_forward_gc(arp_enc* c, const float* images, const float* goals, int 
     if (n < 0) return fail("negative pair count");
     if (n == 0) return 0;
     if (!images || !goals || !out) return fail("null buffer");
-    if (c->cfg.mode == ARP_MODE_F16C) return fail("f16c: no goal-conditioned pass (its [hi | x4 | dx4] attention rows exist on the LDS-resident kernel only, <= 288 tokens)");
-    ARP_HIP_OK(hipSetDevice(c->cfg.device));
-    const size_t fi = (size_t)c->cfg.img_res * c->cfg.img_res * 3, fo = (size_t)c->gc_tokens() * c->cfg.width;
-    const int mb = c->cfg.max_frames;
-    if (!c->stream) ARP_TRY(c->stream.create());
-    ARP_TRY(c->img_in.ensure((size_t)2 * std::min(n, mb) * fi * 4));  // the chunk's frames, then its goals
-    ARP_TRY(c->out.ensure((size_t)std::min(n, mb) * fo * 4));
-    for (int off = 0; off < n; off += mb) {
-        const int nb = std::min(mb, n - off);
-        float* gdev = c->img_in.as<float>() + (size_t)nb * fi;
-        ARP_HIP_OK(hipMemcpyAsync(c->img_in.p, images + off * fi, nb * fi * 4, hipMemcpyHostToDevice, c->stream));
-        ARP_HIP_OK(hipMemcpyAsync(gdev, goals + off * fi, nb * fi * 4, hipMemcpyHostToDevice, c->stream));
-        ARP_TRY(enc_forward_gc_on(c, c->stream, c->img_in.as<float>(), gdev, nb, c->out.as<float>(), c->lat_host && n <= mb));
-        ARP_HIP_OK(hipMemcpyAsync(out + off * fo, c->out.p, nb * fo * 4, hipMemcpyDeviceToHost, c->stream));
-        ARP_HIP_OK(hipStreamSynchronize(c->stream));
-    }
-    return 0;
+    ARP_TRY(f16c_plain_only(c, EncSeq::goal()));
+    return forward_host(c, images, goals, n, out);
 }
-int arp_enc_gc_tokens(arp_enc* c) { return c ? c->gc_tokens() : fail("null handle"); }
+int arp_enc_gc_tokens(arp_enc* c) { return c ? EncSeq::goal().tokens(c->tokens()) : fail("null handle"); }
 
 int arp_enc_forward_text(arp_enc* c, const float* images, int n, const int32_t* tokens, const float* mask, int L, int per_row, float* out) {
     if (!c || !c->finalized) return fail("encoder weights not finalized");
@@ -981,32 +861,16 @@ int arp_enc_forward_text(arp_enc* c, const float* images, int n, const int32_t* 
     if (!images || !out || !tokens || !mask) return fail("null buffer");
     ARP_HIP_OK(hipSetDevice(c->cfg.device));
     ARP_TRY(text_prepare(c, L));
-    const int S = per_row ? n : 1, per = (c->tokens() + L + 31) / 32;
-    const size_t fi = (size_t)c->cfg.img_res * c->cfg.img_res * 3, fo = (size_t)(c->tokens() + L) * c->cfg.width;
-    const int mb = c->cfg.max_frames;
-    if (!c->stream) ARP_TRY(c->stream.create());
-    // ids, then words: one pinned block, one async copy in front of the first chunk (the previous call synchronised before it returned: the block is free)
-    const size_t tb = (size_t)S * L * 4, wb = (size_t)S * per * 4;
+    // ids, then words: one pinned block (the previous call synchronised before it returned: the block is free)
+    const int S = per_row ? n : 1;
+    const size_t tb = (size_t)S * L * 4, wb = (size_t)S * EncSeq::text(L).words(c->tokens()) * 4;
     ARP_TRY(c->txt_pin.ensure(tb + wb));
     ARP_TRY(c->txt_dev.ensure(tb + wb));
-    int32_t* tok_h = c->txt_pin.as<int32_t>();
     uint32_t* words_h = reinterpret_cast<uint32_t*>(c->txt_pin.as<char>() + tb);
-    ARP_TRY(enc_text_words(c, tokens, mask, S, L, words_h));
-    memcpy(tok_h, tokens, tb);
-    ARP_HIP_OK(hipMemcpyAsync(c->txt_dev.p, c->txt_pin.p, tb + wb, hipMemcpyHostToDevice, c->stream));
-    const int32_t* tok_d = c->txt_dev.as<int32_t>();
-    const uint32_t* words_d = reinterpret_cast<const uint32_t*>(c->txt_dev.as<char>() + tb);
-    ARP_TRY(c->img_in.ensure((size_t)std::min(n, mb) * fi * 4));
-    ARP_TRY(c->out.ensure((size_t)std::min(n, mb) * fo * 4));
-    for (int off = 0; off < n; off += mb) {
-        const int nb = std::min(mb, n - off);
-        const size_t to = per_row ? (size_t)off * L : 0, wo = per_row ? (size_t)off * per : 0;
-        ARP_HIP_OK(hipMemcpyAsync(c->img_in.p, images + off * fi, nb * fi * 4, hipMemcpyHostToDevice, c->stream));
-        ARP_TRY(enc_forward_text_on(c, c->stream, c->img_in.as<float>(), nb, tok_d + to, words_d + wo, words_h + wo, L, per_row, c->out.as<float>(), c->lat_host && n <= mb));
-        ARP_HIP_OK(hipMemcpyAsync(out + off * fo, c->out.p, nb * fo * 4, hipMemcpyDeviceToHost, c->stream));
-        ARP_HIP_OK(hipStreamSynchronize(c->stream));
-    }
-    return 0;
+    ARP_TRY(text_words(c, tokens, mask, S, L, words_h));
+    memcpy(c->txt_pin.p, tokens, tb);
+    return forward_host(c, images, nullptr, n, out, EncSeq::text(L, per_row, c->txt_dev.as<int32_t>(), reinterpret_cast<const uint32_t*>(c->txt_dev.as<char>() + tb), words_h),
+                        tb + wb);
 }
 int arp_enc_text_tokens(arp_enc* c, int L) { return c && L >= 0 ? c->tokens() + L : fail("null handle or negative length"); }
 
@@ -1095,6 +959,33 @@ int arp_op_split3(const float* x, void* out, size_t out_bytes, int rows, int K) 
     const int rc = launch_split3(nullptr, dx.as<float>(), dout.as<f16_t>(), (size_t)rows, K);
     ARP_HIP_OK(hipDeviceSynchronize());
     ARP_HIP_OK(hipMemcpy(out, dout.p, out_bytes, hipMemcpyDeviceToHost));
+    return rc;
+}
+
+// enc_assemble_kernel through the encoder's own launcher, on host arrays: pe [(goal ? 2 : 1) nb GG, D], cls [D], pos [GG, D]; with L > 0 text_emb [vocab, D],
+// tpos [L, D] and tok int32 [L] (per_row: [nb, L]); x [nb, 1 + GG (+ GG | + L), D] goes up before the launch and comes back after it
+int arp_op_m3ae_assemble(const float* pe, const float* cls, const float* pos, const float* text_emb, const float* tpos, const int32_t* tok, int nb, int GG, int goal,
+                         int L, int per_row, int D, int vocab, float* x) {
+    if (!pe || !cls || !pos || !x || nb <= 0 || GG <= 0 || D <= 0 || L < 0 || (L > 0 && (!text_emb || !tpos || !tok || vocab <= 0))) return fail("m3ae_assemble: bad argument");
+    if (D % 4) return fail("m3ae_assemble: the width must be a multiple of 4 (float4 accesses)");
+    if (goal && L > 0) return fail("m3ae_assemble: an instruction and a goal frame do not combine");
+    const size_t n_tok = L > 0 ? (size_t)(per_row ? nb : 1) * L : 0;
+    for (size_t i = 0; i < n_tok; ++i)
+        if (tok[i] < 0 || tok[i] >= vocab) return fail("m3ae_assemble: token id " + std::to_string(tok[i]) + " is outside the vocabulary [0, " + std::to_string(vocab) + ")");
+    DevBuf dpe, dcls, dpos, demb, dtpos, dtok, dx;
+    auto up = [](DevBuf& d, const void* src, size_t bytes) -> int {
+        ARP_TRY(d.ensure(bytes));
+        ARP_HIP_OK(hipMemcpy(d.p, src, bytes, hipMemcpyHostToDevice));
+        return 0;
+    };
+    ARP_TRY(up(dpe, pe, (size_t)(goal ? 2 : 1) * nb * GG * D * 4)); ARP_TRY(up(dcls, cls, (size_t)D * 4)); ARP_TRY(up(dpos, pos, (size_t)GG * D * 4));
+    if (L > 0) { ARP_TRY(up(demb, text_emb, (size_t)vocab * D * 4)); ARP_TRY(up(dtpos, tpos, (size_t)L * D * 4)); ARP_TRY(up(dtok, tok, n_tok * 4)); }
+    const EncSeq seq = goal ? EncSeq::goal() : L > 0 ? EncSeq::text(L, per_row, dtok.as<int32_t>()) : EncSeq{};
+    const size_t xb = (size_t)nb * seq.tokens(1 + GG) * D * 4;
+    ARP_TRY(up(dx, x, xb));
+    const int rc = launch_assemble(nullptr, dpe.as<float>(), dcls.as<float>(), dpos.as<float>(), demb.as<float>(), dtpos.as<float>(), seq, dx.as<float>(), nb, GG, D);
+    ARP_HIP_OK(hipDeviceSynchronize());
+    ARP_HIP_OK(hipMemcpy(x, dx.p, xb, hipMemcpyDeviceToHost));
     return rc;
 }
 

@@ -174,12 +174,9 @@ struct arp_rollout {
     DevBuf goals_u8, goal32, goal_feat, frame_feat;
     std::vector<char> has_goal;     // [E]
     bool goal_reward() const { return gc && clip; }
-    // A session made by arp_rollout_create_text (model BC, InstructRL): the instruction its steps encode the E new frames with -- L token ids followed by the
-    // visible-bit words of the 1 + P + L keys in HBM, the words on the host (enc_internal.h::enc_forward_text_on).  Constant over the episode, so a ring
-    // entry stays valid for as long as its frame is in the window.
-    int text_L = 0;
-    DevBuf text_dev;
-    std::vector<uint32_t> text_words;
+    // A session made by arp_rollout_create_text (model BC, InstructRL): the instruction its steps encode the E new frames with.  Constant over the episode, so a
+    // ring entry stays valid for as long as its frame is in the window.
+    EncText text;
     const float* logits = nullptr;  // the policy's logits buffer as of the last step
     float* slot_enc = nullptr;
     int32_t* slot_action = nullptr;
@@ -222,8 +219,8 @@ static int rollout_create(arp_dt* policy, arp_enc* encoder, arp_clip* reward, ar
     if (s->pi.bc && reward) return fail("rollout: model BC reads no return-to-go: a reward handle is refused");
     int tokens = 0, width = 0, res = 0, dev = 0;
     ARP_TRY(enc_geometry(s->pi.enc, &tokens, &width, &res, &dev));
-    if (s->pi.gcbc) ARP_TRY(enc_gc_tokens(s->pi.enc, &tokens));  // a (frame, goal) pair per ring entry
-    if (text_L > 0) ARP_TRY(enc_text_tokens(s->pi.enc, text_L, &tokens));  // a frame and the instruction per ring entry
+    if (s->pi.gcbc) ARP_TRY(enc_seq_tokens(s->pi.enc, EncSeq::goal(), &tokens));  // a (frame, goal) pair per ring entry
+    if (text_L > 0) ARP_TRY(enc_seq_tokens(s->pi.enc, EncSeq::text(text_L), &tokens));  // a frame and the instruction per ring entry
     if (H != res || W != res) return fail("rollout: frames are " + std::to_string(H) + " x " + std::to_string(W) + ", the attached encoder reads " + std::to_string(res) + " x " + std::to_string(res));
     if (tokens != s->pi.enc_tokens || width != s->pi.enc_dim) return fail("rollout: encoder geometry does not match the policy's enc_tokens / enc_dim");
     if (dev != s->pi.device) return fail("rollout: the encoder lives on another device");
@@ -297,23 +294,12 @@ int arp_rollout_create_text(arp_dt* policy, arp_enc* encoder_or_null, int n_envs
     arp_enc* enc = encoder_or_null ? encoder_or_null : pi.enc;
     if (!enc) return fail("rollout: create_text: no encoder (pass one, or attach one with arp_dt_attach_text_encoder)");
     ARP_HIP_OK(hipSetDevice(pi.device));
-    ARP_TRY(enc_text_prepare(enc, L));  // the text weights, the mode, the position rows: before the first step
-    int ntok = 0;
-    ARP_TRY(enc_text_tokens(enc, L, &ntok));
-    const int per = (ntok + 31) / 32;
-    std::vector<uint32_t> words(per);
-    ARP_TRY(enc_text_words(enc, tokens, mask, 1, L, words.data()));
+    EncText text;
+    ARP_TRY(text.set(enc, tokens, mask, L));  // the text weights, the mode, the ids, the position rows: before the session exists
     arp_rollout* s = nullptr;
     ARP_TRY(rollout_create(policy, enc, nullptr, nullptr, n_envs, H, W, 1.f, &s, false, L));
-    std::unique_ptr<arp_rollout> own(s);
-    std::vector<int32_t> blob(L + per);
-    memcpy(blob.data(), tokens, (size_t)L * 4);
-    memcpy(blob.data() + L, words.data(), (size_t)per * 4);
-    ARP_TRY(s->text_dev.ensure(blob.size() * 4));
-    ARP_HIP_OK(hipMemcpy(s->text_dev.p, blob.data(), blob.size() * 4, hipMemcpyHostToDevice));
-    s->text_words = std::move(words);
-    s->text_L = L;
-    *out = own.release();
+    s->text = std::move(text);
+    *out = s;
     return 0;
 }
 
@@ -469,11 +455,8 @@ static int rollout_step(arp_rollout* s, const uint8_t* frames_host, const float*
     ARP_TRY(launch_ingest(s, s->frames_u8.as<uint8_t>(), s->enc_in.as<float>(), (size_t)E));
     // 3. the encoder on the E new frames (model GCBC: on the E new (frame, goal) pairs), straight into ring slot `head`
     float* slot = s->ring.as<float>() + (size_t)s->head * E * s->F;
-    if (s->pi.gcbc) ARP_TRY(enc_forward_gc_on(s->enc, S, s->enc_in.as<float>(), s->goal32.as<float>(), E, slot, true));
-    else if (s->text_L > 0)  // (model BC with its instruction: the image + text pass)
-        ARP_TRY(enc_forward_text_on(s->enc, S, s->enc_in.as<float>(), E, s->text_dev.as<int32_t>(), reinterpret_cast<const uint32_t*>(s->text_dev.as<int32_t>() + s->text_L),
-                                    s->text_words.data(), s->text_L, 0, slot, true));
-    else ARP_TRY(enc_forward_on(s->enc, S, s->enc_in.as<float>(), E, slot, true));
+    const EncSeq seq = s->pi.gcbc ? EncSeq::goal(s->goal32.as<float>()) : s->text.L > 0 ? s->text.seq() : EncSeq{};  // (model BC with its instruction: the image + text pass)
+    ARP_TRY(enc_forward_on(s->enc, S, s->enc_in.as<float>(), E, slot, seq, true));
     // 4. window
     {
         WindowArgs a;

@@ -749,6 +749,11 @@ int arp_op_convert_f16c(int with_dx, const float* x, void* xb, size_t xb_bytes, 
 int arp_op_extract_hi(const void* in, size_t in_bytes, int ld, void* out, size_t out_bytes, int rows, int D);
 /* The f16x3 encoder's split pass: x f32 [rows, K] -> rows of 3 K binary16 values [hi | lo | hi], hi = rn16(x), lo = rn16(x - hi)  (K % 8 == 0) */
 int arp_op_split3(const float* x, void* out, size_t out_bytes, int rows, int K);
+/* The M3AE encoder's sequence assembly: x [nb, ntok, D], row 0 = cls, rows 1 .. GG = pe[b GG + p] + pos[p]; goal = 1: the next GG rows = pe[(nb + b) GG + p] +
+ * pos[p] (pe [2 nb GG, D]); L > 0: the next L rows = text_emb[tok[j]] + tpos[j], tok int32 [L] or [nb, L] (per_row).  x goes up before the launch and comes
+ * back after it.  Refuses D % 4 != 0, goal together with L > 0, and an id outside [0, vocab). */
+int arp_op_m3ae_assemble(const float* pe, const float* cls, const float* pos, const float* text_emb, const float* tpos, const int32_t* tok, int nb, int GG, int goal,
+                         int L, int per_row, int D, int vocab, float* x);
 /* The rollout session's decide kernel: logits [E, T, n_actions], lens[e] = window length L in [1, T] -> actions_out[e] = argmax of row L - 1 (the lowest
  * index wins a tie, the first NaN wins: numpy.argmax). */
 int arp_op_rollout_decide(const float* logits, const int32_t* lens, int E, int T, int n_actions, int32_t* actions_out);

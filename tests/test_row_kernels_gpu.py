@@ -14,7 +14,8 @@ third segment bitwise the first, |hi + lo - v| <= delta + 2^-11 |lo| + 2^-25.  [
 kernel's own hi, fp4((v - delta - hi) 2^13) <= dx4 <= fp4((v + delta - hi) 2^13); in the [hi | x4] form the dx4 bytes keep the fill.
 
 Sums (row_stats, the assemble kernel's strip 0, reward, l2_normalize): (L + 1) u sum |terms|, L the additions on the longest path, stated at each test.
-Kernels that only move or round data (text_embed, rows_gather, extract_hi, the operand copies, convert_f16c*, split3) are held to bit equality.
+Kernels that only move or round data or add once (text_embed, m3ae_assemble, rows_gather, extract_hi, the operand copies, convert_f16c*, split3) are held to
+bit equality.
 
 Largest |out - v| / delta measured on an MI355X over every LayerNorm case of this module (the bar is 1.0; the tests print theirs, `pytest -s`): f32 form
 0.175; ln_pre rows of the two assembly kernels 0.173; hi + lo of the [hi | lo | hi] form 0.275 of its own bound.  A numpy f32 restatement of the kernel with
@@ -513,6 +514,55 @@ def test_split3(gpu_lib, K):
             assert np.array_equal(seg, want.view(np.uint16)), f"split3 K={K} rows={rows}: {name}"
         assert (ob[rows * K * 6:] == FILL).all()
     assert gpu_lib.lib.arp_op_split3(_fp(x), _vp(ob), ob.size, 1, 12) != 0
+
+
+# ---- the M3AE encoder's sequence assembly ------------------------------------------------------------------------------------------------------------
+
+M3AE_VOCAB = 9
+M3AE_ASM = [(1, 1, 4, "plain"), (1, 1, 4, "goal"), (1, 1, 4, "text1"),      # the smallest of each kind
+            (2, 3, 128, "plain"),                                            # 2 * 4 * 128 = 1024 values: exactly one full 256-thread block, no guard
+            (3, 5, 36, "plain"), (3, 5, 36, "goal"), (3, 5, 36, "text7"), (3, 5, 36, "text7-rows")]   # a ragged last block: the guard
+
+
+def _m3ae_asm_inputs(nb, GG, D, kind):
+    rng = np.random.default_rng(nb * 1000 + GG * 100 + D)
+    goal, L, per_row = int(kind == "goal"), {"text1": 1, "text7": 7, "text7-rows": 7}.get(kind, 0), int(kind == "text7-rows")
+    pe = rng.standard_normal(((1 + goal) * nb * GG, D)).astype(np.float32)
+    cls, pos = rng.standard_normal(D).astype(np.float32), rng.standard_normal((GG, D)).astype(np.float32)
+    emb, tpos = rng.standard_normal((M3AE_VOCAB, D)).astype(np.float32), rng.standard_normal((max(L, 1), D)).astype(np.float32)
+    # ids 0 and vocab - 1, a repeated id; with per_row every row has its own ids
+    tok = np.array([[3, 0, 8, 3, 5, 1, 7], [8, 8, 2, 0, 6, 4, 1], [5, 7, 0, 0, 3, 8, 2]], np.int32)[:nb if per_row else 1, :max(L, 1)].copy()
+    return goal, L, per_row, pe, cls, pos, emb, tpos, tok
+
+
+@pytest.mark.parametrize("nb,GG,D,kind", M3AE_ASM, ids=[f"{n}x{g}x{d}-{k}" for n, g, d, k in M3AE_ASM])
+def test_m3ae_assemble(gpu_lib, nb, GG, D, kind):
+    """enc_assemble_kernel: row 0 = cls, the frame's patches + pos, then the goal's patches + pos or text_emb[tok] + tpos.  Every value is a copy or ONE f32
+    addition of the same two operands: bit for bit.  x goes up as NaN, so an unwritten row fails."""
+    goal, L, per_row, pe, cls, pos, emb, tpos, tok = _m3ae_asm_inputs(nb, GG, D, kind)
+    ntok = 1 + (1 + goal) * GG + L
+    want = np.empty((nb, ntok, D), np.float32)
+    want[:, 0] = cls
+    want[:, 1:1 + GG] = pe[:nb * GG].reshape(nb, GG, D) + pos
+    if goal:
+        want[:, 1 + GG:] = pe[nb * GG:].reshape(nb, GG, D) + pos
+    if L:
+        want[:, 1 + GG:] = emb[np.broadcast_to(tok, (nb, L))] + tpos[:L]
+    x = np.full((nb, ntok, D), np.nan, np.float32)
+    gpu_lib.check(gpu_lib.lib.arp_op_m3ae_assemble(_fp(pe), _fp(cls), _fp(pos), _fp(emb), _fp(tpos), _ip(tok), nb, GG, goal, L, per_row, D, M3AE_VOCAB, _fp(x)))
+    assert np.array_equal(x, want), (kind, np.argwhere(~(x == want))[:4])
+
+
+def test_m3ae_assemble_refusals(gpu_lib):
+    lib = gpu_lib.lib
+    for D, goal, ids, word in ((6, 0, [1, 2], "multiple of 4"), (4, 1, [1, 2], "do not combine"), (4, 0, [1, M3AE_VOCAB], "outside the vocabulary"),
+                               (4, 0, [-1, 2], "outside the vocabulary")):
+        pe, cls, pos = np.ones((2 * 3, D), np.float32), np.ones(D, np.float32), np.ones((3, D), np.float32)
+        emb, tpos, tok = np.ones((M3AE_VOCAB, D), np.float32), np.ones((2, D), np.float32), np.array(ids, np.int32)
+        x = np.full((1, 1 + 2 * 3 + 2, D), 7.0, np.float32)
+        rc = lib.arp_op_m3ae_assemble(_fp(pe), _fp(cls), _fp(pos), _fp(emb), _fp(tpos), _ip(tok), 1, 3, goal, 2, 0, D, M3AE_VOCAB, _fp(x))
+        assert rc != 0 and word in gpu_lib.last_error(), (D, goal, ids, gpu_lib.last_error())
+        assert (x == 7.0).all()
 
 
 # ---- the split-K reduce + LayerNorm row kernel, element by element ---------------------------------------------------------------------------------
