@@ -276,6 +276,10 @@ SIGNATURES = {
     "arp_op_extract_hi": (_i, [_vp, C.c_size_t, _i, _vp, C.c_size_t, _i, _i]),
     "arp_op_split3": (_i, [_fp, _vp, C.c_size_t, _i, _i]),
     "arp_op_m3ae_assemble": (_i, [_fp, _fp, _fp, _fp, _fp, _i32p, _i, _i, _i, _i, _i, _i, _i, _fp]),
+    "arp_op_preprocess_forms": (_i, [_u8p, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp, _i32p]),
+    "arp_op_preprocess_bilinear": (_i, [_u8p, _i, _i, _i, _i, _i, _i, _vp]),
+    "arp_op_crop_u8": (_i, [_u8p, _i, _i, _i, _i, _i, _i, _u8p]),
+    "arp_op_patchify": (_i, [_fp, _i, _i, _i, _i, _vp]),
 }
 
 for _name, (_res, _args) in SIGNATURES.items():

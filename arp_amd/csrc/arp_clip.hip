@@ -402,6 +402,16 @@ static int get_plan(arp_clip* c, int H, int W, int use_crop, ResizePlan** out, b
     return 0;
 }
 
+// the fine-tune transform on nb frames of H x W: one thread per 4 output pixels of a channel; resizes only when BOTH sides differ from R
+template <typename T>
+static int launch_preprocess_bilinear(hipStream_t stream, const uint8_t* frames_dev, T* out, int nb, int H, int W, int R, int P) {
+    const size_t total = (size_t)nb * 3 * R * (R / 4);
+    hipLaunchKernelGGL((preprocess_bilinear_kernel<T>), dim3((unsigned)((total + 255) / 256)), dim3(256), 0, stream, frames_dev, out, nb, H, W, R, P,
+                       (H != R && W != R) ? 1 : 0);
+    ARP_HIP_OK(hipGetLastError());
+    return 0;
+}
+
 // frames (device) -> un-normalised image features in c->feat [nb, embed]
 template <typename T>
 static int forward_chunk(arp_clip* c, const uint8_t* frames_dev, int nb, ResizePlan* plan) {
@@ -414,11 +424,7 @@ static int forward_chunk(arp_clip* c, const uint8_t* frames_dev, int nb, ResizeP
     } lat_guard{c};
     if (c->pre_bilinear) {
         ProfScope ps(c->prof, c->stream, "preprocess_bilinear");
-        const int H = c->pre_bilinear >> 16, W = c->pre_bilinear & 0xffff, R = k.img_res;
-        const size_t total = (size_t)nb * 3 * R * (R / 4);
-        hipLaunchKernelGGL((preprocess_bilinear_kernel<T>), dim3((unsigned)((total + 255) / 256)), dim3(256), 0, c->stream, frames_dev, c->patches.as<T>(), nb,
-                           H, W, R, k.patch, (H != R && W != R) ? 1 : 0);
-        ARP_HIP_OK(hipGetLastError());
+        ARP_TRY(launch_preprocess_bilinear<T>(c->stream, frames_dev, c->patches.as<T>(), nb, c->pre_bilinear >> 16, c->pre_bilinear & 0xffff, k.img_res, k.patch));
     } else {
         ProfScope ps(c->prof, c->stream, "preprocess");
         ARP_TRY((launch_preprocess<T, PRE_PATCH>(*plan, frames_dev, nb, k.patch, c->lut, c->patches.p, c->stream)));
@@ -679,6 +685,20 @@ static __global__ __launch_bounds__(256) void crop_u8_kernel(const uint8_t* __re
     }
 }
 
+static int launch_crop_u8(hipStream_t stream, const uint8_t* src, uint8_t* dst, int n, int H, int W, int y0, int x0, int cs) {
+    const size_t total = (size_t)n * cs * cs * 3;
+    hipLaunchKernelGGL(crop_u8_kernel, dim3((unsigned)std::min<size_t>((total + 255) / 256, 4096)), dim3(256), 0, stream, src, dst, n, H, W, y0, x0, cs);
+    ARP_HIP_OK(hipGetLastError());
+    return 0;
+}
+
+// an h x w frame in front of the fine-tune transform at resolution R
+static int finetune_sides_ok(int h, int w, int R) {
+    if ((h != R) != (w != R)) return fail("the reference resizes only when BOTH sides differ from 224 (clip_multiscale_adapter.py:127): "
+                                          "a frame with exactly one side at 224 cannot enter the tower");
+    return 0;
+}
+
 // the frames the fine-tune transform's resize reads: the whole frame, or its centre crop of side W / 2
 static int ms_finetune_geometry(const arp_clip* c, int H, int W, int use_crop, int* h, int* w, int* y0, int* x0) {
     const int R = c->cfg.img_res;
@@ -689,9 +709,7 @@ static int ms_finetune_geometry(const arp_clip* c, int H, int W, int use_crop, i
         *h = *w = cs;
         *y0 = (int)((H - cs) / 2); *x0 = (int)((W - cs) / 2);
     }
-    if ((*h != R) != (*w != R)) return fail("the reference resizes only when BOTH sides differ from 224 (clip_multiscale_adapter.py:127): "
-                                            "a frame with exactly one side at 224 cannot enter the tower");
-    return 0;
+    return finetune_sides_ok(*h, *w, R);
 }
 
 int clip_ms_prepare(arp_clip* c, int nb, int H, int W, int use_crop, int transform, uint64_t* generation, int* capturable) {
@@ -739,9 +757,7 @@ int clip_ms_enqueue(arp_clip* c, const uint8_t* frames_dev, int nb, int H, int W
             const size_t total = (size_t)nb * h * w * 3;
             if (total > c->crop_buf.bytes) return fail("clip_ms_enqueue: call clip_ms_prepare first");
             ProfScope ps(c->prof, c->stream, "crop");
-            hipLaunchKernelGGL(crop_u8_kernel, dim3((unsigned)std::min<size_t>((total + 255) / 256, 4096)), dim3(256), 0, c->stream, frames_dev,
-                               c->crop_buf.as<uint8_t>(), nb, H, W, y0, x0, h);
-            ARP_HIP_OK(hipGetLastError());
+            ARP_TRY(launch_crop_u8(c->stream, frames_dev, c->crop_buf.as<uint8_t>(), nb, H, W, y0, x0, h));
             src = c->crop_buf.as<uint8_t>();
         }
         pre = (h << 16) | w;
@@ -1181,6 +1197,85 @@ int arp_preprocess(const uint8_t* frames, int n, int H, int W, int use_crop, int
     ARP_HIP_OK(hipDeviceSynchronize());
     ARP_HIP_OK(hipMemcpy(out, o.p, (size_t)n * ob, hipMemcpyDeviceToHost));
     return 0;
+}
+
+// The frame front ends one at a time, in the forms the passes launch (include/arp_hip.h).  Each entry owns its buffers; `out` goes up before the launch and
+// comes back after it, so the caller sees every byte the kernel did not write.
+namespace {
+int frontend_geometry(const char* who, const void* frames, const void* out, int n, int H, int W, int res, int patch, int mode) {
+    const std::string w(who);
+    if (!frames || !out || n <= 0 || H <= 0 || W <= 0 || H > 0xffff || W > 0xffff) return fail(w + ": bad argument");
+    if (mode != ARP_MODE_F32 && mode != ARP_MODE_BF16 && mode != ARP_MODE_F16) return fail(w + ": mode is 0 (f32), 1 (bf16) or 2 (binary16)");
+    if (res <= 0 || patch <= 0 || patch % 4 || res % patch) return fail(w + ": patch must be a multiple of 4 that divides res (four values per store)");
+    return 0;
+}
+struct FrontBufs {
+    DevBuf in, o;
+    void* host_out = nullptr;
+    size_t out_bytes = 0;
+    int up(const uint8_t* frames, size_t frame_bytes, void* out, size_t ob) {
+        host_out = out; out_bytes = ob;
+        ARP_TRY(in.ensure(frame_bytes)); ARP_TRY(o.ensure(ob));
+        ARP_HIP_OK(hipMemcpy(in.p, frames, frame_bytes, hipMemcpyHostToDevice));
+        ARP_HIP_OK(hipMemcpy(o.p, out, ob, hipMemcpyHostToDevice));
+        return 0;
+    }
+    int down(int rc) {
+        ARP_TRY(rc);
+        ARP_HIP_OK(hipDeviceSynchronize());
+        ARP_HIP_OK(hipMemcpy(host_out, o.p, out_bytes, hipMemcpyDeviceToHost));
+        return 0;
+    }
+};
+}  // namespace
+
+int arp_op_preprocess_forms(const uint8_t* frames, int n, int H, int W, int use_crop, int res, int patch, int mode, int layout, int tr_start, void* out,
+                            int32_t* info) {
+    ARP_TRY(frontend_geometry("preprocess_forms", frames, out, n, H, W, res, patch, mode));
+    if (!info) return fail("preprocess_forms: bad argument");
+    if (layout != PRE_PATCH && layout != PRE_NCHW) return fail("preprocess_forms: layout is 0 (patch-major) or 1 (NCHW)");
+    if (layout == PRE_NCHW && mode != ARP_MODE_F32) return fail("preprocess_forms: the NCHW form exists in f32 only (arp_preprocess)");
+    if (tr_start < 1 || tr_start > 32) return fail("preprocess_forms: tr_start is 1 .. 32 (the passes ask for 32 or 8)");
+    ResizePlan plan;
+    ARP_TRY(build_plan(H, W, use_crop, res, plan, tr_start));
+    const size_t fb = (size_t)H * W * 3, esz = mode == ARP_MODE_F32 ? 4 : 2;
+    FrontBufs b;
+    DevBuf lut;
+    ARP_TRY(b.up(frames, (size_t)n * fb, out, (size_t)n * 3 * res * res * esz));
+    ARP_TRY(lut.ensure(768 * 4));
+    std::vector<float> l(768);
+    build_lut(l.data());
+    ARP_HIP_OK(hipMemcpy(lut.p, l.data(), 768 * 4, hipMemcpyHostToDevice));
+    const int row_bytes = plan.cw * 3;
+    info[0] = preprocess_instance(plan); info[1] = plan.TR; info[2] = plan.kmax_h; info[3] = plan.kmax_v; info[4] = plan.max_rows;
+    info[5] = (int32_t)plan.lds_bytes;
+    info[6] = plan.cx == 0 && plan.cw == W && row_bytes % 16 == 0 && fb % 16 == 0 && (reinterpret_cast<uintptr_t>(b.in.p) & 15) == 0;
+    info[7] = (res + plan.TR - 1) / plan.TR;
+    int rc;
+    if (layout == PRE_NCHW) rc = launch_preprocess<float, PRE_NCHW>(plan, b.in.as<uint8_t>(), n, patch, lut.as<float>(), b.o.p, nullptr);
+    else if (mode == ARP_MODE_BF16) rc = launch_preprocess<bf16_t, PRE_PATCH>(plan, b.in.as<uint8_t>(), n, patch, lut.as<float>(), b.o.p, nullptr);
+    else if (mode == ARP_MODE_F16) rc = launch_preprocess<f16_t, PRE_PATCH>(plan, b.in.as<uint8_t>(), n, patch, lut.as<float>(), b.o.p, nullptr);
+    else rc = launch_preprocess<float, PRE_PATCH>(plan, b.in.as<uint8_t>(), n, patch, lut.as<float>(), b.o.p, nullptr);
+    return b.down(rc);
+}
+
+int arp_op_preprocess_bilinear(const uint8_t* frames, int n, int H, int W, int res, int patch, int mode, void* out) {
+    ARP_TRY(frontend_geometry("preprocess_bilinear", frames, out, n, H, W, res, patch, mode));
+    ARP_TRY(finetune_sides_ok(H, W, res));
+    FrontBufs b;
+    ARP_TRY(b.up(frames, (size_t)n * H * W * 3, out, (size_t)n * 3 * res * res * (mode == ARP_MODE_F32 ? 4 : 2)));
+    const uint8_t* in = b.in.as<uint8_t>();
+    return b.down(mode == ARP_MODE_BF16  ? launch_preprocess_bilinear<bf16_t>(nullptr, in, b.o.as<bf16_t>(), n, H, W, res, patch)
+                  : mode == ARP_MODE_F16 ? launch_preprocess_bilinear<f16_t>(nullptr, in, b.o.as<f16_t>(), n, H, W, res, patch)
+                                         : launch_preprocess_bilinear<float>(nullptr, in, b.o.as<float>(), n, H, W, res, patch));
+}
+
+int arp_op_crop_u8(const uint8_t* frames, int n, int H, int W, int y0, int x0, int cs, uint8_t* out) {
+    if (!frames || !out || n <= 0 || H <= 0 || W <= 0 || cs <= 0 || y0 < 0 || x0 < 0 || y0 + (long)cs > H || x0 + (long)cs > W)
+        return fail("crop_u8: the crop window must lie inside the frame");
+    FrontBufs b;
+    ARP_TRY(b.up(frames, (size_t)n * H * W * 3, out, (size_t)n * cs * cs * 3));
+    return b.down(launch_crop_u8(nullptr, b.in.as<uint8_t>(), b.o.as<uint8_t>(), n, H, W, y0, x0, cs));
 }
 
 int arp_clip_set_fp8_mlp(arp_clip* c, int on) {

@@ -136,6 +136,16 @@ __global__ __launch_bounds__(256) void patchify_split3_kernel(const float* __res
     *reinterpret_cast<uint2*>(o + 2 * (size_t)K) = make_uint2(hi[0], hi[1]);
 }
 
+// nb images -> patch rows of type T at `out`, or (X3) rows of (hi, lo, hi) binary16 triples; four values per thread
+template <typename T, bool X3> int launch_patchify(hipStream_t stream, const float* src, T* out, int nb, int res, int P) {
+    const size_t tot = (size_t)nb * (res / P) * (res / P) * P * P * 3;
+    const dim3 grid((unsigned)((tot / 4 + 255) / 256));
+    if constexpr (X3) hipLaunchKernelGGL(patchify_split3_kernel, grid, dim3(256), 0, stream, src, out, nb, res, P);
+    else hipLaunchKernelGGL((patchify_kernel<T>), grid, dim3(256), 0, stream, src, out, nb, res, P);
+    ARP_HIP_OK(hipGetLastError());
+    return 0;
+}
+
 struct HostTensor {
     std::vector<float> data;
     std::vector<int64_t> shape;
@@ -344,11 +354,7 @@ template <typename T, bool X3> int front_end(arp_enc* c, arp_enc::Ws& w, TowerCt
     {
         ProfScope ps(c->prof, t.stream, "m3ae.patchify");
         for (int s = 0; s < sets; ++s) {
-            const float* src = s ? seq.goals_dev : img_dev;
-            const dim3 grid((unsigned)((tot / 4 + 255) / 256));
-            if constexpr (X3) hipLaunchKernelGGL(patchify_split3_kernel, grid, dim3(256), 0, t.stream, src, patches + s * seg * tot, nb, k.img_res, k.patch);
-            else hipLaunchKernelGGL((patchify_kernel<T>), grid, dim3(256), 0, t.stream, src, patches + s * tot, nb, k.img_res, k.patch);
-            ARP_HIP_OK(hipGetLastError());
+            ARP_TRY((launch_patchify<T, X3>(t.stream, s ? seq.goals_dev : img_dev, patches + s * seg * tot, nb, k.img_res, k.patch)));
         }
     }
     ARP_TRY((tower_gemm<T, float, ACT_NONE, false, 8 + SITE_PATCH>(t, "m3ae.image_embedding", patches, w_emb, c->b_emb, nullptr, w.pe.p, sets * nb * G * G, k.width,
@@ -959,6 +965,27 @@ int arp_op_split3(const float* x, void* out, size_t out_bytes, int rows, int K) 
     const int rc = launch_split3(nullptr, dx.as<float>(), dout.as<f16_t>(), (size_t)rows, K);
     ARP_HIP_OK(hipDeviceSynchronize());
     ARP_HIP_OK(hipMemcpy(out, dout.p, out_bytes, hipMemcpyDeviceToHost));
+    return rc;
+}
+
+// The encoder's front: images f32 NHWC [n, res, res, 3] -> patch rows through the launcher front_end calls.  form 0 / 1 / 2: patchify_kernel<float | bf16 |
+// binary16>, rows of 3 P^2 values; form 3: patchify_split3_kernel, rows of 9 P^2 binary16 values [hi | lo | hi].  out goes up before the launch and comes back
+// after it.
+int arp_op_patchify(const float* images, int n, int res, int patch, int form, void* out) {
+    if (!images || !out || n <= 0 || res <= 0 || patch <= 0 || form < 0 || form > 3) return fail("arp_op_patchify: bad argument");
+    if (patch % 4 || res % patch) return fail("arp_op_patchify: patch must be a multiple of 4 that divides res (four values of a patch row per thread)");
+    const size_t vals = (size_t)n * res * res * 3, ob = vals * (form == 0 ? 4 : form == 3 ? 6 : 2);
+    DevBuf dx, dout;
+    ARP_TRY(dx.ensure(vals * 4)); ARP_TRY(dout.ensure(ob));
+    ARP_HIP_OK(hipMemcpy(dx.p, images, vals * 4, hipMemcpyHostToDevice));
+    ARP_HIP_OK(hipMemcpy(dout.p, out, ob, hipMemcpyHostToDevice));
+    const float* src = dx.as<float>();
+    const int rc = form == 0   ? launch_patchify<float, false>(nullptr, src, dout.as<float>(), n, res, patch)
+                   : form == 1 ? launch_patchify<bf16_t, false>(nullptr, src, dout.as<bf16_t>(), n, res, patch)
+                   : form == 2 ? launch_patchify<f16_t, false>(nullptr, src, dout.as<f16_t>(), n, res, patch)
+                               : launch_patchify<f16_t, true>(nullptr, src, dout.as<f16_t>(), n, res, patch);
+    ARP_HIP_OK(hipDeviceSynchronize());
+    ARP_HIP_OK(hipMemcpy(out, dout.p, ob, hipMemcpyDeviceToHost));
     return rc;
 }
 

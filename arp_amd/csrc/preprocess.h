@@ -9,8 +9,9 @@
 // are a 3x256-entry f32 lookup table computed on the host with the same IEEE f32 operations
 // torchvision's ToTensor/Normalize perform, so the f32 output is bit-identical by construction.
 //
-// One workgroup = one (frame, tile of TR output rows).  The input rows the tile needs (<= ~42 rows
-// of 768 B for 256->224, TR = 32) are fetched once with coalesced 16-byte loads into LDS, the
+// One workgroup = one (frame, tile of TR output rows).  The input rows the tile needs (<= 22 rows
+// of 768 B for 256->224 at TR = 16, the tile build_plan settles on under its 52 KiB LDS budget;
+// TR = 32 would need 40 rows and 65 KiB) are fetched once with coalesced 16-byte loads into LDS, the
 // horizontal pass writes a uint8 intermediate to LDS, the vertical pass reads it back and streams
 // the normalised result out in 8/16-byte vectors.
 #pragma once

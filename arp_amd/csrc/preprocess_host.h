@@ -142,6 +142,16 @@ static void build_lut(float* lut /* [3][256] */) {
         }
 }
 
+// Which kernel template serves a plan: 0 = preprocess_kernel (the generic one), otherwise the KT of preprocess_fast_kernel (5, 6 or 8).
+// short filters + dword-aligned rows: the register-unpacking instance; anything else: the generic one.  launch_preprocess launches what this returns and
+// arp_op_preprocess_forms reports it, so the two cannot disagree.
+static inline int preprocess_instance(const ResizePlan& p) {
+    const bool fast = p.kmax_h <= 8 && p.kmax_v <= 8 && ((p.cw * 3) & 3) == 0 && !getenv("ARP_PREPROCESS_GENERIC");
+    if (!fast) return 0;
+    const int kt = std::max(p.kmax_h, p.kmax_v);
+    return kt <= 5 ? 5 : (kt <= 6 ? 6 : 8);
+}
+
 template <typename T, int LAYOUT>
 static int launch_preprocess(const ResizePlan& p, const uint8_t* frames, int n, int P, const float* lut, void* out,
                              hipStream_t stream) {
@@ -150,10 +160,8 @@ static int launch_preprocess(const ResizePlan& p, const uint8_t* frames, int n, 
     a.h_tab = p.h_tab.as<int>(); a.v_tab = p.v_tab.as<int>(); a.lut = lut;
     a.n = n; a.H = p.H; a.W = p.W; a.cy = p.cy; a.cx = p.cx; a.ch = p.ch; a.cw = p.cw;
     a.R = p.R; a.P = P; a.kmax_h = p.kmax_h; a.kmax_v = p.kmax_v; a.TR = p.TR; a.max_rows = p.max_rows;
-    // short filters + dword-aligned rows: the register-unpacking instance; anything else: the generic one
-    const bool fast = p.kmax_h <= 8 && p.kmax_v <= 8 && ((p.cw * 3) & 3) == 0 && !getenv("ARP_PREPROCESS_GENERIC");
-    const int kt = std::max(p.kmax_h, p.kmax_v);
-    auto kern = !fast ? preprocess_kernel<T, LAYOUT> : (kt <= 5 ? preprocess_fast_kernel<T, LAYOUT, 5> : (kt <= 6 ? preprocess_fast_kernel<T, LAYOUT, 6> : preprocess_fast_kernel<T, LAYOUT, 8>));
+    const int inst = preprocess_instance(p);
+    auto kern = inst == 0 ? preprocess_kernel<T, LAYOUT> : (inst == 5 ? preprocess_fast_kernel<T, LAYOUT, 5> : (inst == 6 ? preprocess_fast_kernel<T, LAYOUT, 6> : preprocess_fast_kernel<T, LAYOUT, 8>));
     ARP_HIP_OK(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
                                    (int)p.lds_bytes));
     const int tiles = (p.R + p.TR - 1) / p.TR;

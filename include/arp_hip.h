@@ -754,6 +754,25 @@ int arp_op_split3(const float* x, void* out, size_t out_bytes, int rows, int K);
  * back after it.  Refuses D % 4 != 0, goal together with L > 0, and an id outside [0, vocab). */
 int arp_op_m3ae_assemble(const float* pe, const float* cls, const float* pos, const float* text_emb, const float* tpos, const int32_t* tok, int nb, int GG, int goal,
                          int L, int per_row, int D, int vocab, float* x);
+/* ---- the frame front ends, one kernel at a time, in the forms the passes launch ----
+ * Every `out` is a byte buffer the caller fills; it goes up before the launch and comes back after it.  patch % 4 == 0 and res % patch == 0 throughout.
+ *
+ * arp_op_preprocess_forms: the Pillow-exact bicubic transform of arp_preprocess (uint8 NHWC frames [n, H, W, 3]) through build_plan(tr_start) and
+ * launch_preprocess as a pass calls them.  mode 0 / 1 / 2 = f32 / bf16 / binary16; layout 0 = patch-major [n (res / patch)^2, 3 patch^2] (all modes),
+ * 1 = NCHW [n, 3, res, res] (f32 only; anything else is refused).  tr_start: the largest tile tried, 1 .. 32 (the passes ask for 32 or 8).
+ * info[8] receives what was chosen: [0] kernel instance (0 = the generic preprocess_kernel, 5 / 6 / 8 = preprocess_fast_kernel's KT), [1] TR, output rows
+ * per workgroup, [2] kmax_h, [3] kmax_v, [4] max_rows, [5] lds_bytes, [6] 1 when the kernel stages input rows with 16-byte loads (no horizontal crop, rows
+ * and frames multiples of 16 bytes), 0 when byte by byte, [7] tiles (workgroups) per frame.  ARP_PREPROCESS_GENERIC and ARP_PRE_LDS_KB apply. */
+int arp_op_preprocess_forms(const uint8_t* frames, int n, int H, int W, int use_crop, int res, int patch, int mode, int layout, int tr_start, void* out,
+                            int32_t* info);
+/* The fine-tune transform (preprocess_bilinear_kernel) with the grid and the resize rule of a pass: patch-major output in the mode's type; a frame with
+ * exactly one side at res is refused as a pass refuses it. */
+int arp_op_preprocess_bilinear(const uint8_t* frames, int n, int H, int W, int res, int patch, int mode, void* out);
+/* crop_u8_kernel: out [n, cs, cs, 3] = frames[:, y0 : y0 + cs, x0 : x0 + cs, :], the window inside the frame */
+int arp_op_crop_u8(const uint8_t* frames, int n, int H, int W, int y0, int x0, int cs, uint8_t* out);
+/* The M3AE encoder's patchify: images f32 NHWC [n, res, res, 3] -> rows "b (h p1) (w p2) c -> b (h w) (p1 p2 c)".  form 0 / 1 / 2: f32 / bf16 / binary16
+ * rows of 3 patch^2 values; form 3: rows of 9 patch^2 binary16 values [hi | lo | hi], hi = rn16(x), lo = rn16(x - hi). */
+int arp_op_patchify(const float* images, int n, int res, int patch, int form, void* out);
 /* The rollout session's decide kernel: logits [E, T, n_actions], lens[e] = window length L in [1, T] -> actions_out[e] = argmax of row L - 1 (the lowest
  * index wins a tie, the first NaN wins: numpy.argmax). */
 int arp_op_rollout_decide(const float* logits, const int32_t* lens, int E, int T, int n_actions, int32_t* actions_out);

@@ -211,7 +211,8 @@ def test_attention_x3_every_tile_boundary(gpu_lib, N, causal):
     assert err < 1e-5, f"N={N} causal={causal}: max err {err}"
 
 
-PRE_CASES = [(256, 256, False), (256, 256, True), (64, 64, False), (128, 96, False), (200, 300, False), (512, 512, True)]
+PRE_CASES = [(256, 256, False), (256, 256, True), (64, 64, False), (128, 96, False), (200, 300, False), (512, 512, True),
+             (512, 512, False), (400, 400, False), (320, 320, False), (64, 66, False)]   # generic (kmax 10), fast<8>, fast<6>, generic (198-byte rows)
 
 
 @pytest.mark.parametrize("case", PRE_CASES)
