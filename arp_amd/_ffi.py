@@ -195,6 +195,12 @@ SIGNATURES = {
     "arp_ft_comm_selfcheck": (_i, [_vp, C.POINTER(C.c_double)]),
     "arp_ft_bucket_plan": (_i, [C.POINTER(FtCfg), _i64p, _i64p]),
     "arp_ft_event_record": (_i, [_vp, _vp]),
+    "arp_ft_feed_attach": (_i, [_vp, _vp, _vp, _i32p]),
+    "arp_ft_feed_detach": (_i, [_vp]),
+    "arp_ft_feed_stage_async": (_i, [_vp, _i, _i64p, _i]),
+    "arp_ft_feed_train_step_async": (_i, [_vp, _i, C.c_float]),
+    "arp_ft_feed_collect": (_i, [_vp, _fp]),
+    "arp_ft_feed_forward": (_i, [_vp, _i, _fp, _fp, _fp]),
     "arp_ft_profile_enable": (_i, [_vp, _i]),
     "arp_ft_profile_reset": (_i, [_vp]),
     "arp_ft_profile_json": (_i, [_vp, C.c_char_p, _i]),
@@ -231,6 +237,8 @@ SIGNATURES = {
     "arp_dt_upload_batch_index_pairs_async": (_i, [_vp, _i, _vp, _i64p, _i64p, _i]),
     "arp_dt_set_batch_index_pairs": (_i, [_vp, _vp, _i64p, _i64p, _i]),
     "arp_ds_gather_pairs_debug": (_i, [_vp, _i64p, _i64p, _i, _i, _fp, _fp, _i32p]),
+    "arp_ds_set_quad_bounds": (_i, [_vp, _i32p, _i32p]),
+    "arp_ds_quads_debug": (_i, [_vp, _i64p, _i, _i, _i32p, _fp, _i32p]),
     "arp_rollout_create": (_i, [_vp, _vp, _i, _i, _i, _f, C.POINTER(_vp)]),
     "arp_rollout_create_with_encoder": (_i, [_vp, _vp, _vp, _i, _i, _i, _f, C.POINTER(_vp)]),
     "arp_rollout_create_ft": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _f, C.POINTER(_vp)]),
@@ -278,6 +286,7 @@ SIGNATURES = {
     "arp_op_m3ae_assemble": (_i, [_fp, _fp, _fp, _fp, _fp, _i32p, _i, _i, _i, _i, _i, _i, _i, _fp]),
     "arp_op_preprocess_forms": (_i, [_u8p, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp, _i32p]),
     "arp_op_preprocess_bilinear": (_i, [_u8p, _i, _i, _i, _i, _i, _i, _vp]),
+    "arp_op_preprocess_bilinear_rows": (_i, [_u8p, _i, _i32p, _i, _i, _i, _i, _i, _i, _i, _vp]),
     "arp_op_crop_u8": (_i, [_u8p, _i, _i, _i, _i, _i, _i, _u8p]),
     "arp_op_patchify": (_i, [_fp, _i, _i, _i, _i, _vp]),
 }

@@ -117,6 +117,10 @@ struct arp_clip : ClipModel {
     int ms_ld = 0;
     const int* ms_rows = nullptr;
     int pre_bilinear = 0;  // next forward_chunk uses the fine-tune transform (bilinear) instead of the PIL-bicubic one
+    // ... reading its frames through a row table (clip_ms_enqueue_rows): frames_dev is then a resident set of pre_set_h x pre_set_w frames, frame f of the
+    // pass is its row pre_rows[f], and (pre_bilinear >> 16) x (pre_bilinear & 0xffff) is the source window at (pre_y0, pre_x0) of such a frame
+    const int32_t* pre_rows = nullptr;
+    int pre_set_h = 0, pre_set_w = 0, pre_y0 = 0, pre_x0 = 0;
     std::vector<std::unique_ptr<arp_clip>> siblings;  // n_streams - 1 of them
     Event ev_fork;
     std::vector<Event> ev_join;  // one per sibling
@@ -412,6 +416,26 @@ static int launch_preprocess_bilinear(hipStream_t stream, const uint8_t* frames_
     return 0;
 }
 
+// the same transform on frames read through a row table from a resident set of H x W frames; (y0, x0, h, w): the source window (preprocess.h)
+template <typename T>
+static int launch_preprocess_bilinear_rows(hipStream_t stream, const uint8_t* set_dev, const int32_t* rows_dev, T* out, int nb, int H, int W, int y0, int x0, int h,
+                                           int w, int R, int P) {
+    BilinearRowsArgs a;
+    a.set = set_dev; a.rows = rows_dev; a.out = out;
+    a.n = nb; a.H = H; a.W = W; a.y0 = y0; a.x0 = x0; a.h = h; a.w = w; a.R = R; a.P = P;
+    a.resize = (h != R && w != R) ? 1 : 0;
+    // source rows P output rows can touch: y1(last) + 1 - y0(first) <= (P - 1) h / R + 3, the coordinates' own rounding included
+    a.max_rows = std::min(h, a.resize ? (int)((long long)(P - 1) * h / R) + 4 : P + 1);
+    const size_t lds = ((size_t)a.max_rows * w * 3 + 15) & ~(size_t)15;
+    a.staged = (W * 3) % 16 == 0 && (x0 * 3) % 16 == 0 && (w * 3) % 16 == 0 && (reinterpret_cast<uintptr_t>(set_dev) & 15) == 0 && lds <= 48 * 1024;
+    const unsigned grid = (unsigned)nb * (unsigned)(R / P);
+    const size_t shm = a.staged ? lds : 0;
+    if (sizeof(T) == 2 && P % 8 == 0) hipLaunchKernelGGL((preprocess_bilinear_rows_kernel<T, sizeof(T) == 2 ? 8 : 4>), dim3(grid), dim3(256), shm, stream, a);
+    else hipLaunchKernelGGL((preprocess_bilinear_rows_kernel<T, 4>), dim3(grid), dim3(256), shm, stream, a);
+    ARP_HIP_OK(hipGetLastError());
+    return 0;
+}
+
 // frames (device) -> un-normalised image features in c->feat [nb, embed]
 template <typename T>
 static int forward_chunk(arp_clip* c, const uint8_t* frames_dev, int nb, ResizePlan* plan) {
@@ -422,7 +446,11 @@ static int forward_chunk(arp_clip* c, const uint8_t* frames_dev, int nb, ResizeP
         arp_clip* c;
         ~LatGuard() { c->lat_now = false; c->lat_h0 = false; c->lat_f0 = false; }
     } lat_guard{c};
-    if (c->pre_bilinear) {
+    if (c->pre_bilinear && c->pre_rows) {
+        ProfScope ps(c->prof, c->stream, "preprocess_bilinear_rows");
+        ARP_TRY(launch_preprocess_bilinear_rows<T>(c->stream, frames_dev, c->pre_rows, c->patches.as<T>(), nb, c->pre_set_h, c->pre_set_w, c->pre_y0, c->pre_x0,
+                                                   c->pre_bilinear >> 16, c->pre_bilinear & 0xffff, k.img_res, k.patch));
+    } else if (c->pre_bilinear) {
         ProfScope ps(c->prof, c->stream, "preprocess_bilinear");
         ARP_TRY(launch_preprocess_bilinear<T>(c->stream, frames_dev, c->patches.as<T>(), nb, c->pre_bilinear >> 16, c->pre_bilinear & 0xffff, k.img_res, k.patch));
     } else {
@@ -765,6 +793,25 @@ int clip_ms_enqueue(arp_clip* c, const uint8_t* frames_dev, int nb, int H, int W
     c->ms_out = c->ms_res.as<float>(); c->ms_ld = c->vis.layers * c->cfg.width; c->ms_rows = nullptr; c->pre_bilinear = pre;
     const int r = forward_chunk_dispatch(c, src, nb, plan);
     c->ms_out = nullptr; c->pre_bilinear = 0;
+    ARP_TRY(r);
+    *inter = c->ms_res.as<float>();
+    *final_feat = c->feat.as<float>();
+    return 0;
+}
+
+// clip_ms_enqueue with the fine-tune transform reading its nb frames through a row table: frame f is row rows_dev[f] of the resident H x W set at set_base_dev
+// (every entry a row of the set: the caller's contract, arp_ds keeps it).  No gathered copy of the frames and no crop buffer: use_crop is the source window of
+// preprocess_bilinear_rows_kernel.  Same prepare, same tower dispatch (the non-graph one, as every pass with ms_out set), same export buffers.
+int clip_ms_enqueue_rows(arp_clip* c, const uint8_t* set_base_dev, const int32_t* rows_dev, int nb, int H, int W, int use_crop, const float** inter,
+                         const float** final_feat) {
+    if (!c || !set_base_dev || !rows_dev || !inter || !final_feat) return fail("null argument");
+    if (nb <= 0 || nb > c->ws_frames || (size_t)nb * c->vis.layers * c->cfg.width * 4 > c->ms_res.bytes) return fail("clip_ms_enqueue_rows: call clip_ms_prepare first");
+    int h, w, y0, x0;
+    ARP_TRY(ms_finetune_geometry(c, H, W, use_crop, &h, &w, &y0, &x0));
+    c->ms_out = c->ms_res.as<float>(); c->ms_ld = c->vis.layers * c->cfg.width; c->ms_rows = nullptr; c->pre_bilinear = (h << 16) | w;
+    c->pre_rows = rows_dev; c->pre_set_h = H; c->pre_set_w = W; c->pre_y0 = y0; c->pre_x0 = x0;
+    const int r = forward_chunk_dispatch(c, set_base_dev, nb, nullptr);
+    c->ms_out = nullptr; c->pre_bilinear = 0; c->pre_rows = nullptr;
     ARP_TRY(r);
     *inter = c->ms_res.as<float>();
     *final_feat = c->feat.as<float>();
@@ -1268,6 +1315,34 @@ int arp_op_preprocess_bilinear(const uint8_t* frames, int n, int H, int W, int r
     return b.down(mode == ARP_MODE_BF16  ? launch_preprocess_bilinear<bf16_t>(nullptr, in, b.o.as<bf16_t>(), n, H, W, res, patch)
                   : mode == ARP_MODE_F16 ? launch_preprocess_bilinear<f16_t>(nullptr, in, b.o.as<f16_t>(), n, H, W, res, patch)
                                          : launch_preprocess_bilinear<float>(nullptr, in, b.o.as<float>(), n, H, W, res, patch));
+}
+
+// preprocess_bilinear_rows_kernel alone: frame f of the output is row rows[f] of the n_set frames, through the source window use_crop names
+int arp_op_preprocess_bilinear_rows(const uint8_t* set_frames, int n_set, const int32_t* rows, int n, int H, int W, int use_crop, int res, int patch, int mode,
+                                    void* out) {
+    ARP_TRY(frontend_geometry("preprocess_bilinear_rows", set_frames, out, n, H, W, res, patch, mode));
+    if (!rows || n_set <= 0) return fail("preprocess_bilinear_rows: bad argument");
+    for (int f = 0; f < n; ++f)
+        if (rows[f] < 0 || rows[f] >= n_set)
+            return fail("preprocess_bilinear_rows: row " + std::to_string(rows[f]) + " (frame " + std::to_string(f) + ") is outside the set's " + std::to_string(n_set) + " frames");
+    int h = H, w = W, y0 = 0, x0 = 0;
+    if (use_crop) {
+        const int cs = W / 2;
+        if (cs <= 0 || cs > H) return fail("use_crop: the centre crop of side W / 2 does not fit the frame");
+        h = w = cs;
+        y0 = (int)((H - cs) / 2); x0 = (int)((W - cs) / 2);
+    }
+    ARP_TRY(finetune_sides_ok(h, w, res));
+    FrontBufs b;
+    DevBuf dr;
+    ARP_TRY(b.up(set_frames, (size_t)n_set * H * W * 3, out, (size_t)n * 3 * res * res * (mode == ARP_MODE_F32 ? 4 : 2)));
+    ARP_TRY(dr.ensure((size_t)n * 4));
+    ARP_HIP_OK(hipMemcpy(dr.p, rows, (size_t)n * 4, hipMemcpyHostToDevice));
+    const uint8_t* in = b.in.as<uint8_t>();
+    const int32_t* rd = dr.as<int32_t>();
+    return b.down(mode == ARP_MODE_BF16  ? launch_preprocess_bilinear_rows<bf16_t>(nullptr, in, rd, b.o.as<bf16_t>(), n, H, W, y0, x0, h, w, res, patch)
+                  : mode == ARP_MODE_F16 ? launch_preprocess_bilinear_rows<f16_t>(nullptr, in, rd, b.o.as<f16_t>(), n, H, W, y0, x0, h, w, res, patch)
+                                         : launch_preprocess_bilinear_rows<float>(nullptr, in, rd, b.o.as<float>(), n, H, W, y0, x0, h, w, res, patch));
 }
 
 int arp_op_crop_u8(const uint8_t* frames, int n, int H, int W, int y0, int x0, int cs, uint8_t* out) {

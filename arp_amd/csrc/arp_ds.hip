@@ -20,10 +20,10 @@ using namespace arp;
 struct arp_ds {
     int n_rows = 0, res = 0, device = 0;
     size_t fb = 0;  // bytes of one uint8 frame = floats of one f32 frame
-    DevBuf frames, action, rtg, start, lut, enc, iota;
+    DevBuf frames, action, rtg, start, lut, enc, iota, qfirst, qlast;  // qfirst / qlast: the fine-tune quads' per-row trajectory interval (arp_ds_set_quad_bounds)
     std::vector<uint8_t> row_up, enc_up;  // which rows have been uploaded
     int n_up = 0, n_enc_up = 0;
-    bool labels = false, has_rtg = false, has_lut = false;
+    bool labels = false, has_rtg = false, has_lut = false, has_quads = false;
     int n_actions = 0, tokens = 0, dim = 0;
     size_t enc_row() const { return (size_t)tokens * dim; }
 };
@@ -106,6 +106,27 @@ __global__ void ds_label_gather_kernel(const int32_t* __restrict__ action, const
     const int j = ds_source_row(idx, start, f, T);
     if (action_out) action_out[f] = action[j];
     if (rtg_out) rtg_out[f] = rtg[j];
+}
+
+// The fine-tune step's four rows (finetune_module/action_finetune_data_procgen.py:144,162,164): one lane per sample,
+//     q = sort(first[i], i, min(i + 1, last[i]), last[i]),  r = q[2] == q[3],  action = action[q[0]].
+// The sort is not a formality: a row behind the last done flag carries trajectory 0's interval, which does not contain it (arp_amd/finetune_data.py).  A fixed
+// five-comparator network; rows go out group-major (rows_out[g * B + b], g < G), the order the head reads image0 | image1 | image2 (| image3).
+__global__ void ds_quads_kernel(const int32_t* __restrict__ idx, const int32_t* __restrict__ first, const int32_t* __restrict__ last,
+                                const int32_t* __restrict__ action, int B, int G, int32_t* __restrict__ rows_out, float* __restrict__ r_out,
+                                int32_t* __restrict__ action_out) {
+    const int b = blockIdx.x * blockDim.x + threadIdx.x;
+    if (b >= B) return;
+    const int i = idx[b], l = last[i];
+    int q0 = first[i], q1 = i, q2 = min(i + 1, l), q3 = l;
+    auto cx = [](int& x, int& y) { const int lo = min(x, y), hi = max(x, y); x = lo; y = hi; };
+    cx(q0, q1); cx(q2, q3); cx(q0, q2); cx(q1, q3); cx(q1, q2);
+    const int q[4] = {q0, q1, q2, q3};
+#pragma unroll
+    for (int g = 0; g < 4; ++g)
+        if (g < G) rows_out[(size_t)g * B + b] = q[g];
+    r_out[b] = q2 == q3 ? 1.f : 0.f;
+    action_out[b] = action[q0];
 }
 
 // blocks along a row: enough for DS_TARGET_BLOCKS in all, at most one per tile
@@ -201,9 +222,88 @@ int ds_gather_pairs_on(arp_ds* d, hipStream_t st, const int32_t* idx_dev, const 
     return 0;
 }
 
+int ds_check_quads(arp_ds* d, const int64_t* idx, int B, int G, int device, int n_actions, int* res) {
+    if (!d || !idx || B <= 0) return fail("bad argument");
+    if (G != 3 && G != 4) return fail("a fine-tune sample has 3 image groups, or 4 with its goal frame");
+    if (d->device != device) return fail("the dataset lives on device " + std::to_string(d->device) + ", the handle on device " + std::to_string(device));
+    if (!d->labels) return fail("the dataset's labels are not set (arp_ds_set_labels)");
+    if (!d->has_quads) return fail("the dataset's quad bounds are not set (arp_ds_set_quad_bounds)");
+    if (d->n_up != d->n_rows) return fail("only " + std::to_string(d->n_up) + " of " + std::to_string(d->n_rows) + " frame rows were uploaded");
+    if (n_actions > 0 && d->n_actions > n_actions) return fail("the dataset's actions go up to " + std::to_string(d->n_actions) + " ids, the handle has " + std::to_string(n_actions));
+    for (int b = 0; b < B; ++b)
+        if (idx[b] < 0 || idx[b] >= d->n_rows) return fail("index " + std::to_string((long long)idx[b]) + " (batch position " + std::to_string(b) + ") is outside [0, " + std::to_string(d->n_rows) + ")");
+    if (res) *res = d->res;
+    return 0;
+}
+
+int ds_quads_on(arp_ds* d, hipStream_t st, const int32_t* idx_dev, int B, int G, int32_t* rows_out, float* r_out, int32_t* action_out) {
+    if (!d->labels || !d->has_quads) return fail("the dataset's labels and quad bounds must be set (arp_ds_set_labels, arp_ds_set_quad_bounds)");
+    if (B <= 0 || (G != 3 && G != 4) || !idx_dev || !rows_out || !r_out || !action_out) return fail("ds_quads_on: bad argument");
+    hipLaunchKernelGGL(ds_quads_kernel, dim3((B + 63) / 64), dim3(64), 0, st, idx_dev, d->qfirst.as<int32_t>(), d->qlast.as<int32_t>(), d->action.as<int32_t>(), B, G,
+                       rows_out, r_out, action_out);
+    ARP_HIP_OK(hipGetLastError());
+    return 0;
+}
+
+const uint8_t* ds_frames_of(arp_ds* d) { return d->frames.as<uint8_t>(); }
+
+int ds_info(arp_ds* d, int* n_rows, int* res, int* device) {
+    if (!d) return fail("null dataset handle");
+    *n_rows = d->n_rows; *res = d->res; *device = d->device;
+    return 0;
+}
+
 }  // namespace arp
 
 extern "C" {
+
+// The per-row trajectory interval the fine-tune quads are computed from (ProcgenActionDataset.bounds()): 0 <= first <= last < n_rows for every row.
+// NOT first <= row <= last: the rows behind the last done flag carry trajectory 0's interval (the reference's quirk, kept).
+int arp_ds_set_quad_bounds(arp_ds* d, const int32_t* first, const int32_t* last) {
+    if (!d || !first || !last) return fail("null argument");
+    for (int i = 0; i < d->n_rows; ++i)
+        if (first[i] < 0 || first[i] > last[i] || last[i] >= d->n_rows)
+            return fail("row " + std::to_string(i) + ": quad bounds [" + std::to_string(first[i]) + ", " + std::to_string(last[i]) + "] are not an interval inside [0, " +
+                        std::to_string(d->n_rows) + ")");
+    ARP_HIP_OK(hipSetDevice(d->device));
+    const size_t nb = (size_t)d->n_rows * 4;
+    ARP_TRY(d->qfirst.ensure(nb));
+    ARP_TRY(d->qlast.ensure(nb));
+    ARP_HIP_OK(hipMemcpy(d->qfirst.p, first, nb, hipMemcpyHostToDevice));
+    ARP_HIP_OK(hipMemcpy(d->qlast.p, last, nb, hipMemcpyHostToDevice));
+    d->has_quads = true;
+    return 0;
+}
+
+// Debug read-back of the quads B indices name: rows_out int32 [G, B] (group-major), r_out f32 [B], action_out int32 [B].  Synchronous, on the null stream.
+int arp_ds_quads_debug(arp_ds* d, const int64_t* idx, int B, int G, int32_t* rows_out, float* r_out, int32_t* action_out) {
+    if (!d || !rows_out || !r_out || !action_out) return fail("null argument");
+    ARP_TRY(ds_check_quads(d, idx, B, G, d->device, 0, nullptr));
+    ARP_HIP_OK(hipSetDevice(d->device));
+    std::vector<int32_t> h(idx, idx + B);
+    // each output is followed on the device by one guard word the kernel must leave alone: a store past an array's end is an error of this call
+    constexpr uint32_t GUARD = 0x5a5a5a5au;
+    const size_t nq = (size_t)G * B, nb = (size_t)B;
+    DevBuf di, dq, dr, da;  // (freed on every return; hipFree waits for the kernel)
+    ARP_TRY(di.ensure(nb * 4));
+    ARP_TRY(dq.ensure((nq + 1) * 4));
+    ARP_TRY(dr.ensure((nb + 1) * 4));
+    ARP_TRY(da.ensure((nb + 1) * 4));
+    ARP_HIP_OK(hipMemcpy(di.p, h.data(), nb * 4, hipMemcpyHostToDevice));
+    ARP_HIP_OK(hipMemcpy(dq.as<uint32_t>() + nq, &GUARD, 4, hipMemcpyHostToDevice));
+    ARP_HIP_OK(hipMemcpy(dr.as<uint32_t>() + nb, &GUARD, 4, hipMemcpyHostToDevice));
+    ARP_HIP_OK(hipMemcpy(da.as<uint32_t>() + nb, &GUARD, 4, hipMemcpyHostToDevice));
+    ARP_TRY(ds_quads_on(d, nullptr, di.as<int32_t>(), B, G, dq.as<int32_t>(), dr.as<float>(), da.as<int32_t>()));
+    uint32_t g[3] = {0, 0, 0};
+    ARP_HIP_OK(hipMemcpy(&g[0], dq.as<uint32_t>() + nq, 4, hipMemcpyDeviceToHost));
+    ARP_HIP_OK(hipMemcpy(&g[1], dr.as<uint32_t>() + nb, 4, hipMemcpyDeviceToHost));
+    ARP_HIP_OK(hipMemcpy(&g[2], da.as<uint32_t>() + nb, 4, hipMemcpyDeviceToHost));
+    if (g[0] != GUARD || g[1] != GUARD || g[2] != GUARD) return fail("arp_ds_quads_debug: the quad kernel wrote past the end of an output");
+    ARP_HIP_OK(hipMemcpy(rows_out, dq.p, nq * 4, hipMemcpyDeviceToHost));
+    ARP_HIP_OK(hipMemcpy(r_out, dr.p, nb * 4, hipMemcpyDeviceToHost));
+    ARP_HIP_OK(hipMemcpy(action_out, da.p, nb * 4, hipMemcpyDeviceToHost));
+    return 0;
+}
 
 int arp_ds_create(int64_t n_rows, int res, int device, arp_ds** out) {
     if (!out) return fail("null argument");
@@ -389,7 +489,7 @@ int arp_ds_gather_pairs_debug(arp_ds* d, const int64_t* idx, const int64_t* goal
 // HBM the dataset holds, in bytes
 int64_t arp_ds_nbytes(arp_ds* d) {
     if (!d) return 0;
-    return (int64_t)(d->frames.bytes + d->action.bytes + d->rtg.bytes + d->start.bytes + d->lut.bytes + d->enc.bytes + d->iota.bytes);
+    return (int64_t)(d->frames.bytes + d->action.bytes + d->rtg.bytes + d->start.bytes + d->lut.bytes + d->enc.bytes + d->iota.bytes + d->qfirst.bytes + d->qlast.bytes);
 }
 
 }  // extern "C"

@@ -21,12 +21,14 @@
 
 #include <algorithm>
 #include <map>
+#include <memory>
 #include <string>
 #include <vector>
 
 #include "../../include/arp_hip.h"
 #include "clip_internal.h"
 #include "common.h"
+#include "ds_internal.h"
 #include "dtops.h"
 #include "ftops.h"
 #include "ftrows.h"
@@ -113,6 +115,25 @@ struct arp_ft {
         std::vector<Graph> graphs;
         bool use_graph = true;         // ARP_FT_REWARD_GRAPH=0, or a capture that did not take: launch by launch
     } res;
+    // ---- the feed (arp_ft_feed_*): batches built on the device from a resident demonstration set.  A batch is B row indices; the towers' stream turns them
+    // into the slot's features (quad kernel -> transform from rows -> vision tower -> copy out of the towers' export buffers), the head's stream stages the
+    // slot into x_in / x_fin / r / action and steps.  Two slots, two events each way: `ready` (towers' stream -> head's stream: the slot holds its batch),
+    // `consumed` (head's stream -> towers' stream: the slot has been copied out and may be refilled).  No hipGraph, no host synchronisation on the path.
+    struct Feed {
+        arp_clip* towers = nullptr;
+        arp_ds* ds = nullptr;
+        int res = 0;
+        DevBuf t_inter, t_final;  // the ONE prompt's tower features [1, Dt], [1, embed] (null tokens: a goal_conditioned head reads none)
+        struct Slot {
+            DevBuf inter, fin, r, action, rows, idx;  // [G B, Dv] f32, [G B, embed] f32, [B] f32, [B] int32, [G B] int32, [B] int32
+            PinBuf idx_host;                          // index staging
+            Event ready, consumed, uploaded;
+            int cap = 0, B = 0;                       // rows the buffers hold; rows of the staged batch
+            bool staged = false;                      // holds a batch no step has taken yet
+            bool was_consumed = false, was_uploaded = false;  // the events have been recorded at least once
+        } slot[2];
+    };
+    std::unique_ptr<Feed> feed;  // (null: no feed attached; everything above is released with it)
     Profiler prof;
     // data parallelism (BASELINE configs[4]: DP = 8): one process per GPU, one all-reduce(sum) of the flat gradient per step
     ncclComm_t comm = nullptr;
@@ -756,9 +777,9 @@ int res_ensure_dispatch(arp_ft* c, hipStream_t st, int rows) {
 }
 
 // what every entry of the path refuses before it touches the device
-int res_check(arp_ft* c, arp_clip* towers, ClipMsInfo* ci) {
+// device and geometry of a (head, towers) pair
+int towers_match(arp_ft* c, arp_clip* towers, ClipMsInfo* ci) {
     if (!c || !towers) return fail("null handle");
-    if (c->cfg.goal_conditioned) return fail("the resident reward path has no goal frames: a goal_conditioned head is refused (pass rewards= computed by the caller)");
     ARP_TRY(clip_ms_info(towers, ci));
     if (ci->device != c->cfg.device)
         return fail("the towers live on device " + std::to_string(ci->device) + ", the head on device " + std::to_string(c->cfg.device));
@@ -769,6 +790,11 @@ int res_check(arp_ft* c, arp_clip* towers, ClipMsInfo* ci) {
                     std::to_string(k.width_v) + ", width_t " + std::to_string(k.width_t) + ", layers " + std::to_string(k.layers) + ", embed " +
                     std::to_string(k.embed) + ")");
     return 0;
+}
+int res_check(arp_ft* c, arp_clip* towers, ClipMsInfo* ci) {
+    if (!c || !towers) return fail("null handle");
+    if (c->cfg.goal_conditioned) return fail("the resident reward path has no goal frames: a goal_conditioned head is refused (pass rewards= computed by the caller)");
+    return towers_match(c, towers, ci);
 }
 int res_check_text(arp_ft* c, arp_clip* towers) {
     if (c->res.n_prompts <= 0) return fail("no prompts cached: call arp_ft_reward_set_text first");
@@ -923,7 +949,7 @@ int arp_ft_destroy(arp_ft* c) {
     if (!c) return 0;
     (void)hipSetDevice(c->cfg.device);
     if (c->stream) (void)hipStreamSynchronize(c->stream);
-    if (c->res.rows > 0) (void)hipDeviceSynchronize();  // the resident reward path runs on the towers' stream, which this handle does not own
+    if (c->res.rows > 0 || c->feed) (void)hipDeviceSynchronize();  // the resident reward path and the feed run on the towers' stream, which this handle does not own
     res_drop_graphs(c);
     if (c->has_comm && rccl_api()) (void)rccl_api()->CommDestroy(c->comm);
     if (c->comm_stream) (void)hipStreamSynchronize(c->comm_stream);
@@ -1291,6 +1317,169 @@ int arp_ft_event_record(arp_ft* c, arp_event* e) {
     ARP_HIP_OK(hipEventRecord(e->e, c->stream));
     return 0;
 }
+// ---- the feed: fine-tune batches from a device-resident demonstration set -------------------------------------------------------------------------------
+extern "C++" {
+namespace {
+// dst[b, :] = src[0, :]: the one prompt's tower features under every sample (what a host-built batch tiles B times)
+__global__ __launch_bounds__(256) void ft_bcast_row_kernel(const float* __restrict__ src, float* __restrict__ dst, int B, int D) {
+    const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (i < (size_t)B * D) dst[i] = src[i % D];
+}
+
+int feed_slot(arp_ft* c, int slot, arp_ft::Feed::Slot** out) {
+    if (!c) return fail("null handle");
+    if (!c->feed) return fail("no feed attached: call arp_ft_feed_attach first");
+    if (slot < 0 || slot > 1) return fail("a feed has slots 0 and 1");
+    *out = &c->feed->slot[slot];
+    return 0;
+}
+
+// head's side of a slot: wait for `ready`, copy the slot into the step's inputs, record `consumed`.  The staged batch is taken: one step per staging.
+int feed_take(arp_ft* c, int slot) {
+    arp_ft::Feed::Slot* s = nullptr;
+    ARP_TRY(feed_slot(c, slot, &s));
+    if (!s->staged) return fail("slot " + std::to_string(slot) + " holds no staged batch (arp_ft_feed_stage_async fills it; ONE step or forward takes it)");
+    ARP_HIP_OK(hipSetDevice(c->cfg.device));
+    const int B = s->B, G = c->groups();
+    const size_t E = c->cfg.embed;
+    ARP_TRY(ensure_buffers(c, B));
+    ARP_HIP_OK(hipStreamWaitEvent(c->stream, s->ready, 0));
+    ARP_HIP_OK(hipMemcpyAsync(c->x_in[0].p, s->inter.p, (size_t)G * B * c->Dv() * 4, hipMemcpyDeviceToDevice, c->stream));
+    ARP_HIP_OK(hipMemcpyAsync(c->x_fin[0].p, s->fin.p, (size_t)G * B * E * 4, hipMemcpyDeviceToDevice, c->stream));
+    if (!c->cfg.goal_conditioned) {
+        hipLaunchKernelGGL(ft_bcast_row_kernel, dim3(cdiv((size_t)B * c->Dt(), 256)), dim3(256), 0, c->stream, c->feed->t_inter.as<float>(), c->x_in[1].as<float>(), B, c->Dt());
+        hipLaunchKernelGGL(ft_bcast_row_kernel, dim3(cdiv((size_t)B * E, 256)), dim3(256), 0, c->stream, c->feed->t_final.as<float>(), c->x_fin[1].as<float>(), B, (int)E);
+        ARP_HIP_OK(hipGetLastError());
+    }
+    ARP_HIP_OK(hipMemcpyAsync(c->r.p, s->r.p, (size_t)B * 4, hipMemcpyDeviceToDevice, c->stream));
+    ARP_HIP_OK(hipMemcpyAsync(c->action.p, s->action.p, (size_t)B * 4, hipMemcpyDeviceToDevice, c->stream));
+    ARP_HIP_OK(hipEventRecord(s->consumed, c->stream));
+    s->was_consumed = true;
+    s->staged = false;
+    return 0;
+}
+}  // namespace
+}  // extern "C++"
+
+// Attach: check device and geometry (towers against the head's cfg, the set's frames against the fine-tune transform), run the text tower's multi-scale
+// export ONCE for the one prompt every sample shares (tokens [1, ctx]; NULL for a goal_conditioned head, which reads none) and keep it in HBM.  The slots'
+// buffers come with the first staging of a size.  Everything belongs to the head handle: arp_ft_feed_detach gives it back, and so does arp_ft_destroy.
+int arp_ft_feed_attach(arp_ft* c, arp_clip* towers, arp_ds* ds, const int32_t* tokens) {
+    ClipMsInfo ci;
+    ARP_TRY(towers_match(c, towers, &ci));
+    if (!ds) return fail("null dataset handle");
+    if (c->feed) return fail("a feed is attached already: arp_ft_feed_detach first");
+    if (c->cfg.goal_conditioned && tokens) return fail("a goal_conditioned head reads no prompt (image3 stands where it stands): pass no tokens");
+    if (!c->cfg.goal_conditioned && !tokens) return fail("the head reads a prompt: pass its tokens [1, ctx] (only a goal_conditioned head takes none)");
+    int n_rows = 0, res = 0, dev = 0;
+    ARP_TRY(ds_info(ds, &n_rows, &res, &dev));
+    if (dev != c->cfg.device) return fail("the dataset lives on device " + std::to_string(dev) + ", the head on device " + std::to_string(c->cfg.device));
+    ARP_HIP_OK(hipSetDevice(c->cfg.device));
+    uint64_t gen = 0;
+    int capturable = 0;
+    ARP_TRY(clip_ms_prepare(towers, 1, res, res, 0, CLIP_TF_FINETUNE, &gen, &capturable));  // (refuses a frame geometry the fine-tune transform cannot take)
+    auto f = std::make_unique<arp_ft::Feed>();
+    if (tokens) {
+        ARP_TRY(f->t_inter.ensure((size_t)c->Dt() * 4));
+        ARP_TRY(f->t_final.ensure((size_t)c->cfg.embed * 4));
+        ARP_TRY(arp_clip_encode_text_multiscale_dev(towers, tokens, 1, f->t_inter.as<float>(), f->t_final.as<float>()));
+        ARP_HIP_OK(hipStreamSynchronize(ci.stream));
+    }
+    for (auto& s : f->slot) {
+        ARP_TRY(s.ready.create());
+        ARP_TRY(s.consumed.create());
+        ARP_TRY(s.uploaded.create());
+    }
+    f->towers = towers;
+    f->ds = ds;
+    f->res = res;
+    c->feed = std::move(f);
+    return 0;
+}
+
+int arp_ft_feed_detach(arp_ft* c) {
+    if (!c) return fail("null handle");
+    if (!c->feed) return 0;
+    (void)hipSetDevice(c->cfg.device);
+    (void)hipDeviceSynchronize();  // (the towers' stream, which this handle does not own, may still be filling a slot)
+    c->feed.reset();
+    return 0;
+}
+
+// Stage a batch of B row indices into a slot, on the towers' stream: host checks, index upload, wait for the slot's `consumed`, quad kernel, transform from
+// rows + vision tower for G B frames, the export copied into the slot (the towers' buffers live only until their next pass), `ready` recorded.  Nothing is
+// waited for on the host (a slot that grows, or the towers' buffers, synchronise once per size; the index staging waits for its own previous upload, which
+// has long run unless the same slot is staged twice in a row).
+int arp_ft_feed_stage_async(arp_ft* c, int slot, const int64_t* idx, int B) {
+    arp_ft::Feed::Slot* s = nullptr;
+    ARP_TRY(feed_slot(c, slot, &s));
+    arp_ft::Feed& f = *c->feed;
+    const int G = c->groups();
+    ClipMsInfo ci;
+    ARP_TRY(clip_ms_info(f.towers, &ci));
+    ARP_TRY(ds_check_quads(f.ds, idx, B, G, c->cfg.device, c->cfg.n_actions, nullptr));
+    if ((long long)G * B > ci.max_batch)
+        return fail("a batch of " + std::to_string(B) + " samples is " + std::to_string((long long)G * B) + " frames in one tower pass, the towers were created with max_batch " +
+                    std::to_string(ci.max_batch));
+    ARP_HIP_OK(hipSetDevice(c->cfg.device));
+    hipStream_t st = ci.stream;
+    const size_t M = (size_t)G * B, Dv = c->Dv(), E = c->cfg.embed;
+    if (B > s->cap) {  // both streams may still touch the buffers about to move
+        ARP_HIP_OK(hipStreamSynchronize(st));
+        ARP_HIP_OK(hipStreamSynchronize(c->stream));
+        ARP_TRY(s->inter.ensure(M * Dv * 4)); ARP_TRY(s->fin.ensure(M * E * 4)); ARP_TRY(s->rows.ensure(M * 4));
+        ARP_TRY(s->r.ensure((size_t)B * 4)); ARP_TRY(s->action.ensure((size_t)B * 4)); ARP_TRY(s->idx.ensure((size_t)B * 4));
+        ARP_TRY(s->idx_host.ensure((size_t)B * 4));
+        s->cap = B;
+    }
+    uint64_t gen = 0;
+    int capturable = 0;
+    ARP_TRY(clip_ms_prepare(f.towers, (int)M, f.res, f.res, 0, CLIP_TF_FINETUNE, &gen, &capturable));
+    if (s->was_uploaded) ARP_HIP_OK(hipEventSynchronize(s->uploaded));
+    s->staged = false;  // (whatever the slot held is being overwritten)
+    for (int b = 0; b < B; ++b) s->idx_host.as<int32_t>()[b] = (int32_t)idx[b];
+    ARP_HIP_OK(hipMemcpyAsync(s->idx.p, s->idx_host.p, (size_t)B * 4, hipMemcpyHostToDevice, st));
+    ARP_HIP_OK(hipEventRecord(s->uploaded, st));
+    s->was_uploaded = true;
+    if (s->was_consumed) ARP_HIP_OK(hipStreamWaitEvent(st, s->consumed, 0));
+    ARP_TRY(ds_quads_on(f.ds, st, s->idx.as<int32_t>(), B, G, s->rows.as<int32_t>(), s->r.as<float>(), s->action.as<int32_t>()));
+    const float *inter = nullptr, *fin = nullptr;
+    ARP_TRY(clip_ms_enqueue_rows(f.towers, ds_frames_of(f.ds), s->rows.as<int32_t>(), (int)M, f.res, f.res, 0, &inter, &fin));
+    ARP_HIP_OK(hipMemcpyAsync(s->inter.p, inter, M * Dv * 4, hipMemcpyDeviceToDevice, st));
+    ARP_HIP_OK(hipMemcpyAsync(s->fin.p, fin, M * E * 4, hipMemcpyDeviceToDevice, st));
+    ARP_HIP_OK(hipEventRecord(s->ready, st));
+    s->B = B;
+    s->staged = true;
+    return 0;
+}
+
+// One train step on a staged slot: the head's stream waits for `ready`, copies the slot into the step's inputs (the cached prompt row under every sample),
+// records `consumed`, then runs the existing step -- its all-reduce path included when a communicator exists.  Enqueued; arp_ft_feed_collect reads the losses.
+int arp_ft_feed_train_step_async(arp_ft* c, int slot, float lr) {
+    ARP_TRY(feed_take(c, slot));
+    if (c->cfg.mode == ARP_MODE_F16) return step_impl<f16_t>(c, lr, nullptr);
+    return c->cfg.mode == ARP_MODE_BF16 ? step_impl<bf16_t>(c, lr, nullptr) : step_impl<float>(c, lr, nullptr);
+}
+
+// waits for the head's stream and reads the last step's losses (aux4 as arp_ft_train_step's: rank means under data parallelism)
+int arp_ft_feed_collect(arp_ft* c, float* aux4) {
+    if (!c || !aux4) return fail("null argument");
+    if (!c->metrics.p) return fail("no step has run");
+    ARP_HIP_OK(hipSetDevice(c->cfg.device));
+    ARP_HIP_OK(hipMemcpyAsync(aux4, c->metrics.p, 16, hipMemcpyDeviceToHost, c->stream));
+    ARP_HIP_OK(hipStreamSynchronize(c->stream));
+    const float inv = 1.0f / (float)std::max(c->world, 1);
+    for (int i = 0; i < 3; ++i) aux4[i] *= inv;
+    if (c->world > 1) aux4[3] *= inv;
+    return 0;
+}
+
+// the same staging, then the forward only (the reference's valid_epoch); synchronous like arp_ft_forward
+int arp_ft_feed_forward(arp_ft* c, int slot, float* metrics4, float* scores, float* logits) {
+    ARP_TRY(feed_take(c, slot));
+    return arp_ft_forward(c, metrics4, scores, logits);
+}
+
 // Data parallelism (BASELINE configs[4]): the id comes from arp_dt_comm_unique_id (one RCCL id serves any handle type)
 // Flat-gradient ranges of the data-parallel step's seven all-reduce buckets in production order, from the configuration alone (no
 // GPU): ranges28 = {lo, hi} x 14 in floats (bucket b = ranges 2b, 2b + 1), *total = the flat parameter count.

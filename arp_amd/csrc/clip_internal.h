@@ -22,4 +22,9 @@ int clip_ms_prepare(arp_clip* c, int nb, int H, int W, int use_crop, int transfo
 // Enqueue preprocess + vision tower for nb frames already in device memory, on the handle's stream: no copy out, no synchronisation, no allocation.
 // *inter [nb, layers * width] (the per-block CLS rows) and *final_feat [nb, embed] (un-normalised) stay in the handle's buffers until its next pass.
 int clip_ms_enqueue(arp_clip* c, const uint8_t* frames_dev, int nb, int H, int W, int use_crop, int transform, const float** inter, const float** final_feat);
+// clip_ms_enqueue for the fine-tune transform with the frames taken through a row table from a RESIDENT set: frame f of the pass is row rows_dev[f] of the
+// uint8 set [n_rows, H, W, 3] at set_base_dev (every entry a row of the set: the caller's contract).  No gathered copy of the frames, no crop buffer (use_crop
+// becomes the transform's source window); same clip_ms_prepare, no allocation, copy out or synchronisation, the non-graph tower dispatch.
+int clip_ms_enqueue_rows(arp_clip* c, const uint8_t* set_base_dev, const int32_t* rows_dev, int nb, int H, int W, int use_crop, const float** inter,
+                         const float** final_feat);
 }  // namespace arp

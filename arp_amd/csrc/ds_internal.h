@@ -20,4 +20,13 @@ int ds_gather_on(arp_ds* d, hipStream_t st, const int32_t* idx_dev, int B, int T
 int ds_check_goals(arp_ds* d, const int64_t* gidx, int B);
 int ds_gather_pairs_on(arp_ds* d, hipStream_t st, const int32_t* idx_dev, const int32_t* gidx_dev, int B, int T, float* frames_out, float* goals_out,
                        int32_t* action_out);
+// The fine-tune step's quads (arp_ft_feed_*).  ds_check_quads, on the HOST before any launch: the dataset lives on `device`, labels and quad bounds are set,
+// every frame row is uploaded, the actions fit `n_actions` (every id in the table was range-checked by arp_ds_set_labels), every idx is in [0, n_rows);
+// *res: the frame edge.  ds_quads_on: ONE small kernel on `st`, one lane per sample -- q = sort4(first[i], i, min(i + 1, last[i]), last[i]);
+// rows_out[g * B + b] = q[g] for g < G (3 or 4; group-major), r_out[b] = q[2] == q[3] (from all four rows whatever G is), action_out[b] = action[q[0]].
+int ds_check_quads(arp_ds* d, const int64_t* idx, int B, int G, int device, int n_actions, int* res);
+int ds_quads_on(arp_ds* d, hipStream_t st, const int32_t* idx_dev, int B, int G, int32_t* rows_out, float* r_out, int32_t* action_out);
+// the resident uint8 frames [n_rows, res, res, 3]
+const uint8_t* ds_frames_of(arp_ds* d);
+int ds_info(arp_ds* d, int* n_rows, int* res, int* device);
 }  // namespace arp

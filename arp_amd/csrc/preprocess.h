@@ -308,6 +308,39 @@ __global__ __launch_bounds__(256) void preprocess_fast_kernel(PreprocArgs a) {
 // x.float() -> torchvision resize on a tensor = bilinear, align_corners = False, no antialias (only when BOTH sides
 // differ from 224, :127) -> x / 255 -> (x - mean) / std.  Same arithmetic order as torch's upsample_bilinear2d:
 // src = (dst + 0.5) * in/out - 0.5 clamped at 0;  v = h0 (w0 v00 + w1 v01) + h1 (w0 v10 + w1 v11).
+// The arithmetic of one pixel, written ONCE for every kernel of this transform and pinned: hipcc contracts `(o + 0.5) s - 0.5` and the two-level blend into
+// fused multiply-adds as it sees fit, so two separately written expressions may differ in the last bit.  Contraction is switched off inside these
+// functions and the fused operations are spelled out -- the ones hipcc chose for preprocess_bilinear_kernel when it stood alone:
+//     f   = fma(s, o + 0.5, -0.5) clamped at 0
+//     top = fma(w0, v00, w1 v01),  bot = fma(w1, v11, w0 v10),  px = h0 top + h1 bot  (two products, one sum)
+// tests/test_finetune_feed_gpu.py holds preprocess_bilinear_rows_kernel to bitwise equality with preprocess_bilinear_kernel in all three output types.
+__device__ __forceinline__ float bilinear_coord(int o, float s, int resize) {
+#pragma clang fp contract(off)
+    const float f = resize ? __builtin_fmaf(s, (float)o + 0.5f, -0.5f) : (float)o;
+    return f < 0.f ? 0.f : f;
+}
+__device__ __forceinline__ float bilinear_blend(float h0, float h1, float w0, float w1, float v00, float v01, float v10, float v11) {
+#pragma clang fp contract(off)
+    const float top = __builtin_fmaf(w0, v00, w1 * v01), bot = __builtin_fmaf(w1, v11, w0 * v10);
+    return h0 * top + h1 * bot;
+}
+__device__ __forceinline__ float bilinear_normalise(float px, int c) {
+#pragma clang fp contract(off)
+    const float mean[3] = {0.48145466f, 0.4578275f, 0.40821073f}, stdv[3] = {0.26862954f, 0.26130258f, 0.27577711f};
+    return (px / 255.0f - mean[c]) / stdv[c];
+}
+// one output pixel of channel c from a source whose rows are `stride` bytes apart: rows yr0 / yr1 and columns x0 / x1 are relative to `src`
+__device__ __forceinline__ float bilinear_pixel(const uint8_t* src, int stride, int yr0, int yr1, float h0, float h1, int ox, float sx, int w, int c, int resize) {
+    const float fx = bilinear_coord(ox, sx, resize);
+    const int x0 = (int)fx, x1 = x0 + (x0 < w - 1 ? 1 : 0);
+    const float w1 = fx - (float)x0, w0 = 1.f - w1;
+    const float v00 = src[(size_t)yr0 * stride + x0 * 3 + c];
+    if (!resize) return bilinear_normalise(v00, c);
+    const float v01 = src[(size_t)yr0 * stride + x1 * 3 + c];
+    const float v10 = src[(size_t)yr1 * stride + x0 * 3 + c], v11 = src[(size_t)yr1 * stride + x1 * 3 + c];
+    return bilinear_normalise(bilinear_blend(h0, h1, w0, w1, v00, v01, v10, v11), c);
+}
+
 template <typename T>
 __global__ __launch_bounds__(256) void preprocess_bilinear_kernel(const uint8_t* __restrict__ frames, T* __restrict__ out, int n, int H, int W, int R,
                                                                   int P, int resize) {
@@ -319,30 +352,101 @@ __global__ __launch_bounds__(256) void preprocess_bilinear_kernel(const uint8_t*
     const int oy = (int)((i / (R / 4)) % R);
     const int c = (int)((i / ((size_t)(R / 4) * R)) % 3);
     const int frame = (int)(i / ((size_t)(R / 4) * R * 3));
-    const float mean[3] = {0.48145466f, 0.4578275f, 0.40821073f}, stdv[3] = {0.26862954f, 0.26130258f, 0.27577711f};
     const uint8_t* f = frames + (size_t)frame * H * W * 3;
     float v[4];
     const float sy = (float)H / (float)R, sx = (float)W / (float)R;
-    float fy = resize ? ((float)oy + 0.5f) * sy - 0.5f : (float)oy;
-    fy = fy < 0.f ? 0.f : fy;
+    const float fy = bilinear_coord(oy, sy, resize);
     const int y0 = (int)fy, y1 = y0 + (y0 < H - 1 ? 1 : 0);
     const float h1 = fy - (float)y0, h0 = 1.f - h1;
 #pragma unroll
-    for (int k = 0; k < 4; ++k) {
-        const int ox = ox4 * 4 + k;
-        float fx = resize ? ((float)ox + 0.5f) * sx - 0.5f : (float)ox;
-        fx = fx < 0.f ? 0.f : fx;
-        const int x0 = (int)fx, x1 = x0 + (x0 < W - 1 ? 1 : 0);
-        const float w1 = fx - (float)x0, w0 = 1.f - w1;
-        const float v00 = f[((size_t)y0 * W + x0) * 3 + c], v01 = f[((size_t)y0 * W + x1) * 3 + c];
-        const float v10 = f[((size_t)y1 * W + x0) * 3 + c], v11 = f[((size_t)y1 * W + x1) * 3 + c];
-        const float px = resize ? h0 * (w0 * v00 + w1 * v01) + h1 * (w0 * v10 + w1 * v11) : v00;
-        v[k] = (px / 255.0f - mean[c]) / stdv[c];
-    }
+    for (int k = 0; k < 4; ++k) v[k] = bilinear_pixel(f, W * 3, y0, y1, h0, h1, ox4 * 4 + k, sx, W, c, resize);
     const int ox = ox4 * 4;
     const size_t prow = ((size_t)frame * G + oy / P) * G + ox / P;
     const int kidx = c * P * P + (oy % P) * P + (ox % P);
     store4(out + prow * (size_t)(3 * P * P) + kidx, v[0], v[1], v[2], v[3]);
+}
+
+// ---- the same transform reading frames RESIDENT in HBM through a row table (the fine-tune feed, arp_ft_feed_*) -----------------------------------------
+// Frame f of the pass is row rows[f] of a uint8 set [n_set, H, W, 3]: no gathered copy of the frames, and no crop buffer either -- the centre crop of the
+// fine-tune transform is the source window (y0, x0, h, w) folded into the address.  One workgroup = one (frame, patch row): the row index is uniform (a
+// scalar load), the P output rows touch at most floor((P - 1) h / R) + 3 source rows (20 rows of 768 B for 256 -> 224 at P = 16), which are staged into LDS
+// with 16-byte loads per lane when every source row segment is 16-byte aligned (st.staged: W 3, x0 3 and w 3 multiples of 16, and the rows fit the LDS
+// budget); otherwise the pixels are read from global memory byte by byte, as preprocess_bilinear_kernel reads them.  The patch row's G x 3 x P x P outputs are
+// contiguous in the patch-major layout: the work items walk them in memory order, V values = 16 bytes per lane where P allows (V = 4 for f32, 8 for the 16-bit
+// types; 4 = 8 bytes when P is not a multiple of 8).  Per pixel the arithmetic is bilinear_pixel's, bit for bit that of preprocess_bilinear_kernel.
+struct BilinearRowsArgs {
+    const uint8_t* set;   // [n_set, H, W, 3]
+    const int32_t* rows;  // [n]: set row of each frame of the pass (every entry in [0, n_set): the caller's side of the contract)
+    void* out;            // patch-major [n * G * G, 3 * P * P] of T
+    int n, H, W;          // frames of the pass; geometry of a set frame
+    int y0, x0, h, w;     // source window inside a set frame (the whole frame, or its centre crop)
+    int R, P, resize;
+    int staged, max_rows; // stage the source rows of a patch row into LDS (16-byte loads); LDS capacity in source rows
+};
+
+template <typename T, int V>
+__global__ __launch_bounds__(256) void preprocess_bilinear_rows_kernel(BilinearRowsArgs a) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    static_assert(V == 4 || (V == 8 && sizeof(T) == 2));
+    const int tid = threadIdx.x;
+    const int G = a.R / a.P;
+    const int frame = blockIdx.x / G, pr = blockIdx.x - frame * G;
+    if (frame >= a.n) return;
+    const int row = a.rows[frame];  // (uniform)
+    const int stride = a.W * 3;
+    const uint8_t* __restrict__ src = a.set + (size_t)row * a.H * stride + (size_t)a.y0 * stride + (size_t)a.x0 * 3;  // the window's first byte
+    const float sy = (float)a.h / (float)a.R, sx = (float)a.w / (float)a.R;
+    const int oy0 = pr * a.P;
+
+    int y_lo = 0, nrows = 0;
+    const int rb = a.w * 3;
+    if (a.staged) {
+        const float f_lo = bilinear_coord(oy0, sy, a.resize), f_hi = bilinear_coord(oy0 + a.P - 1, sy, a.resize);
+        y_lo = (int)f_lo;
+        const int y_last = (int)f_hi;
+        nrows = min(y_last + (y_last < a.h - 1 ? 1 : 0) + 1 - y_lo, a.max_rows);
+        const int vpr = rb >> 4, nvec = nrows * vpr;
+        uint4* dst = reinterpret_cast<uint4*>(smem);
+        int i = tid;
+        for (; i + 768 < nvec; i += 1024) {  // four loads in flight per lane
+            uint4 v[4];
+#pragma unroll
+            for (int q = 0; q < 4; ++q) {
+                const int j = i + q * 256, r = j / vpr;
+                v[q] = *reinterpret_cast<const uint4*>(src + (size_t)(y_lo + r) * stride + (size_t)(j - r * vpr) * 16);
+            }
+#pragma unroll
+            for (int q = 0; q < 4; ++q) dst[i + q * 256] = v[q];
+        }
+        for (; i < nvec; i += 256) {
+            const int r = i / vpr;
+            dst[i] = *reinterpret_cast<const uint4*>(src + (size_t)(y_lo + r) * stride + (size_t)(i - r * vpr) * 16);
+        }
+        __syncthreads();
+    }
+
+    const int pv = a.P / V, items = G * 3 * a.P * pv;  // the patch row's outputs in memory order, V at a time
+    T* __restrict__ obase = static_cast<T*>(a.out) + ((size_t)frame * G + pr) * G * (size_t)(3 * a.P * a.P);
+    for (int i = tid; i < items; i += 256) {
+        const int pxv = i % pv, py = (i / pv) % a.P, c = (i / (pv * a.P)) % 3, g = i / (pv * a.P * 3);
+        const float fy = bilinear_coord(oy0 + py, sy, a.resize);
+        const int y0 = (int)fy, y1 = y0 + (y0 < a.h - 1 ? 1 : 0);
+        const float h1 = fy - (float)y0, h0 = 1.f - h1;
+        const int ox = g * a.P + pxv * V;
+        float v[V];
+        if (a.staged) {
+            const uint8_t* lds = reinterpret_cast<const uint8_t*>(smem);
+            const int r0 = min(y0 - y_lo, nrows - 1), r1 = min(y1 - y_lo, nrows - 1);
+#pragma unroll
+            for (int k = 0; k < V; ++k) v[k] = bilinear_pixel(lds, rb, r0, r1, h0, h1, ox + k, sx, a.w, c, a.resize);
+        } else {
+#pragma unroll
+            for (int k = 0; k < V; ++k) v[k] = bilinear_pixel(src, stride, y0, y1, h0, h1, ox + k, sx, a.w, c, a.resize);
+        }
+        T* o = obase + (size_t)i * V;
+        if constexpr (V == 4) store4(o, v[0], v[1], v[2], v[3]);
+        else *reinterpret_cast<uint4*>(o) = make_uint4(pack2<T>(v[0], v[1]), pack2<T>(v[2], v[3]), pack2<T>(v[4], v[5]), pack2<T>(v[6], v[7]));
+    }
 }
 
 }  // namespace arp

@@ -271,7 +271,11 @@ class DeviceDataset:
     def load(cls, dataset, device=0, lut=None, chunk_rows=1024, verify_rows=8):
         """Read every row's last frame (``read_last_frames_spans``: one inflate per ``num_frames`` rows), upload chunk by chunk -- the next chunk is
         read while the copy of this one runs --, set the labels.  Refuses a file whose stacked rows do not follow the window rule."""
-        if not dataset.verify(verify_rows, seed=0):
+        from .finetune_data import ProcgenActionDataset
+        action_set = isinstance(dataset, ProcgenActionDataset)  # the fine-tune step's set: frames and actions only, and it reads `[-1]` of a row, never a window
+        if action_set and len(dataset.image_keys) != 1:
+            raise ArpError("the device-resident set holds one image_key (several work on the host side only)")
+        if not action_set and not dataset.verify(verify_rows, seed=0):
             raise ArpError("this file's rows are not recorder-stacked (ob[i][-T:] differs from the frames of rows max(i - k, trajectory start)): "
                            "a device-resident dataset would train on other windows than the reference reads")
         H, W, ch = dataset.frame_shape
@@ -282,7 +286,7 @@ class DeviceDataset:
             self.dataset, self.window_size = dataset, dataset.window_size
             self.set_lut(default_lut() if lut is None else lut)
             from concurrent.futures import ThreadPoolExecutor
-            ob = dataset.store[dataset.image_key]
+            ob = dataset.store[dataset.image_keys[0] if action_set else dataset.image_key]
             bounds = list(dataset.h5_file_traj_idx)
             if bounds[-1] < dataset.n_rows:
                 bounds.append(dataset.n_rows)
@@ -300,7 +304,8 @@ class DeviceDataset:
                     r0, fr = nxt.result()
                     nxt = pool.submit(read, r0 + len(fr)) if r0 + len(fr) < dataset.n_rows else None
                     self.upload_frames(r0, fr)
-            rtg = (dataset.rtg / np.float32(dataset.scale)).astype(np.float32) if dataset.use_vl else None  # the scale is divided in here, as __getitem__ does
+            # the scale is divided in here, as __getitem__ does; the fine-tune step's set carries no return-to-go
+            rtg = (dataset.rtg / np.float32(dataset.scale)).astype(np.float32) if not action_set and dataset.use_vl else None
             self.set_labels(dataset.action, rtg, dataset.traj_start, int(dataset.action.max()) + 1 if len(dataset.action) else 1)
         except BaseException:
             self.close()
@@ -322,6 +327,23 @@ class DeviceDataset:
             raise ValueError(f"labels must have one value per row ({self.n_rows})")
         check(lib.arp_ds_set_labels(self._h, _ffi.as_ptr(a, C.c_int32), None if r is None else _ffi.as_ptr(r, C.c_float), _ffi.as_ptr(s, C.c_int32),
                                     int(n_actions)))
+
+    def set_quad_bounds(self, first, last):
+        """The per-row trajectory interval the fine-tune step's four frames are taken from (``ProcgenActionDataset.bounds()``)."""
+        f = np.require(np.asarray(first, dtype=np.int32), requirements="C")
+        l = np.require(np.asarray(last, dtype=np.int32), requirements="C")
+        if f.shape != (self.n_rows,) or l.shape != (self.n_rows,):
+            raise ValueError(f"quad bounds must have one value per row ({self.n_rows})")
+        check(lib.arp_ds_set_quad_bounds(self._h, _ffi.as_ptr(f, C.c_int32), _ffi.as_ptr(l, C.c_int32)))
+
+    def quads(self, idx, groups=4):
+        """Debug read-back of the quad kernel: ``(rows int32 [groups, B] group-major, r f32 [B], action int32 [B])`` of the processed indices ``idx``."""
+        idx = np.require(np.asarray(idx, dtype=np.int64).reshape(-1), requirements="C")
+        B, G = len(idx), int(groups)
+        rows, r, act = np.empty((max(G, 0), B), np.int32), np.empty(B, np.float32), np.empty(B, np.int32)
+        check(lib.arp_ds_quads_debug(self._h, _ffi.as_ptr(idx, C.c_int64), B, G, _ffi.as_ptr(rows, C.c_int32), _ffi.as_ptr(r, C.c_float),
+                                     _ffi.as_ptr(act, C.c_int32)))
+        return rows, r, act
 
     def set_lut(self, lut):
         t = np.require(np.asarray(lut, dtype=np.float32), requirements="C")

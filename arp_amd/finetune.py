@@ -170,10 +170,12 @@ class FinetuneTrainer:
         self._B = B
 
     def feature_buffers(self, B):
-        """Device buffers (img_inter, img_final, txt_inter, txt_final) for ``ClipLabeller.encode_multiscale_to``."""
+        """Device buffers (img_inter, img_final, txt_inter, txt_final) for ``ClipLabeller.encode_multiscale_to``; the image buffers hold the head's
+        image groups (3, or 4 for a ``goal_conditioned`` head: image0..image3)."""
         from .clip import DeviceBuffer
         c = self.cfg
-        return (DeviceBuffer(3 * B * c.d_img * 4), DeviceBuffer(3 * B * c.embed * 4), DeviceBuffer(B * c.d_txt * 4), DeviceBuffer(B * c.embed * 4))
+        G = 4 if c.goal_conditioned else 3
+        return (DeviceBuffer(G * B * c.d_img * 4), DeviceBuffer(G * B * c.embed * 4), DeviceBuffer(B * c.d_txt * 4), DeviceBuffer(B * c.embed * 4))
 
     def set_batch_device(self, bufs, r, action):
         """As set_batch, with the tower features already in HBM (image rows ordered image0 | image1 | image2)."""
@@ -420,6 +422,102 @@ class FinetunedClip:
     def close(self):
         self.head.close()
         self.towers.close()
+
+
+class FinetuneFeed:
+    """The fine-tune step fed from a device-resident demonstration set: a batch is an array of row indices.
+
+    ``trainer``: a :class:`FinetuneTrainer`; ``towers``: the frozen :class:`arp_amd.clip.ClipLabeller`; ``device_dataset``: an
+    :class:`arp_amd.dataset.DeviceDataset` holding every row's frame and action (``DeviceDataset.load(action_dataset)``); ``action_dataset``: the
+    :class:`arp_amd.finetune_data.ProcgenActionDataset` whose ``bounds()`` name each row's four frames; ``tokens``: the ONE prompt's tokens ``[1, ctx]``
+    (``None`` for -- and only for -- a ``goal_conditioned`` head).  Indices are PROCESSED indices (file rows), what
+    ``arp_amd.dataset.index_batches(len(action_dataset), B, seed, process_index=action_dataset.process_index)`` yields under ``"index"``: the
+    distribution of the reference's ``DataLoader(shuffle=True, drop_last=True)``, other numbers (documented there).  Under data parallelism the feed takes this
+    rank's already-sharded index array.
+
+    Per step the towers' stream runs the quad kernel, the fine-tune transform straight from the resident frames and the vision tower into one of two
+    slots; the head's stream copies the slot into the step's inputs and steps.  Two events per slot order the two streams (DESIGN, "fine-tune feed").
+    Not carried over: kornia's ColorJitter (as everywhere in this package), more than one prompt per sample, more than one ``image_key``."""
+
+    def __init__(self, trainer, towers, device_dataset, action_dataset, tokens=None):
+        if len(getattr(action_dataset, "image_keys", [None])) != 1:
+            raise ValueError("the device feed takes one image_key (several work on the host side only)")
+        self.trainer, self.towers, self.device_dataset, self.action_dataset = trainer, towers, device_dataset, action_dataset
+        first, last = action_dataset.bounds()
+        device_dataset.set_quad_bounds(first, last)
+        t = None
+        if tokens is not None:
+            t = np.require(np.asarray(tokens, dtype=np.int32).reshape(-1, towers.cfg.ctx), requirements="C")
+            if t.shape[0] != 1:
+                raise ValueError(f"the feed caches ONE prompt for every sample (the reference dataset yields one), not {t.shape[0]}")
+        check(lib.arp_ft_feed_attach(trainer._h, towers._h, device_dataset._h, None if t is None else _ffi.as_ptr(t, C.c_int32)))
+        self._attached = True
+
+    def close(self):
+        if getattr(self, "_attached", False) and self.trainer._h:
+            check(lib.arp_ft_feed_detach(self.trainer._h))
+        self._attached = False
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    # -- the two halves of a step -----------------------------------------------------------------------------------------------------------------
+    def stage(self, slot, index):
+        """Enqueue the batch ``index`` names into ``slot`` (0 / 1) on the towers' stream; every index is checked on the host first."""
+        idx = np.require(np.asarray(index, dtype=np.int64).reshape(-1), requirements="C")
+        check(lib.arp_ft_feed_stage_async(self.trainer._h, int(slot), _ffi.as_ptr(idx, C.c_int64), len(idx)))
+        self.trainer._B = len(idx)
+
+    def step_async(self, slot, lr):
+        check(lib.arp_ft_feed_train_step_async(self.trainer._h, int(slot), float(lr)))
+
+    def collect(self):
+        aux = np.empty(4, np.float32)
+        check(lib.arp_ft_feed_collect(self.trainer._h, _ffi.as_ptr(aux, C.c_float)))
+        return {k: float(aux[i]) for i, k in enumerate(AUX_KEYS)}
+
+    # -- what a training loop calls ---------------------------------------------------------------------------------------------------------------
+    def train_step(self, index, lr):
+        """One synchronous step on the batch ``index`` names; returns the pre-update losses (as ``FinetuneTrainer.train_step``)."""
+        self.stage(0, index)
+        self.step_async(0, lr)
+        return self.collect()
+
+    def eval_step(self, index):
+        """The forward only (the reference's ``valid_epoch``): the dict of ``FinetuneTrainer.forward``; moves no parameter."""
+        self.stage(0, index)
+        B = self.trainer._B
+        m = np.empty(4, np.float32)
+        s = np.empty((3, B), np.float32)
+        lg = np.empty((B, self.trainer.cfg.n_actions), np.float32)
+        check(lib.arp_ft_feed_forward(self.trainer._h, 0, _ffi.as_ptr(m, C.c_float), _ffi.as_ptr(s, C.c_float), _ffi.as_ptr(lg, C.c_float)))
+        return {"loss": float(m[0]), "vip_loss": float(m[1]), "id_loss": float(m[2]), "lambda_id": float(m[3]), "scores": s, "logits": lg}
+
+    def run(self, index_batches, lr):
+        """Generator over an iterable of index arrays (or the ``{"index": ...}`` dicts of ``index_batches``): one aux dict per step.  Batch k + 1 is staged
+        BEFORE step k's losses are waited for, so its tower pass runs beside step k's head -- the same numbers as :meth:`train_step` on the same stream
+        (bitwise: tests/test_finetune_feed_gpu.py).  ``lr``: a float or a callable ``step number -> float``."""
+        rate = lr if callable(lr) else (lambda _k: lr)
+        it = iter(index_batches)
+        take = lambda b: b["index"] if isinstance(b, dict) else b  # noqa: E731
+        try:
+            nxt = take(next(it))
+        except StopIteration:
+            return
+        self.stage(0, nxt)
+        k = 0
+        while nxt is not None:
+            self.step_async(k & 1, rate(k))
+            try:
+                nxt = take(next(it))
+                self.stage((k + 1) & 1, nxt)
+            except StopIteration:
+                nxt = None
+            yield self.collect()
+            k += 1
 
 
 def flops_per_sample(cfg):

@@ -516,6 +516,32 @@ int arp_dt_upload_batch_index_pairs_async(arp_dt* h, int slot, arp_ds* ds, const
 int arp_dt_set_batch_index_pairs(arp_dt* h, arp_ds* ds, const int64_t* idx, const int64_t* goal_idx, int B);
 /* Debug read-back of a pair batch: frames_out and goals_out f32 [B, window, res, res, 3], action_out int32 [B, window]; each output may be NULL. */
 int arp_ds_gather_pairs_debug(arp_ds* ds, const int64_t* idx, const int64_t* goal_idx, int B, int window, float* frames_out, float* goals_out, int32_t* action_out);
+/* The fine-tune step's quads.  arp_ds_set_quad_bounds: first / last int32 [n_rows], the trajectory interval each row's four frames are taken from
+ * (ProcgenActionDataset.bounds()); 0 <= first <= last < n_rows is checked for every row, first <= row <= last is NOT (the rows behind the last done flag
+ * carry trajectory 0's interval: the reference's quirk).  Sample i reads q = sort(first[i], i, min(i + 1, last[i]), last[i]); r = q[2] == q[3]; its action
+ * is action[q[0]].  arp_ds_quads_debug: read-back of the quad kernel for B indices and G = 3 / 4 groups -- rows_out int32 [G, B] (group-major), r_out f32 [B],
+ * action_out int32 [B]; the same host checks as a staging; a store past the end of an output is detected on the device and is an error. */
+int arp_ds_set_quad_bounds(arp_ds* ds, const int32_t* first, const int32_t* last);
+int arp_ds_quads_debug(arp_ds* ds, const int64_t* idx, int B, int G, int32_t* rows_out, float* r_out, int32_t* action_out);
+/* The feed: fine-tune batches built on the device from a resident demonstration set (finetune_module/action_finetune_data_procgen.py's four frames per
+ * sample).  A batch is B row indices of `ds` (processed indices: file rows), which needs its frames, labels and quad bounds (arp_ds_set_quad_bounds).
+ * arp_ft_feed_attach checks device and geometry, runs the text tower's multi-scale export once for the ONE prompt every sample shares (tokens [1, ctx]; NULL
+ * for -- and only for -- a goal_conditioned head) and keeps it in HBM; the two slots' buffers come with the first staging of a size.  Everything belongs to
+ * the head handle (arp_debug_live counts it); arp_ft_feed_detach and arp_ft_destroy give it back.  towers and ds must outlive the attachment.
+ * arp_ft_feed_stage_async(slot 0 / 1): on the HOST first -- labels, quad bounds and every frame row present, every idx in [0, n_rows), the set's actions fit
+ * the head, groups * B <= the towers' max_batch (groups = 3, or 4 for a goal_conditioned head) -- then on the TOWERS' stream: index upload, wait for the
+ * slot's `consumed` event, the quad kernel, the fine-tune transform reading the resident frames through the row table + the vision tower for groups * B
+ * frames, the export copied into the slot, the slot's `ready` event.  No host synchronisation.
+ * arp_ft_feed_train_step_async: the head's stream waits for `ready`, copies the slot into the step's inputs (the cached prompt row under every sample),
+ * records `consumed`, runs the existing step (all-reduce included when a communicator exists).  A staged batch is taken by ONE step or forward: stepping a
+ * slot twice, or before it is staged, is refused.  arp_ft_feed_collect waits for the head's stream and reads the step's aux4 (as arp_ft_train_step).
+ * arp_ft_feed_forward: the same staging, then arp_ft_forward (the reference's valid_epoch).  No hipGraph anywhere: two streams ordered by events. */
+int arp_ft_feed_attach(arp_ft* h, arp_clip* towers, arp_ds* ds, const int32_t* tokens);
+int arp_ft_feed_detach(arp_ft* h);
+int arp_ft_feed_stage_async(arp_ft* h, int slot, const int64_t* idx, int B);
+int arp_ft_feed_train_step_async(arp_ft* h, int slot, float lr);
+int arp_ft_feed_collect(arp_ft* h, float* aux4);
+int arp_ft_feed_forward(arp_ft* h, int slot, float* metrics4, float* scores, float* logits);
 
 /* ---- row N4: a device-resident rollout session ------------------------------------------------------
  * batch_rollout's inner loop (arp_dt/envs/rollout_procgen.py:96-166, driven by create_test_step, main_procgen.py:171-229) for n_envs independent
@@ -768,6 +794,10 @@ int arp_op_preprocess_forms(const uint8_t* frames, int n, int H, int W, int use_
 /* The fine-tune transform (preprocess_bilinear_kernel) with the grid and the resize rule of a pass: patch-major output in the mode's type; a frame with
  * exactly one side at res is refused as a pass refuses it. */
 int arp_op_preprocess_bilinear(const uint8_t* frames, int n, int H, int W, int res, int patch, int mode, void* out);
+/* The same transform reading its frames through a row table (preprocess_bilinear_rows_kernel, the feed's): frame f of the output is row rows[f] of the
+ * n_set frames [n_set, H, W, 3]; use_crop: the centre crop of side W / 2 as the kernel's source window.  A row outside the set is refused on the host. */
+int arp_op_preprocess_bilinear_rows(const uint8_t* set_frames, int n_set, const int32_t* rows, int n, int H, int W, int use_crop, int res, int patch, int mode,
+                                    void* out);
 /* crop_u8_kernel: out [n, cs, cs, 3] = frames[:, y0 : y0 + cs, x0 : x0 + cs, :], the window inside the frame */
 int arp_op_crop_u8(const uint8_t* frames, int n, int H, int W, int y0, int x0, int cs, uint8_t* out);
 /* The M3AE encoder's patchify: images f32 NHWC [n, res, res, 3] -> rows "b (h p1) (w p2) c -> b (h w) (p1 p2 c)".  form 0 / 1 / 2: f32 / bf16 / binary16
